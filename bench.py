@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — samples/sec of the DLRM training step on MI355X (BASELINE.json metric), one JSON line.
 
-    python bench.py [--gpus 1] [--steps K] [--warmup W]
+    python bench.py [--gpus 1] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,10 @@ region.  A "step" = forward + loss + zero_grad + backward + optimizer.step — t
 times between its time_wrap calls (dlrm_s_pytorch.py:1558-1626).  For N > 1 the global batch stays
 65536 (strong scaling): tables are sharded table-wise over the ranks, pooled embeddings cross one RCCL
 all-to-all per direction, MLP gradients one DDP all-reduce (extend_distributed.py semantics).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`ms_per_step` = one timed step); `--full` adds
+everything measured or checked beside it (parity check, box calibration, per-kernel roofline, baselines, ...).  `--dump-outputs DIR`
+writes what the last timed step computed as .npy files, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -82,8 +87,7 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--alts", action="store_true",
                     help="also measure the alternative schedules beside the headline (bf16x6 arithmetic, two-kernel lookups, 2 HIP streams; "
-                         "N > 1: the other all-to-all schedule and the other dense-gradient all-reduce).  Off by default: the default run is "
-                         "the headline + roofline + cpu_baseline only")
+                         "N > 1: the other all-to-all schedule and the other dense-gradient all-reduce).  Off by default, also under --full")
     ap.add_argument("--offsets", default="fresh", choices=["fresh", "tagged", "resident"],
                     help="what the timed steps receive as bag offsets.  fresh (default): a NEW untagged offsets tensor object every step, as the "
                          "reference loop's loader + dlrm_wrap deliver (dlrm_s_pytorch.py:129-145,1541-1548) — the fused lookup path then "
@@ -169,7 +173,22 @@ def parse():
     ap.add_argument("--mlp-arith", default=os.environ.get("DLRM_MLP_ARITH", "f32"), choices=["f32", "bf16x6", "bf16"],
                     help="f32: native fp32 MFMA; bf16x6: exact 3-term bf16 split of the fp32 operands, 6 bf16 MFMA products, "
                          "fp32 accumulation (fp32 round-off class)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: pre-run parity check, box calibration, per-kernel timers + roofline, "
+                         "tagged-offsets leg, stand-alone embedding kernel, high-row check, reference timed region, full-size parity, "
+                         "scaling model, RCCL self-check, update-in-backward leg, collective timings (N > 1) and the CPU baseline legs.  "
+                         "Without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the loss, the "
+                         "model output, every dense parameter and a fixed, seeded sample of rows of every large one (embedding tables: "
+                         "plus rows the last batch looked up; the row numbers as <name>.sampled_rows.npy, float64); at most 64 MB in all")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only; each of these is a default-on extra that --full restores
+        for name in ("no_parity_check", "no_box_calibration", "no_kernel_timers", "no_standalone_emb", "no_high_row_check",
+                     "no_reference_region", "no_full_size_parity", "no_rccl_selfcheck", "no_alt_update_in_backward", "no_cpu_baseline"):
+            setattr(args, name, True)
+    return args
 
 
 def measure_box(device, quick=False):
@@ -658,6 +677,42 @@ def rccl_selfcheck(timeout=300):
         return {"ok": False, "error": "%s: %s" % (type(e).__name__, str(e)[:300])}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1024          # rows kept of a parameter with more than DUMP_FULL_ELEMS elements
+DUMP_FULL_ELEMS = 1 << 20
+DUMP_LOOKED_UP_ROWS = 256        # embedding tables: rows of the first lookups of the last batch, beside the seeded sample
+
+
+def dump_outputs(out_dir, loss, Z, model, last_idx=None):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files — loss, model output (Z), and every parameter after
+    the step's update (whole when small; else a fixed seeded sample of its rows, for the embedding tables plus the rows of the first
+    lookups of the last batch, so that the sparse update is visible).  The same arguments give the same files' shapes and row sets."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    if Z is not None:
+        arrays["Z"] = Z.detach().float()
+    for name, p in model.named_parameters():
+        w = p.detach()
+        if w.numel() <= DUMP_FULL_ELEMS or w.dim() < 2:
+            arrays[name] = w.float()
+            continue
+        n = w.size(0)
+        rng = np.random.default_rng(zlib.crc32(name.encode()))       # (str.__hash__ is salted per process)
+        rows = rng.choice(n, size=min(n, DUMP_SAMPLE_ROWS), replace=False)
+        parts = name.split(".")
+        if last_idx is not None and len(parts) == 3 and parts[0] == "emb_l" and parts[2] == "weight":
+            looked_up = last_idx[int(parts[1])][:DUMP_LOOKED_UP_ROWS].cpu().numpy()
+            rows = np.concatenate([rows, looked_up])
+        rows = np.unique(rows)
+        arrays[name + ".sampled_rows"] = torch.from_numpy(rows.astype(np.float64))
+        arrays[name + ".sample"] = w[torch.from_numpy(rows).to(w.device)].float()
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def source_hashes():
     import hashlib
     csrc = os.path.join(ROOT, "dlrm_amd", "csrc")
@@ -981,8 +1036,11 @@ def main():
         opt.zero_grad()
         E.backward(one)
         opt.step()
+        if args.dump_outputs:
+            last_out["Z"] = Z                   # --dump-outputs: the model output of the latest eager step
         return E
 
+    last_out = {}
     graphed = None
     if args.graph:
         if N > 1:
@@ -1063,8 +1121,13 @@ def main():
     if args.gc == "off":
         gc.enable()
     iota = {k: ops.IOTA_STATS[k] - iota0[k] for k in iota0}
+    if args.dump_outputs and rank == 0:
+        last_i = args.warmup + args.steps                 # the index the last timed step() was called with
+        last_idx = batches[last_i % len(batches)][2] if (N == 1 and not hot) else None
+        dump_outputs(args.dump_outputs, loss, graphed.out if graphed is not None else last_out.get("Z"), model, last_idx)
+    last_out.clear()
     tagged_ms = None
-    if fresh_off is not None and args.offsets == "fresh" and graphed is None:
+    if args.full and fresh_off is not None and args.offsets == "fresh" and graphed is None:
         # the same steps on offsets tensors that carry their producer's proof (what dlrm_amd.datagen / CriteoBinBatches hand out): the
         # difference to the headline is what the per-step device proof of untagged tensors costs; reported beside it, never instead
         keep_timers, ops.timers = ops.timers, None
@@ -1158,7 +1221,7 @@ def main():
     # algorithmic figure counts bytes the caches serve (small tables, duplicate rows), so `achieved` can exceed what the HBM interface
     # moved: `traffic_gbps` is the rate the memory system really sustained and `frac_traffic` prices THAT against the 8 TB/s peak.
     # Nothing is capped: an algorithmic frac_of_measured_peak above 1 means cache hits, and the traffic columns show it.
-    pmc = load_pmc_traffic() if (N == 1 and args.workload == "criteo_terabyte" and not args.batch and not args.row_cap) else None
+    pmc = load_pmc_traffic() if (args.full and N == 1 and args.workload == "criteo_terabyte" and not args.batch and not args.row_cap) else None
     for name, k in kernels.items():
         t = pmc["kernels"].get(name) if pmc else None
         if t and not t.get("stale") and t.get("traffic_bytes") and "ms_per_step" in k:
@@ -1235,7 +1298,7 @@ def main():
                                         "traffic_gbps (PMC HBM bytes / time)", "frac_traffic (traffic_gbps / 8000)"],
                 "embedding_hbm_gbps": emb_gbps, "box": box}
 
-    klaunch = kernel_launches_per_step() if (N == 1 and args.workload == "criteo_terabyte" and graphed is None) else None
+    klaunch = kernel_launches_per_step() if (args.full and N == 1 and args.workload == "criteo_terabyte" and graphed is None) else None
     for name, k in kernels.items():
         k["c_abi_calls_per_step"] = k.get("launches_per_step")          # ("launches_per_step" stays as the older name of the same number: C-ABI calls)
         k["kernel_launches_per_step"] = (klaunch or {}).get("by_category", {}).get(name)
@@ -1288,7 +1351,7 @@ def main():
                              "Criteo-Kaggle shapes with the small-batch tower kernels); the whole-step HIP graph (--graph) replays them with one launch"},
         "box": box,
         "parity_check": parity,
-        "kernel_timing": "HIP events on the launch stream, one per change of launch category (a run of consecutive launches of one category "
+        "kernel_timing": None if not timed_steps else "HIP events on the launch stream, one per change of launch category (a run of consecutive launches of one category "
                          "is one event pair; dlrm_amd.ops.KernelTimers), on %d of the %d timed steps.  An event is a queue barrier (~5 us) charged to "
                          "the category it closes: the categories sum to %.3f ms against the %.3f ms step (+%.1f %%) — every frac of this line is "
                          "that much pessimistic, none optimistic" % (timed_steps, args.steps, cat_sum, ms, (cat_sum / ms - 1) * 100 if ms else 0),
@@ -1403,7 +1466,7 @@ def main():
             result["full_size_parity"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
             torch.cuda.empty_cache()
         partial["json"] = json.dumps(result)
-    if N == 1 and not hot:
+    if args.full and N == 1 and not hot:
         try:
             result["scaling_model"] = scaling_model(kernels, ms, B, len(rows), D, result.get("embedding_kernel_standalone"))
         except Exception as e:                              # noqa: BLE001
@@ -1573,41 +1636,42 @@ def main():
             except Exception as e:                       # noqa: BLE001 - never allowed to break the headline line
                 result["alt_dense_sync"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         # ---- the collectives alone, at the step's exact sizes, HIP events on the stream they are enqueued on ---------------
-        try:
-            watchdog(args.hang_timeout, "collective micro-measurements")
-            Tl_, D_ = len(local_tables), D
-            splits = model.n_emb_per_rank or [Tl_] * N
-            send = torch.empty(B * Tl_ * D_, device=device)
-            recv = torch.empty((B // N) * sum(splits) * D_, device=device)
-            send_counts = [(B // N) * Tl_ * D_] * N
-            recv_counts = [(B // N) * t * D_ for t in splits]
-            flat = torch.empty(sum(p.numel() for p in model.bot_l.parameters()) + sum(p.numel() for p in model.top_l.parameters()), device=device)
+        if args.full:
+            try:
+                watchdog(args.hang_timeout, "collective micro-measurements")
+                Tl_, D_ = len(local_tables), D
+                splits = model.n_emb_per_rank or [Tl_] * N
+                send = torch.empty(B * Tl_ * D_, device=device)
+                recv = torch.empty((B // N) * sum(splits) * D_, device=device)
+                send_counts = [(B // N) * Tl_ * D_] * N
+                recv_counts = [(B // N) * t * D_ for t in splits]
+                flat = torch.empty(sum(p.numel() for p in model.bot_l.parameters()) + sum(p.numel() for p in model.top_l.parameters()), device=device)
 
-            def timed(fn, iters=10):
-                for _ in range(3):
-                    fn()
-                torch.cuda.synchronize()
-                torch.distributed.barrier()
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(iters):
-                    fn()
-                b.record()
-                torch.cuda.synchronize()
-                t = torch.tensor([a.elapsed_time(b) / iters], device=device, dtype=torch.float64)
-                torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-                return float(t.item())
-            a2a_f = timed(lambda: torch.distributed.all_to_all_single(recv, send, recv_counts, send_counts))
-            a2a_b = timed(lambda: torch.distributed.all_to_all_single(send, recv, send_counts, recv_counts))
-            ar = timed(lambda: torch.distributed.all_reduce(flat))
-            off_node = send.numel() * 4 * (N - 1) / N
-            result["collectives"] = {
-                "a2a_fwd_ms": a2a_f, "a2a_bwd_ms": a2a_b, "allreduce_ms": ar, "timing": "HIP events, max over ranks, 10 back-to-back calls",
-                "a2a_send_bytes_per_rank": send.numel() * 4, "a2a_bytes_leaving_rank": off_node,
-                "a2a_fwd_gbps_per_rank": off_node / (a2a_f * 1e-3) / 1e9, "allreduce_bytes": flat.numel() * 4,
-                "in_step": "2 all-to-alls (forward + backward) + the dense-gradient all-reduce of each tower (--dense-sync %s) per step" % args.dense_sync}
-        except Exception as e:                           # noqa: BLE001 - diagnostic section, never breaks the headline line
-            result["collectives"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+                def timed(fn, iters=10):
+                    for _ in range(3):
+                        fn()
+                    torch.cuda.synchronize()
+                    torch.distributed.barrier()
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(iters):
+                        fn()
+                    b.record()
+                    torch.cuda.synchronize()
+                    t = torch.tensor([a.elapsed_time(b) / iters], device=device, dtype=torch.float64)
+                    torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+                    return float(t.item())
+                a2a_f = timed(lambda: torch.distributed.all_to_all_single(recv, send, recv_counts, send_counts))
+                a2a_b = timed(lambda: torch.distributed.all_to_all_single(send, recv, send_counts, recv_counts))
+                ar = timed(lambda: torch.distributed.all_reduce(flat))
+                off_node = send.numel() * 4 * (N - 1) / N
+                result["collectives"] = {
+                    "a2a_fwd_ms": a2a_f, "a2a_bwd_ms": a2a_b, "allreduce_ms": ar, "timing": "HIP events, max over ranks, 10 back-to-back calls",
+                    "a2a_send_bytes_per_rank": send.numel() * 4, "a2a_bytes_leaving_rank": off_node,
+                    "a2a_fwd_gbps_per_rank": off_node / (a2a_f * 1e-3) / 1e9, "allreduce_bytes": flat.numel() * 4,
+                    "in_step": "2 all-to-alls (forward + backward) + the dense-gradient all-reduce of each tower (--dense-sync %s) per step" % args.dense_sync}
+            except Exception as e:                           # noqa: BLE001 - diagnostic section, never breaks the headline line
+                result["collectives"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         result["distributed"] = dist_info
         if selftest:
             result["selftest"] = "DLRM_BENCH_SELFTEST_GLOO=1: all ranks on ONE GPU over gloo with host-staged exchanges — control-flow test, NOT a measurement"

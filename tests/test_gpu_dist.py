@@ -388,7 +388,7 @@ def _run_bench_n2(extra_env, extra_args, timeout):
 def test_bench_two_rank_control_flow(dense_sync):
     """headline (reference exchange schedule) + alternative exchange schedule + the other dense-gradient synchronisation + collective
     timings + process-group report, end to end through torchrun, as the driver launches it"""
-    d, _ = _run_bench_n2({}, ["--steps", "3", "--hang-timeout", "120", "--dense-sync", dense_sync, "--alts"], 600)
+    d, _ = _run_bench_n2({}, ["--steps", "3", "--hang-timeout", "120", "--dense-sync", dense_sync, "--alts", "--full"], 600)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["scaling"] == "strong" and "selftest" in d
     assert dense_sync in d["config"]["parallelism"] and d["config"]["a2a_chunks"] == 1
     assert d["alt_a2a_pipelined"]["value"] > 0 and d["alt_a2a_pipelined"]["a2a_chunks"] > 1
@@ -434,7 +434,7 @@ def test_bench_two_rank_sharded_multihot_control_flow():
     slices through kjt_input_dist (id re-layouts as block-copy kernels), fused row-wise Adagrad, DDP towers — end to end through
     torchrun as the driver launches it (one GPU, gloo rendezvous, reduced sizes: control flow, not a measurement)."""
     d, _ = _run_bench_n2({}, ["--steps", "3", "--hang-timeout", "120", "--workload", "mlperf_v2_multihot", "--interaction", "dot",
-                              "--mlp-arith", "f32"], 600)
+                              "--mlp-arith", "f32", "--full"], 600)
     assert d["n_gpus"] == 2 and d["value"] > 0 and "selftest" in d and np.isfinite(d["final_loss"])
     assert "planned sharding x2" in d["config"]["parallelism"] and d["config"]["optimizer"] == "rwsadagrad"
     dist = d["distributed"]

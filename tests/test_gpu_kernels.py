@@ -223,8 +223,6 @@ def test_lookup_sort_is_stable_and_exact(case, monkeypatch):
 @pytest.mark.parametrize("B", [67, 5000])
 def test_interact_fwd_bwd(F, D, itself, B):
     from dlrm_amd import ops
-    if B > 67 and D != 128:
-        pytest.skip("large batch only exercises the multi-sample-per-wave loop of the D = 128 path")
     rng = np.random.default_rng(F * 1000 + D)
     feat = rng.standard_normal((B, F, D)).astype(np.float32)
     want = O.interact_fwd(feat, itself)

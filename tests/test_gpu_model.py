@@ -1070,6 +1070,9 @@ def test_kernel_timers_runs_partition_the_step(towers, monkeypatch):
     ops.timers = ops.KernelTimers()
     try:
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        # the stream spins while the host enqueues the instrumented step: a host stall (garbage collection, a busy host) cannot
+        # leave the GPU idle between a and b, so the window holds the step's GPU work only
+        torch.cuda._sleep(50_000_000)
         a.record()
         ops.timers.enabled = True
         step()
@@ -1089,3 +1092,39 @@ def test_kernel_timers_runs_partition_the_step(towers, monkeypatch):
     assert s["emb_fwd"]["calls"] == 1 and s["emb_bwd_sgd"]["calls"] == 1 and s["interact_fwd"]["calls"] == 1
     total = sum(v["total_ms"] for v in s.values())
     assert 0.5 * wall <= total <= 1.05 * wall, (total, wall, s)
+
+
+def test_bench_dump_outputs_of_two_plain_runs_match(tmp_path):
+    """`bench.py --dump-outputs DIR` (plain run, reduced sizes): the last timed step's loss — the line's final_loss —, model output and
+    parameters land as float32 .npy files (row numbers of a sample in float64) under the 64 MB limit, and two runs with the same
+    arguments give the same files, shapes and sampled rows, and the same values up to fp32 summation order."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 4096
+    lines, dirs = [], [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                            "--row-cap", "50000", "--dump-outputs", str(d)], cwd=root, capture_output=True, text=True, timeout=600)
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and out, (r.returncode, r.stderr[-3000:])
+        lines.append(json.loads(out[-1]))
+    assert all(l["kernel_timing"] is None and l["steps"] == 3 and l["ms_per_step"] > 0 for l in lines)
+    files = sorted(os.listdir(dirs[0]))
+    assert files == sorted(os.listdir(dirs[1]))
+    assert {"loss.npy", "Z.npy", "bot_l.0.weight.npy", "top_l.0.weight.npy", "emb_l.0.weight.sample.npy", "emb_l.0.weight.sampled_rows.npy",
+            "emb_l.5.weight.npy"} <= set(files)
+    total = 0
+    for f in files:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        total += a.nbytes
+        assert a.dtype == b.dtype == (np.float64 if f.endswith(".sampled_rows.npy") else np.float32), f
+        assert a.shape == b.shape and np.all(np.isfinite(a)), f
+        if f.endswith(".sampled_rows.npy"):
+            assert np.array_equal(a, b), f
+        else:
+            np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-6, err_msg=f)
+    assert total <= 64 << 20
+    assert np.load(os.path.join(dirs[0], "Z.npy")).shape == (B, 1)
+    assert np.load(os.path.join(dirs[0], "loss.npy")).tolist() == [np.float32(lines[0]["final_loss"])]

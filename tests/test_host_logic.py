@@ -646,3 +646,46 @@ def test_bench_help_renders():
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "--gpus" in r.stdout and "--mlp-arith" in r.stdout, r.stderr[-500:]
+
+
+def test_bench_dump_outputs_files_dtypes_sample_and_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (dump_outputs): loss + model output + every parameter as float32 .npy, small parameters whole, a large
+    one as a fixed seeded row sample (an embedding table: plus the rows the last batch looked up) with its row numbers in float64; the
+    same call gives the same files, shapes and row sets; more than the byte limit is an error, not a truncated dump."""
+    import importlib
+    import sys as _sys
+    monkeypatch.setattr(_sys, "argv", ["bench.py"])
+    bench = importlib.import_module("bench")
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            torch.manual_seed(0)
+            self.emb_l = torch.nn.ModuleList([torch.nn.EmbeddingBag(bench.DUMP_FULL_ELEMS // 4 + 7, 8), torch.nn.EmbeddingBag(10, 8)])
+            self.top_l = torch.nn.Linear(5, 1)
+
+    net = Net()
+    big_rows = net.emb_l[0].weight.size(0)
+    idx = torch.tensor([[3, big_rows - 1, 3] + [5] * 300, [1, 2, 3] + [4] * 300])
+    loss, Z = torch.tensor(0.25), torch.randn(6, 1)
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        bench.dump_outputs(str(d), loss, Z, net, idx)
+    files = sorted(os.listdir(dirs[0]))
+    assert files == sorted(os.listdir(dirs[1])) == sorted(
+        ["loss.npy", "Z.npy", "emb_l.0.weight.sample.npy", "emb_l.0.weight.sampled_rows.npy", "emb_l.1.weight.npy",
+         "top_l.weight.npy", "top_l.bias.npy"])
+    got = {f: np.load(os.path.join(dirs[0], f)) for f in files}
+    for f, a in got.items():
+        assert a.dtype == (np.float64 if f.endswith(".sampled_rows.npy") else np.float32), f
+        assert np.array_equal(a, np.load(os.path.join(dirs[1], f))), f
+    assert got["loss.npy"].tolist() == [0.25] and np.array_equal(got["Z.npy"], Z.numpy())
+    rows = got["emb_l.0.weight.sampled_rows.npy"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < big_rows
+    assert {3, 5, big_rows - 1} <= set(rows.tolist()) and len(rows) <= bench.DUMP_SAMPLE_ROWS + bench.DUMP_LOOKED_UP_ROWS
+    assert np.array_equal(got["emb_l.0.weight.sample.npy"], net.emb_l[0].weight.detach().numpy()[rows])
+    assert np.array_equal(got["emb_l.1.weight.npy"], net.emb_l[1].weight.detach().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    with pytest.raises(RuntimeError, match="exceed"):
+        bench.dump_outputs(str(tmp_path / "c"), loss, Z, net, idx)
+    assert not (tmp_path / "c").exists() or not os.listdir(tmp_path / "c")

@@ -4,7 +4,7 @@ OUT=gpurun_out/${1:-selftest}; mkdir -p $OUT
 export DLRM_BENCH_SELFTEST_GLOO=1
 for sync in ddp flat; do
 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 4 --warmup 2 \
-    --batch 8192 --row-cap 200000 --hang-timeout 120 --dense-sync $sync > $OUT/n2_$sync.json 2> $OUT/n2_$sync.err
+    --batch 8192 --row-cap 200000 --hang-timeout 120 --dense-sync $sync --full > $OUT/n2_$sync.json 2> $OUT/n2_$sync.err
 echo "rc=$? ($sync)"; grep -v "amdgpu.ids\|watchdog [0-9]" $OUT/n2_$sync.err | tail -8 | cut -c1-300
 python - <<PY
 import json

@@ -3,8 +3,8 @@
 # Everything lands under gpurun_out/<out-tag>/ (merged back by gpurun).  Stages:
 #   smoke            __graft_entry__.smoke()
 #   tests[=EXPR]     pytest -m gpu over tests/ (EXPR = a -k expression; files with FILES="tests/a.py tests/b.py")
-#   bench[=ARGS]     python bench.py ARGS            -> bench.json (default line: headline + roofline + cpu_baseline)
-#   quick[=ARGS]     bench.py without baselines / parity / calibration, ARGS appended -> quick_<n>.json (repeatable)
+#   bench[=ARGS]     python bench.py --full ARGS     -> bench.json (full line: headline + roofline + cpu_baseline)
+#   quick[=ARGS]     bench.py --full without baselines / parity / calibration, ARGS appended -> quick_<n>.json (repeatable)
 #   rocprof          rocprofv3 --kernel-trace --stats of the quick headline + per-kernel tables + one-step trace
 #   pmc              FETCH_SIZE / WRITE_SIZE passes (separate, kernel-trace only) folded into pmc_traffic.json
 #   pmcm             MFMA-busy / LDS-conflict passes -> pmc_mfma_lds.md
@@ -16,7 +16,7 @@ OUT=gpurun_out/${1:?out tag}; shift
 mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
-QUICK="--no-cpu-baseline --no-parity-check --no-box-calibration --no-rccl-selfcheck --no-high-row-check --no-full-size-parity --no-reference-region --no-alt-update-in-backward"
+QUICK="--full --no-cpu-baseline --no-parity-check --no-box-calibration --no-rccl-selfcheck --no-high-row-check --no-full-size-parity --no-reference-region --no-alt-update-in-backward"
 n=0
 summ() { python - "$1" <<'PY'
 import json, sys
@@ -40,7 +40,7 @@ for stage in "$@"; do
   case $name in
     smoke) timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "== smoke rc=$?"; tail -1 $OUT/smoke.log ;;
     tests) timeout ${TEST_TIMEOUT:-2400} python -m pytest ${FILES:-tests} -m gpu -x -q ${arg:+-k "$arg"} > $OUT/pytest_$n.log 2>&1; echo "== tests rc=$? ($arg)"; tail -4 $OUT/pytest_$n.log ;;
-    bench) timeout 1200 python bench.py $arg > $OUT/bench.json 2> $OUT/bench.err; echo "== bench rc=$? ($arg)"; summ $OUT/bench.json ;;
+    bench) timeout 1200 python bench.py --full $arg > $OUT/bench.json 2> $OUT/bench.err; echo "== bench rc=$? ($arg)"; summ $OUT/bench.json ;;
     quick) timeout 600 python bench.py --steps 20 --warmup 5 $QUICK $arg > $OUT/quick_$n.json 2> $OUT/quick_$n.err; echo "== quick_$n rc=$? ($arg)"; summ $OUT/quick_$n.json ;;
     rocprof)
       ( cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d $ROOT/$OUT/rocprof -o bench -- python $ROOT/bench.py --steps 10 --warmup 3 $QUICK $arg > $ROOT/$OUT/rocprof_bench.json 2> $ROOT/$OUT/rocprof.err ); echo "== rocprof rc=$?"
@@ -63,8 +63,8 @@ for stage in "$@"; do
       python tools/pmc_mfma_table.py $OUT > $OUT/pmc_mfma_lds.md; head -14 $OUT/pmc_mfma_lds.md
       find $OUT -name "*.csv" -size +6M -delete ;;
     secondary)
-      timeout 400 python bench.py --workload mlperf_v2_multihot --interaction dot --steps 10 --warmup 3 --no-rccl-selfcheck > $OUT/bench_mlperf_v2_dot.json 2> /dev/null; echo "== v2 dot"; summ $OUT/bench_mlperf_v2_dot.json
-      timeout 400 python bench.py --workload mlperf_v2_multihot --interaction dcn --steps 10 --warmup 3 --no-rccl-selfcheck > $OUT/bench_mlperf_v2_dcn.json 2> /dev/null; echo "== v2 dcn"; summ $OUT/bench_mlperf_v2_dcn.json
+      timeout 400 python bench.py --full --workload mlperf_v2_multihot --interaction dot --steps 10 --warmup 3 --no-rccl-selfcheck > $OUT/bench_mlperf_v2_dot.json 2> /dev/null; echo "== v2 dot"; summ $OUT/bench_mlperf_v2_dot.json
+      timeout 400 python bench.py --full --workload mlperf_v2_multihot --interaction dcn --steps 10 --warmup 3 --no-rccl-selfcheck > $OUT/bench_mlperf_v2_dcn.json 2> /dev/null; echo "== v2 dcn"; summ $OUT/bench_mlperf_v2_dcn.json
       for v in "tb_rwsadagrad:--optimizer rwsadagrad" "tb_bf16:--mlp-arith bf16" "tb_bf16x6:--mlp-arith bf16x6" "tb_graph:--graph" \
                "kaggle_graph:--workload criteo_kaggle --steps 300 --warmup 20 --graph" "kaggle_eager:--workload criteo_kaggle --steps 300 --warmup 20"; do
         t=${v%%:*}; a=${v#*:}

@@ -1,6 +1,6 @@
 # fresh (proof inside every timed step) vs producer-tagged offsets as SEPARATE processes, interleaved: what the proof costs without the
 # in-process ordering of bench.py's own comparison leg
-Q="--no-cpu-baseline --no-parity-check --no-box-calibration --no-rccl-selfcheck --no-high-row-check --no-standalone-emb --steps 30 --warmup 5"
+Q="--full --no-cpu-baseline --no-parity-check --no-box-calibration --no-rccl-selfcheck --no-high-row-check --no-standalone-emb --steps 30 --warmup 5"
 for r in 1 2 3; do
   for m in fresh tagged resident; do
     python bench.py $Q --offsets $m 2>/dev/null | python -c "
