@@ -80,7 +80,7 @@ class UniformBatchGenerator:
                 o_k = off[k]
                 if onehot:
                     # gen_onehot_kernel writes bag start b for bag b: the producer's own proof of "one lookup per bag"
-                    # (ops.offsets_are_iota then needs no device pass and no synchronisation for this tensor object)
+                    # (ops.offsets_are_iota, dlrm_amd/iota.py, then needs no device pass and no synchronisation for this tensor object)
                     ops.mark_one_lookup_per_bag(o_k)
                 lS_o.append(o_k)
                 lS_i.append(idx[k, :counts[k]])

@@ -219,7 +219,7 @@ class DLRM_Net(nn.Module):
         # 26 tables: the interaction kernels gather the embedding rows themselves (dlrm_interact_fwd_gather / _bwd_gather) and
         # apply_emb's pooled-embedding buffer is never written or re-read — bit-identical results, forward 0.21 ms instead of 0.34 +
         # 0.26 at Criteo-Terabyte shapes (profiles/round3).  Taken when every table has exactly B lookups AND the bag starts are proven
-        # to be 0, 1, 2, ... (ops.offsets_are_iota: one device pass + one synchronisation per distinct offsets tensor object, cached;
+        # to be 0, 1, 2, ... (ops.offsets_are_iota, dlrm_amd/iota.py: one device pass + one synchronisation per distinct offsets tensor object, cached;
         # a ragged batch with nnz == B — an empty bag next to a two-lookup bag — takes the two kernels like every other multi-hot
         # input).  The kernels still verify the bag starts themselves and report a violation through the index-error block.
         self.fuse_emb_interact = os.environ.get("DLRM_FUSE_EMB_INTERACT", "1") == "1"
@@ -530,7 +530,7 @@ class DLRM_Net(nn.Module):
                 and not any(w is not None for w in (self.v_W_l or []))):
             bags = self._bags(lS_o, lS_i, None)
             # nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the
-            # reference computes it): ops.offsets_are_iota proves offsets == arange(B) on the device, once per offsets tensor
+            # reference computes it): ops.offsets_are_iota (dlrm_amd/iota.py) proves offsets == arange(B) on the device, once per offsets tensor
             # object (None = undecided, only while a HIP graph is being captured: GraphedTrainStep proves every incoming batch).
             if all(n == B for n in bags.nnz) and all(e.weight.data_ptr() % 16 == 0 for e in self.emb_l):
                 # True / None (capturing): the fused kernels alone.  A tensor nobody vouched for: its proof is a device pass whose verdict

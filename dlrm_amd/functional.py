@@ -18,7 +18,7 @@ import torch
 from torch.autograd import Function
 
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID
+from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, _ld
 
 
 # optional: weight-gradient GEMMs on a side stream, concurrent with the data-gradient chain (env DLRM_OVERLAP_WGRAD=1).
@@ -148,10 +148,6 @@ def _grad_out(p: torch.Tensor) -> torch.Tensor:
         return torch.empty_like(p)
     ARENA_BUSY.add(key)
     return v
-
-
-def _ld(t: torch.Tensor) -> int:
-    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
 
 
 def _round4(n: int) -> int:
@@ -611,7 +607,7 @@ class GatherInteractFunction(Function):
 
     @staticmethod
     def forward(ctx, sink, D, self_interaction, bags, x, *weights):
-        # `bags.iota_flag` (a device int32, ops.offsets_iota_state): whether the batch really has ONE lookup per bag is known on the device
+        # `bags.iota_flag` (a device int32, ops.offsets_iota_state in dlrm_amd/iota.py): whether the batch really has ONE lookup per bag is known on the device
         # only — nnz == B does not prove it.  Both implementations are enqueued with that launch predicate (ABI 16): the fused kernel runs if
         # the flag is zero; dlrm_emb_fwd + the plain interaction (the reference's apply_emb + interact_features as two kernels, through a pooled
         # buffer that then has to live until backward) run if it is not.  The launches that do not run return at once; the host never waits.

@@ -176,7 +176,7 @@ class GraphedTrainStep:
 
     def _prove_one_lookup_per_bag(self, lS_o, lS_i) -> None:
         """The fused lookup + interaction kernels are only valid for offsets == arange(B).  Eager steps prove that per offsets tensor
-        (ops.offsets_are_iota); inside a capture nothing can synchronise and the static offsets buffer is rewritten before every
+        (ops.offsets_are_iota, dlrm_amd/iota.py); inside a capture nothing can synchronise and the static offsets buffer is rewritten before every
         replay, so the proof is made HERE, on the caller's tensors, before they are copied.  A batch that fails it turns the fused
         path off for this model and drops the captured graph (the next call re-captures with the two kernels)."""
         model = self.model
@@ -263,8 +263,7 @@ class GraphedTrainStep:
         self._lrs = self._current_lrs()
         # the graph holds raw pointers into the cached scratch workspaces: pin those tensors so that a later, larger
         # request elsewhere (which replaces the cache entry) cannot free memory the replays still use
-        self._pinned_ws = [w for (d_, _), w in list(ops._emb_ws.items()) + list(ops._wgrad_ws.items()) if d_ == dev]
-        self._pinned_ws += [w for (d_, _), w in ops._tower_ws.items() if d_ == dev]
+        self._pinned_ws = [w for (_, d_, _), w in ops._scratch_ws.items() if d_ == dev]
         self.captures += 1
         self._exec, self._raw_arrays = None, None
         if self.raw:
@@ -339,7 +338,7 @@ class GraphedTrainStep:
             # after every replay", so that is what happens here before the static inputs are touched again.  At
             # Criteo-Terabyte sizes the GPU is the bottleneck (the wait costs one launch latency per step); at launch-bound
             # sizes the replay has finished long before the host gets here.
-            ops.wait_spinning(torch.cuda.current_stream(X.device))      # (polled, not slept on: ops._wait_event_spinning)
+            ops.wait_spinning(torch.cuda.current_stream(X.device))      # (polled, not slept on: see ops.wait_spinning)
             self._replayed = False
         self._prove_one_lookup_per_bag(lS_o, lS_i)
         if self.static is None:

@@ -8,6 +8,7 @@ buffer) are used in place.  Anything else raises — there is no CPU/eager fallb
 from __future__ import annotations
 
 import os
+import time
 
 import ctypes as C
 from typing import List, Optional, Sequence, Union
@@ -313,11 +314,16 @@ def _weights_desc(weights: Sequence[torch.Tensor]):
     return int(D), _lib.ptr_array([w.data_ptr() for w in weights]), _lib.i64_array([w.size(0) for w in weights])
 
 
-def _pred_args(pred):
-    """pred = None | (flag, nonzero): flag a device int32 tensor; the launch runs iff (flag != 0) == bool(nonzero) (include/dlrm_hip.h, ABI 16)"""
+def _pred_args(pred, stream: C.c_void_p):
+    """pred = (flag, nonzero): flag a device int32 tensor; the launch runs iff (flag != 0) == bool(nonzero) (include/dlrm_hip.h, ABI 16).
+    stream: what _stream() gave the launch.  A flag of iota.offsets_iota_state names the stream its pool was allocated under; used on
+    another one it is recorded there, torch's convention for memory used off its allocating stream (dlrm_amd/iota.py, rule 3)."""
     flag, nonzero = pred
     if flag.dtype != torch.int32 or not flag.is_cuda or flag.numel() < 1:
         raise RuntimeError("dlrm_amd: a launch predicate is a device int32 tensor")
+    home = getattr(flag, "dlrm_pool_stream", None)
+    if home is not None and home != (stream.value or 0):
+        flag.record_stream(torch.cuda.current_stream())
     return C.c_void_p(flag.data_ptr()), int(bool(nonzero))
 
 
@@ -329,30 +335,41 @@ def emb_fwd(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor, 
     if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
         raise RuntimeError("dlrm_amd: emb_fwd shape mismatch")
     err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
+    st = _stream(out)
     # (a predicated launch belongs to the step's fused lookup + interaction: same timing category, so the three launches are ONE run)
     with _timed("emb_fwd" if pred is None else "emb_interact_fwd"):
         if pred is None:
             rc = lib.dlrm_emb_fwd(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                  bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, _stream(out))
+                                  bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, st)
         else:
             rc = lib.dlrm_emb_fwd_pred(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                       bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred), _stream(out))
+                                       bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_emb_fwd")
     return out
 
 
-_emb_ws = {}   # (device, stream) -> cached workspace of the sort-based updates.  Per stream, like the split-k slabs: kernels of one stream
-               # are ordered, so one workspace suffices — and a workspace allocated under one stream is never handed to kernels of another
-               # (the caching allocator orders re-use of freed memory within the allocating stream only)
+_scratch_ws = {}   # (kind, device, stream) -> cached uint8 scratch: "emb" the workspace of the sort-based updates, "wgrad" the split-K slabs
+                   # of the weight gradients, "tower" the slabs of tower_wgrad.  Per stream: kernels of one stream are ordered, so one buffer per
+                   # kind suffices — and a buffer allocated under one stream is never handed to kernels of another (the caching allocator
+                   # orders re-use of freed memory within the allocating stream only).  Grow-only; GraphedTrainStep pins what a capture used.
 
 
-def _emb_workspace(need: int, device) -> torch.Tensor:
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _emb_ws.get(key)
+def _scratch(kind: str, need: int, device, stream: Optional[int] = None) -> Optional[torch.Tensor]:
+    """stream: the handle of the stream of the TENSORS' device the launch uses (default: its current stream)"""
+    if kind == "wgrad" and need <= 0:
+        return None                      # (no split-K for this shape: linear_head_bwd takes it as "outside the fast path")
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream if stream is None else stream)
+    ws = _scratch_ws.get(key)
     if ws is None or ws.numel() < need:
-        ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
-        _emb_ws[key] = ws
+        ws = _scratch_ws[key] = torch.empty(max(int(need), 256) if kind == "emb" else int(need), dtype=torch.uint8, device=device)
     return ws
+
+
+def _emb_sort_bytes(lib, bags: "BagBatch", rows) -> int:
+    need = lib.dlrm_emb_bwd_workspace_bytes(bags.T, bags._nnz, rows)
+    if need < 0:
+        raise RuntimeError("dlrm_amd: dlrm_emb_bwd_workspace_bytes failed")
+    return need
 
 
 def sort_is_graph_safe(weights: Sequence[torch.Tensor], bags: BagBatch) -> bool:
@@ -370,10 +387,7 @@ def sort_lookups(rows: Sequence[int], bags: BagBatch):
     lib = _lib.load()
     dev = bags.keep[0].device
     rows_a = _lib.i64_array([int(r) for r in rows])
-    need = lib.dlrm_emb_bwd_workspace_bytes(bags.T, bags._nnz, rows_a)
-    if need < 0:
-        raise RuntimeError("dlrm_amd: dlrm_emb_bwd_workspace_bytes failed")
-    ws = _emb_workspace(need, dev)
+    ws = _scratch("emb", _emb_sort_bytes(lib, bags, rows_a), dev)
     L = int(sum(bags.nnz))
     pos = torch.empty(L, dtype=torch.int32, device=dev)
     keys = torch.empty(L, dtype=torch.int64, device=dev)
@@ -423,10 +437,7 @@ def emb_bwd_sgd(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Ten
         raise RuntimeError("dlrm_amd: emb_bwd_sgd shape mismatch")
     ws_ptr, ws_bytes = None, 0
     if mode == UPD_SORTED:
-        need = lib.dlrm_emb_bwd_workspace_bytes(bags.T, bags._nnz, rows)
-        if need < 0:
-            raise RuntimeError("dlrm_amd: dlrm_emb_bwd_workspace_bytes failed")
-        ws = _emb_workspace(need, dout.device)
+        ws = _scratch("emb", _emb_sort_bytes(lib, bags, rows), dout.device)
         ws_ptr, ws_bytes = C.c_void_p(ws.data_ptr()), ws.numel()
     lr_v, lr_p = _lr_args(lr)
     with _timed("emb_bwd_sgd"):
@@ -459,10 +470,7 @@ def emb_presort(weights: Sequence[torch.Tensor], bags: BagBatch, lr: LrLike, pre
     lib = _lib.load()
     D, wp, rows = _weights_desc(weights)
     dev = weights[0].device
-    need = lib.dlrm_emb_bwd_workspace_bytes(bags.T, bags._nnz, rows)
-    if need < 0:
-        raise RuntimeError("dlrm_amd: dlrm_emb_bwd_workspace_bytes failed")
-    ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(_emb_sort_bytes(lib, bags, rows), 256), dtype=torch.uint8, device=dev)
     mask = torch.empty(bags.B, dtype=torch.int32, device=dev)
     with _timed("emb_bwd_sgd"):
         rc = lib.dlrm_emb_presort(bags.T, bags.B, rows, bags._idx, bags._off, bags._nnz, bags.idx_bits, C.c_void_p(ws.data_ptr()), ws.numel(),
@@ -480,10 +488,11 @@ def emb_bwd_sgd_presorted(weights: Sequence[torch.Tensor], bags: BagBatch, dout:
     if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T:
         raise RuntimeError("dlrm_amd: emb_bwd_sgd_presorted shape mismatch")
     lr_v, lr_p = _lr_args(pre.lr)
-    flag, nz = _pred_args(pre.pred) if pre.pred is not None else (None, 0)
+    st = _stream(dout)
+    flag, nz = _pred_args(pre.pred, st) if pre.pred is not None else (None, 0)
     with _timed("emb_bwd_sgd"):
         rc = lib.dlrm_emb_bwd_sgd_presorted(bags.T, bags.B, D, wp, rows, bags._nnz, C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p,
-                                            C.c_void_p(pre.ws.data_ptr()), pre.ws.numel(), int(bool(skip_singles)), flag, nz, _stream(dout))
+                                            C.c_void_p(pre.ws.data_ptr()), pre.ws.numel(), int(bool(skip_singles)), flag, nz, st)
     _lib.check(rc, "dlrm_emb_bwd_sgd_presorted")
 
 
@@ -505,7 +514,7 @@ def emb_bwd_rowwise_adagrad(weights: Sequence[torch.Tensor], states: Sequence[to
     need = lib.dlrm_emb_adagrad_workspace_bytes(bags.T, D, bags._nnz, rows)
     if need < 0:
         raise RuntimeError("dlrm_amd: dlrm_emb_adagrad_workspace_bytes failed")
-    ws = _emb_workspace(need, dout.device)
+    ws = _scratch("emb", need, dout.device)
     lr_v, lr_p = _lr_args(lr)
     with _timed("emb_bwd_adagrad"):
         rc = lib.dlrm_emb_bwd_rowwise_adagrad(bags.T, bags.B, D, wp, sp, rows, bags._idx, bags._off, bags._nnz,
@@ -569,123 +578,20 @@ def interact_fwd(blocks: Sequence[torch.Tensor], D: int, self_interaction: bool,
     F = len(ptrs)
     if R.size(0) != B or R.size(1) < interact_out_width(F, D, self_interaction):
         raise RuntimeError("dlrm_amd: interact_fwd output shape mismatch")
+    st = _stream(R)
     with _timed("interact_fwd" if pred is None else "emb_interact_fwd"):
         if pred is None:
             rc = lib.dlrm_interact_fwd(B, F, D, _lib.ptr_array(ptrs), _lib.i64_array(lds), int(self_interaction),
-                                       C.c_void_p(R.data_ptr()), _ld(R), _stream(R))
+                                       C.c_void_p(R.data_ptr()), _ld(R), st)
         else:
             rc = lib.dlrm_interact_fwd_pred(B, F, D, _lib.ptr_array(ptrs), _lib.i64_array(lds), None, None, None, 64, int(self_interaction),
-                                            C.c_void_p(R.data_ptr()), _ld(R), None, *_pred_args(pred), _stream(R))
+                                            C.c_void_p(R.data_ptr()), _ld(R), None, *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_interact_fwd")
     return R
 
 
 def gather_ok(F: int, D: int) -> bool:
     return bool(_lib.load().dlrm_interact_gather_ok(F, D))
-
-
-# --- "one lookup per bag" proof for the fused lookup + interaction path -------------------------------------------------------
-# nnz == B does not prove offsets == arange(B): EmbeddingBag accepts an empty bag next to a two-lookup bag (dlrm_s_pytorch.py:453-457)
-# and the reference computes that input correctly.  The proof is one pass over the offsets on the device + ONE stream
-# synchronisation, paid once per distinct offsets tensor: the verdict is cached on the tensor OBJECT (weak reference, so a recycled
-# address can never alias) together with its in-place version counter.
-_iota_cache: dict = {}          # id(tensor) -> (weakref, _version, verdict)
-IOTA_STATS = {"checked": 0, "cached": 0, "tagged": 0, "device_predicates": 0, "host_us": 0.0, "wait_us": 0.0}
-_IOTA_TAG = "_dlrm_one_lookup_per_bag"      # attribute a PRODUCER sets on an offsets tensor it wrote as 0, 1, ..., B-1 (value: t._version)
-
-
-def mark_one_lookup_per_bag(t: torch.Tensor) -> torch.Tensor:
-    """Producer-side proof: whoever WROTE the bag starts as 0, 1, ..., B-1 (dlrm_amd.datagen with one fixed lookup per bag,
-    CriteoBinBatches, Multihot over all-ones hot sizes — by construction of their kernels) tags the tensor object, and
-    `offsets_are_iota` then needs neither a device pass nor a synchronisation for it.  The tag holds the tensor's in-place version
-    counter, so a later versioned write voids it; views and copies are new objects and carry no tag (they take the device proof) — and
-    because Python attributes DO travel with copy.deepcopy / pickle, the tag also names the object and the storage address it was given
-    for: a deep copy or an unpickled tensor is a different object at a different address and is therefore untagged.  What no tag
-    can see is a write that bypasses the version counter (`.data` writes, a foreign kernel): producers tag tensors their own kernel has just
-    written and hand them over; the fused kernels still verify every bag start they use and report a violation through the error block."""
-    setattr(t, _IOTA_TAG, (t._version, id(t), t.data_ptr()))
-    return t
-
-
-def _iota_tagged(t: torch.Tensor) -> bool:
-    return getattr(t, _IOTA_TAG, None) == (t._version, id(t), t.data_ptr())
-
-
-def _iota_cached(t: torch.Tensor):
-    e = _iota_cache.get(id(t))
-    if e is not None and e[0]() is t and e[1] == t._version:
-        return e[2]
-    return None
-
-
-def _iota_remember(t: torch.Tensor, verdict: bool) -> None:
-    import weakref
-    if len(_iota_cache) > 256:
-        for k in [k for k, e in _iota_cache.items() if e[0]() is None]:
-            del _iota_cache[k]
-        if len(_iota_cache) > 256:
-            _iota_cache.clear()
-    _iota_cache[id(t)] = (weakref.ref(t), t._version, verdict)
-
-
-class _IotaProof:
-    """a proof in flight: the check kernel runs on the proof stream behind `entry` (an event of the caller's stream recorded when
-    the proof was requested); `done` fires when the verdict is in `flag` (pinned host memory the kernel counts violations into)"""
-    __slots__ = ("srcs", "keep", "flag", "done", "t0")
-
-
-_proof_streams: dict = {}        # device index -> the (high-priority) stream the check kernels run on
-_iota_flag_pool: dict = {}       # device index -> list of free pinned int32[1] flags
-
-
-def offsets_are_iota_start(lS_o):
-    """First half of the proof.  Returns True / False when the verdict is already known (producer tag, cached per tensor object), None
-    while a HIP graph is being captured (undecided: GraphedTrainStep proves every incoming batch before the replay), else a handle for
-    `offsets_are_iota_finish`.  The check kernel is NOT put on the caller's stream: it runs on a proof stream that waits only for what
-    the caller's stream holds at this moment (the tensor's producer, by torch's stream convention), so everything the caller enqueues
-    AFTER this call — DLRM_Net runs the whole bottom tower here — is queued behind nothing of the proof and keeps the GPU busy while
-    the host waits for the verdict."""
-    srcs = [lS_o] if isinstance(lS_o, torch.Tensor) else list(lS_o)
-    if all(_iota_tagged(t) for t in srcs):
-        IOTA_STATS["tagged"] += 1
-        return True
-    verdicts = [True if _iota_tagged(t) else _iota_cached(t) for t in srcs]
-    if all(v is not None for v in verdicts):
-        IOTA_STATS["cached"] += 1
-        return all(verdicts)
-    dev = srcs[0].device
-    if torch.cuda.is_current_stream_capturing():
-        return None
-    import time as _time
-    h = _IotaProof()
-    h.t0 = _time.perf_counter()
-    ptrs, keep = [], []
-    for t in srcs:
-        if not t.is_cuda or t.dtype not in (torch.int64, torch.int32) or t.dtype != srcs[0].dtype:
-            raise RuntimeError("dlrm_amd: offsets must be int32/int64 GPU tensors of one dtype")
-        if t.dim() == 2:
-            if t.stride(1) != 1 and t.size(1) > 1:
-                t = t.contiguous()
-            ptrs += [t.data_ptr() + k * t.stride(0) * t.element_size() for k in range(t.size(0))]
-        else:
-            t = t.contiguous()
-            ptrs.append(t.data_ptr())
-        keep.append(t)
-    B = srcs[0].size(-1)
-    pool = _iota_flag_pool.setdefault(dev.index, [])
-    flag = pool.pop() if pool else torch.zeros(1, dtype=torch.int32).pin_memory()
-    flag[0] = 0
-    cur = torch.cuda.current_stream(dev)
-    ps = _proof_streams.get(dev.index)
-    if ps is None:
-        ps = _proof_streams[dev.index] = torch.cuda.Stream(device=dev, priority=-1)
-    ps.wait_event(cur.record_event())
-    rc = _lib.load().dlrm_offsets_are_iota(len(ptrs), B, _lib.ptr_array(ptrs), 64 if srcs[0].dtype == torch.int64 else 32,
-                                           C.c_void_p(flag.data_ptr()), C.c_void_p(ps.cuda_stream))
-    _lib.check(rc, "dlrm_offsets_are_iota")
-    h.srcs, h.keep, h.flag, h.done = srcs, keep, flag, ps.record_event()
-    IOTA_STATS["host_us"] += (_time.perf_counter() - h.t0) * 1e6
-    return h
 
 
 # Host wait for an event that ends the host's run-ahead once per step: POLL it (hipEventQuery) instead of sleeping on it.
@@ -696,124 +602,15 @@ def offsets_are_iota_start(lS_o):
 SPIN_WAIT_S = 0.0 if os.environ.get("DLRM_SPIN_WAIT", "1") == "0" else 0.05        # DLRM_SPIN_WAIT=0: sleep on the event (A/B)
 
 
-def _wait_event_spinning(ev, limit_s: Optional[float] = None) -> None:
+def wait_spinning(ev, limit_s: Optional[float] = None) -> None:
     """ev: a torch.cuda.Event or a torch.cuda.Stream (both have query() / synchronize()); limit_s: how long to poll before sleeping after all"""
-    import time as _time
     if ev.query():
         return
-    end = _time.perf_counter() + (SPIN_WAIT_S if limit_s is None else (limit_s if SPIN_WAIT_S > 0 else 0.0))
+    end = time.perf_counter() + (SPIN_WAIT_S if limit_s is None else (limit_s if SPIN_WAIT_S > 0 else 0.0))
     while not ev.query():
-        if _time.perf_counter() > end:
+        if time.perf_counter() > end:
             ev.synchronize()
             return
-
-
-wait_spinning = _wait_event_spinning
-
-
-# ---- the verdict left on the DEVICE (ABI 16): no host wait at all ---------------------------------------------------------------------------
-_FLAG_POOL = 1024
-_iota_flag_slots: dict = {}     # device index -> [device int32 pool, pinned int32 pool, next slot]: a slot is used ONCE (zeroed at allocation, never re-armed)
-_iota_unresolved: list = []     # (event, pinned slot, [weak references to the tensor objects]): proofs whose host-visible verdict has not been looked at yet
-
-
-def _iota_drain() -> None:
-    """remember the verdicts of finished device proofs (event.query(): no wait) — a tensor object that comes back is then known"""
-    keep = []
-    for ev, host, refs in _iota_unresolved:
-        if ev.query():
-            ok = int(host[0]) == 0
-            for r in refs:                     # (weak references: the proof keeps no offsets tensor alive; an object that is gone needs no verdict)
-                t = r()
-                if t is not None:
-                    _iota_remember(t, ok)
-        else:
-            keep.append((ev, host, refs))
-    _iota_unresolved[:] = keep[-64:]           # (bounded: a verdict nobody came back for within 64 steps is dropped — the next encounter proves again)
-
-
-def offsets_iota_state(lS_o):
-    """What the caller of the fused lookup + interaction path needs to know about `lS_o`, WITHOUT waiting for the device:
-      True / False    the verdict is known (producer tag, or this tensor object was proven earlier);
-      None            a HIP graph is being captured (undecided: GraphedTrainStep proves every incoming batch before the replay);
-      a device int32  the proof was enqueued on the CURRENT stream (dlrm_offsets_iota_flags: number of bags whose start differs from their
-                      number) — the caller enqueues both implementations with that launch predicate (GatherInteractFunction) and never
-                      waits; the host-visible copy of the verdict is looked at whenever a later call finds its event complete."""
-    srcs = [lS_o] if isinstance(lS_o, torch.Tensor) else list(lS_o)
-    _iota_drain()
-    if all(_iota_tagged(t) for t in srcs):
-        IOTA_STATS["tagged"] += 1
-        return True
-    verdicts = [True if _iota_tagged(t) else _iota_cached(t) for t in srcs]
-    if all(v is not None for v in verdicts):
-        IOTA_STATS["cached"] += 1
-        return all(verdicts)
-    dev = srcs[0].device
-    if torch.cuda.is_current_stream_capturing():
-        return None
-    import time as _time
-    t0 = _time.perf_counter()
-    ptrs, keep = [], []
-    for t in srcs:
-        if not t.is_cuda or t.dtype not in (torch.int64, torch.int32) or t.dtype != srcs[0].dtype:
-            raise RuntimeError("dlrm_amd: offsets must be int32/int64 GPU tensors of one dtype")
-        if t.dim() == 2:
-            if t.stride(1) != 1 and t.size(1) > 1:
-                t = t.contiguous()
-            ptrs += [t.data_ptr() + k * t.stride(0) * t.element_size() for k in range(t.size(0))]
-        else:
-            t = t.contiguous()
-            ptrs.append(t.data_ptr())
-        keep.append(t)
-    slots = _iota_flag_slots.get(dev.index)
-    if slots is None or slots[2] >= _FLAG_POOL:
-        slots = _iota_flag_slots[dev.index] = [torch.zeros(_FLAG_POOL, dtype=torch.int32, device=dev),
-                                               torch.zeros(_FLAG_POOL, dtype=torch.int32).pin_memory(), 0]
-    k = slots[2]
-    slots[2] = k + 1
-    flag, host = slots[0][k:k + 1], slots[1][k:k + 1]
-    with _timed("iota_proof"):
-        rc = _lib.load().dlrm_offsets_iota_flags(len(ptrs), srcs[0].size(-1), _lib.ptr_array(ptrs), 64 if srcs[0].dtype == torch.int64 else 32,
-                                                 C.c_void_p(flag.data_ptr()), C.c_void_p(host.data_ptr()), _stream(srcs[0]))
-    _lib.check(rc, "dlrm_offsets_iota_flags")
-    import weakref
-    _iota_unresolved.append((torch.cuda.current_stream(dev).record_event(), host, [weakref.ref(t) for t in srcs]))
-    IOTA_STATS["device_predicates"] = IOTA_STATS.get("device_predicates", 0) + 1
-    IOTA_STATS["host_us"] += (_time.perf_counter() - t0) * 1e6
-    del keep
-    return flag
-
-
-def offsets_are_iota_finish(h) -> bool:
-    """Second half: wait for the check kernel alone (an event of the proof stream, not a stream synchronisation of the caller's) and
-    read the verdict.  The offsets tensors stayed alive in the handle until here."""
-    if not isinstance(h, _IotaProof):
-        return h
-    import time as _time
-    t0 = _time.perf_counter()
-    _wait_event_spinning(h.done)
-    ok = int(h.flag[0]) == 0
-    _iota_flag_pool[h.srcs[0].device.index].append(h.flag)
-    IOTA_STATS["checked"] += 1
-    # one verdict for the whole set: each tensor of a list is remembered with it (a False verdict of the set is re-examined only if
-    # the same objects come back, and then it is False again)
-    for t in h.srcs:
-        _iota_remember(t, ok)
-    IOTA_STATS["wait_us"] += (_time.perf_counter() - t0) * 1e6
-    h.keep = h.srcs = None
-    return ok
-
-
-def offsets_are_iota(lS_o):
-    """True iff every table's bag starts are 0, 1, ..., B-1 (with nnz == B: exactly one lookup per bag).  `lS_o` is what the caller
-    passed to the module (a stacked [T, B] tensor or a list of [B] tensors).  Free for tensors their PRODUCER tagged
-    (`mark_one_lookup_per_bag`: dlrm_amd.datagen, CriteoBinBatches, Multihot know it by construction) and for tensor objects seen
-    before (verdict cached per object + in-place version; a write that does not bump `_version` — `t.data.copy_`, a collective or a
-    custom kernel writing into a reused buffer — is not noticed here: the fused kernels still verify every bag start themselves and
-    report a violation through the index-error block, so reused offsets buffers must be updated through versioned in-place ops).
-    Any other tensor takes one device pass + a host wait for it (`offsets_are_iota_start` / `_finish`).  While a HIP graph is being
-    captured no wait is possible: returns None (undecided) — GraphedTrainStep proves the incoming batch before every replay."""
-    return offsets_are_iota_finish(offsets_are_iota_start(lS_o))
 
 
 def _gather_desc(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
@@ -840,14 +637,15 @@ def interact_fwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
     _req(R, "R", ndim=2)
     if R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
         raise RuntimeError("dlrm_amd: interact_fwd_gather shape mismatch")
+    st = _stream(R)
     with _timed("emb_interact_fwd"):
         if pred is None:
             rc = lib.dlrm_interact_fwd_gather(bags.B, F, D, p, ld, gidx, goff, rows, bags.idx_bits, int(self_interaction),
-                                              C.c_void_p(R.data_ptr()), _ld(R), C.c_void_p(_err_block(R.device).data_ptr()), _stream(R))
+                                              C.c_void_p(R.data_ptr()), _ld(R), C.c_void_p(_err_block(R.device).data_ptr()), st)
         else:
             rc = lib.dlrm_interact_fwd_pred(bags.B, F, D, p, ld, gidx, goff, rows, bags.idx_bits, int(self_interaction),
                                             C.c_void_p(R.data_ptr()), _ld(R), C.c_void_p(_err_block(R.device).data_ptr()),
-                                            *_pred_args(pred), _stream(R))
+                                            *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_interact_fwd_gather")
     return R
 
@@ -866,22 +664,23 @@ def interact_bwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
     _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
     dptrs = [dx.data_ptr()] + [dE.data_ptr() + 4 * k * D for k in range(bags.T)]
     dlds = [_ld(dx)] + [_ld(dE)] * bags.T
+    st = _stream(dR)
     with _timed("emb_interact_bwd"):
         if presorted is not None:
             lr_v, lr_p = _lr_args(presorted.lr)
-            flag, nz = _pred_args(pred) if pred is not None else (None, 0)
+            flag, nz = _pred_args(pred, st) if pred is not None else (None, 0)
             rc = lib.dlrm_interact_bwd_gather_sgd(bags.B, F, D, p, ld, gidx, goff, rows, bags.idx_bits, int(self_interaction),
                                                   C.c_void_p(dR.data_ptr()), _ld(dR), _lib.ptr_array(dptrs), _lib.i64_array(dlds),
                                                   C.c_void_p(presorted.mask.data_ptr()), lr_v, lr_p,
-                                                  C.c_void_p(_err_block(dR.device).data_ptr()), flag, nz, _stream(dR))
+                                                  C.c_void_p(_err_block(dR.device).data_ptr()), flag, nz, st)
         elif pred is None:
             rc = lib.dlrm_interact_bwd_gather(bags.B, F, D, p, ld, gidx, goff, rows, bags.idx_bits, int(self_interaction),
                                               C.c_void_p(dR.data_ptr()), _ld(dR), _lib.ptr_array(dptrs), _lib.i64_array(dlds),
-                                              C.c_void_p(_err_block(dR.device).data_ptr()), _stream(dR))
+                                              C.c_void_p(_err_block(dR.device).data_ptr()), st)
         else:
             rc = lib.dlrm_interact_bwd_pred(bags.B, F, D, p, ld, gidx, goff, rows, bags.idx_bits, int(self_interaction),
                                             C.c_void_p(dR.data_ptr()), _ld(dR), _lib.ptr_array(dptrs), _lib.i64_array(dlds),
-                                            C.c_void_p(_err_block(dR.device).data_ptr()), *_pred_args(pred), _stream(dR))
+                                            C.c_void_p(_err_block(dR.device).data_ptr()), *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_interact_bwd_gather")
 
 
@@ -898,15 +697,15 @@ def interact_bwd(blocks: Sequence[torch.Tensor], D: int, self_interaction: bool,
     if B != B2 or len(ptrs) != len(dptrs) or dR.size(0) != B:
         raise RuntimeError("dlrm_amd: interact_bwd shape mismatch")
     F = len(ptrs)
+    st = _stream(dR)
     with _timed("interact_bwd" if pred is None else "emb_interact_bwd"):
         if pred is None:
             rc = lib.dlrm_interact_bwd(B, F, D, _lib.ptr_array(ptrs), _lib.i64_array(lds), int(self_interaction),
-                                       C.c_void_p(dR.data_ptr()), _ld(dR), _lib.ptr_array(dptrs), _lib.i64_array(dlds),
-                                       _stream(dR))
+                                       C.c_void_p(dR.data_ptr()), _ld(dR), _lib.ptr_array(dptrs), _lib.i64_array(dlds), st)
         else:
             rc = lib.dlrm_interact_bwd_pred(B, F, D, _lib.ptr_array(ptrs), _lib.i64_array(lds), None, None, None, 64, int(self_interaction),
                                             C.c_void_p(dR.data_ptr()), _ld(dR), _lib.ptr_array(dptrs), _lib.i64_array(dlds), None,
-                                            *_pred_args(pred), _stream(dR))
+                                            *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_interact_bwd")
 
 
@@ -1161,27 +960,13 @@ def linear_bwd_weight_bf16x6(dZ3: torch.Tensor, X3: torch.Tensor, dW: torch.Tens
         raise RuntimeError("dlrm_amd: linear_bwd_weight_bf16x6 shape mismatch")
     if dbias is not None:
         _req(dbias, "dbias", ndim=1)
-    ws = _wgrad_workspace(lib.dlrm_linear_bwd_weight_bf16_workspace_bytes(M, N, K), dW.device)
+    ws = _scratch("wgrad", lib.dlrm_linear_bwd_weight_bf16_workspace_bytes(M, N, K), dW.device)
     with _timed("linear_bwd_weight"):
         rc = lib.dlrm_linear_bwd_weight_bf16x6(M, N, K, K_store, C.c_void_p(dZ3.data_ptr()), N, M * N, C.c_void_p(X3.data_ptr()), Kx, M * Kx,
                                                C.c_void_p(dW.data_ptr()), _ld(dW), C.c_void_p(dbias.data_ptr()) if dbias is not None else None,
                                                int(bool(accumulate)), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(dW))
     _lib.check(rc, "dlrm_linear_bwd_weight_bf16x6")
     return dW
-
-
-_wgrad_ws = {}   # (device, stream) -> cached split-K workspace (kernels of one stream are ordered, so one slab set suffices)
-
-
-def _wgrad_workspace(need: int, device) -> Optional[torch.Tensor]:
-    if need <= 0:
-        return None
-    key = (device, torch.cuda.current_stream(device).cuda_stream)        # (the stream of the TENSORS' device: what the launch uses)
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(int(need), dtype=torch.uint8, device=device)
-        _wgrad_ws[key] = ws
-    return ws
 
 
 def linear_bwd_weight(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, dbias: Optional[torch.Tensor] = None,
@@ -1200,7 +985,7 @@ def linear_bwd_weight(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, dbias
         _req(dbias, "dbias", ndim=1)
         if dbias.numel() != N:
             raise RuntimeError("dlrm_amd: linear_bwd_weight dbias size mismatch")
-    ws = _wgrad_workspace(lib.dlrm_linear_bwd_weight_workspace_bytes(M, N, K), dY.device) if use_workspace else None
+    ws = _scratch("wgrad", lib.dlrm_linear_bwd_weight_workspace_bytes(M, N, K), dY.device) if use_workspace else None
     with _timed("linear_bwd_weight"):
         common = (C.c_void_p(dY.data_ptr()), _ld(dY), C.c_void_p(X.data_ptr()), _ld(X),
                   C.c_void_p(dW.data_ptr()), _ld(dW),
@@ -1230,7 +1015,7 @@ def linear_head_bwd(dY: torch.Tensor, Y: Optional[torch.Tensor], act: int, X: to
         _req(Y, "Y", ndim=2)
     if dX is not None:
         _req(dX, "dX", ndim=2)
-    ws = _wgrad_workspace(lib.dlrm_linear_bwd_weight_workspace_bytes(M, 1, K), dY.device)
+    ws = _scratch("wgrad", lib.dlrm_linear_bwd_weight_workspace_bytes(M, 1, K), dY.device)
     if ws is None:
         return False
     with _timed("linear_bwd_weight"):
@@ -1268,7 +1053,7 @@ def linear_bwd_weight_bf16(dZ16: torch.Tensor, X16: torch.Tensor, dW: torch.Tens
         raise RuntimeError("dlrm_amd: linear_bwd_weight_bf16 shape mismatch")
     if dbias is not None:
         _req(dbias, "dbias", ndim=1)
-    ws = _wgrad_workspace(lib.dlrm_linear_bwd_weight_bf16_workspace_bytes(M, N, K), dW.device)
+    ws = _scratch("wgrad", lib.dlrm_linear_bwd_weight_bf16_workspace_bytes(M, N, K), dW.device)
     with _timed("linear_bwd_weight"):
         rc = lib.dlrm_linear_bwd_weight_bf16(M, N, K, K_store, C.c_void_p(dZ16.data_ptr()), dZ16.stride(0), C.c_void_p(X16.data_ptr()), X16.stride(0),
                                              C.c_void_p(dW.data_ptr()), _ld(dW), C.c_void_p(dbias.data_ptr()) if dbias is not None else None,
@@ -1296,7 +1081,6 @@ def pad_cols(src: torch.Tensor, Kp: int) -> torch.Tensor:
 # small-batch towers (csrc/tower.hip): all layers of an MLP in one launch per direction
 # ------------------------------------------------------------------------------------------------
 TOWER_MAX_LAYERS, TOWER_MAX_WIDTH = 8, 512          # DLRM_TOWER_MAX_LAYERS / DLRM_TOWER_MAX_WIDTH of include/dlrm_hip.h
-_tower_ws = {}     # (device, stream) -> slab workspace of tower_wgrad
 
 
 def _int_array(vals):
@@ -1374,12 +1158,7 @@ def tower_wgrad(dZs: Sequence[torch.Tensor], ins: Sequence[torch.Tensor], dWs: S
     if len(ins) != L or len(dWs) != L or len(dbs) != L or not tower_ok(M, widths):
         raise RuntimeError("dlrm_amd: tower_wgrad argument mismatch")
     wa = _int_array(widths)
-    need = int(lib.dlrm_tower_wgrad_workspace_bytes(M, L, wa))
-    dev = dZs[0].device
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)              # (the stream of the tensors' device: what _stream(dZs[0]) launches on)
-    ws = _tower_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _tower_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _scratch("tower", int(lib.dlrm_tower_wgrad_workspace_bytes(M, L, wa)), dZs[0].device)
     with _timed("linear_bwd_weight"):
         rc = lib.dlrm_tower_wgrad(M, L, wa, _int_array([w.size(1) for w in dWs]),
                                   _lib.ptr_array([z.data_ptr() for z in dZs]), _lib.i64_array([_ld(z) for z in dZs]),
@@ -1731,3 +1510,9 @@ def device_info(device: int = 0) -> dict:
     _lib.check(rc, "dlrm_hip_device_info")
     return {"name": name.value.decode(), "cu_count": cu.value, "lds_bytes": lds.value, "hbm_bytes": hbm.value,
             "build": lib.dlrm_hip_build_info().decode(), "abi": lib.dlrm_hip_abi_version()}
+
+
+# The "one lookup per bag" proof (state and logic) lives in dlrm_amd/iota.py; its public names stay attributes of this module.  Imported
+# HERE, at the end: iota uses _timed, _stream and wait_spinning of this module, so it can only be loaded once they exist.
+from .iota import (IOTA_STATS, mark_one_lookup_per_bag, offsets_are_iota, offsets_are_iota_finish,  # noqa: E402,F401
+                   offsets_are_iota_start, offsets_iota_state)

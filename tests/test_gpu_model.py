@@ -598,7 +598,7 @@ def test_producer_tags_and_the_proof_stream():
     tag, a copy carries none; a generator with variable bag lengths tags nothing.  (b) the two-phase proof (offsets_are_iota_start /
     _finish: the check kernel on its own stream, the host waits for ITS event) — work enqueued on the caller's stream between the two
     halves does not disturb it, the verdict is cached per tensor object afterwards, and a ragged tensor is refused."""
-    from dlrm_amd import ops
+    from dlrm_amd import iota, ops
     from dlrm_amd.datagen import UniformBatchGenerator
     from dlrm_amd.multihot import Multihot
     device = torch.device("cuda:0")
@@ -613,20 +613,20 @@ def test_producer_tags_and_the_proof_stream():
     assert torch.equal(so, torch.arange(B, device=device).repeat(len(rows), 1))                               # ... and the tag tells the truth
     import copy
     dc = copy.deepcopy(lS_o[0])                      # Python attributes travel with a deep copy: the tag must NOT (it names object + address)
-    assert getattr(dc, ops._IOTA_TAG, None) is not None and not ops._iota_tagged(dc) and ops._iota_tagged(lS_o[0])
+    assert getattr(dc, iota._IOTA_TAG, None) is not None and not iota._iota_tagged(dc) and iota._iota_tagged(lS_o[0])
     c = so.clone()                                   # a copy is a new object: it takes the device proof
     assert ops.offsets_are_iota(c) is True and ops.IOTA_STATS["checked"] == s0["checked"] + 1
     so[2, 7] = 9                                     # a versioned write voids the tag; the device pass then sees the ragged bags
     assert ops.offsets_are_iota(so) is False and ops.IOTA_STATS["checked"] == s0["checked"] + 2
     ragged_gen = UniformBatchGenerator(13, rows, 3, False, seed=3, device=device)
     _, ro, _, _ = ragged_gen.batch(B, 0)
-    assert not any(getattr(o, ops._IOTA_TAG, None) is not None for o in ro)
+    assert not any(getattr(o, iota._IOTA_TAG, None) is not None for o in ro)
     mh = Multihot([1, 1, 1], [50, 300, 7], B, device=device)
     _, _, off_l = mh.expand(torch.randint(0, 7, (3, B), device=device, dtype=torch.int32), want_global_offsets=False)
     assert ops.offsets_are_iota(off_l) is True and ops.IOTA_STATS["checked"] == s0["checked"] + 2            # tagged: no pass
     mh2 = Multihot([2, 1, 1], [50, 300, 7], B, device=device)
     _, _, off2 = mh2.expand(torch.randint(0, 7, (3, B), device=device, dtype=torch.int32), want_global_offsets=False)
-    assert getattr(off2, ops._IOTA_TAG, None) is None
+    assert getattr(off2, iota._IOTA_TAG, None) is None
     # (b) two-phase proof with caller-stream work in between
     fresh = torch.arange(B, device=device).repeat(len(rows), 1)
     h = ops.offsets_are_iota_start(fresh)

@@ -689,3 +689,144 @@ def test_bench_dump_outputs_files_dtypes_sample_and_limit(tmp_path, monkeypatch)
     with pytest.raises(RuntimeError, match="exceed"):
         bench.dump_outputs(str(tmp_path / "c"), loss, Z, net, idx)
     assert not (tmp_path / "c").exists() or not os.listdir(tmp_path / "c")
+
+
+class _StubEvent:
+    def __init__(self):
+        self.complete = False
+
+    def query(self):
+        return self.complete
+
+
+class _StubPool:
+    """what iota._drain reads of a flag pool: the host-visible verdict words"""
+
+    def __init__(self):
+        self.host = torch.zeros(4, dtype=torch.int32)
+        self.dev = torch.zeros(4, dtype=torch.int32)
+
+
+def test_producer_tag_names_object_version_and_address(monkeypatch):
+    """The producer tag of the one-lookup-per-bag proof on CPU tensors (the logic needs no device): a tagged tensor is known to both
+    proofs without a launch; a versioned in-place write voids the tag; copy.deepcopy carries the attribute but the copy is NOT tagged."""
+    import copy
+    from dlrm_amd import iota, ops
+    monkeypatch.setattr(iota, "_iota_cache", {})
+    t = ops.mark_one_lookup_per_bag(torch.arange(8))
+    s0 = dict(ops.IOTA_STATS)
+    assert iota._iota_tagged(t)
+    assert ops.offsets_iota_state(t) is True and ops.offsets_are_iota_start([t, t]) is True and ops.offsets_are_iota(t) is True
+    assert ops.IOTA_STATS["tagged"] == s0["tagged"] + 3
+    assert {k: ops.IOTA_STATS[k] for k in s0 if k != "tagged"} == {k: s0[k] for k in s0 if k != "tagged"}
+    dc = copy.deepcopy(t)
+    assert getattr(dc, iota._IOTA_TAG, None) is not None and not iota._iota_tagged(dc) and iota._iota_tagged(t)
+    assert not iota._iota_tagged(t.clone()) and getattr(t[:4], iota._IOTA_TAG, None) is None
+    t[3] = 0
+    assert not iota._iota_tagged(t)
+
+
+def test_verdict_cache_is_per_object_and_version_and_evicts_dead_entries_first(monkeypatch):
+    import weakref
+    from dlrm_amd import iota, ops
+    cache = {}
+    monkeypatch.setattr(iota, "_iota_cache", cache)
+    a, b = torch.arange(8), torch.arange(8)
+    iota._iota_remember(a, True)
+    iota._iota_remember(b, False)
+    s0 = dict(ops.IOTA_STATS)
+    assert iota._iota_cached(a) is True and iota._iota_cached(b) is False
+    assert ops.offsets_iota_state(a) is True and ops.offsets_are_iota_start(b) is False and ops.offsets_iota_state([a, b]) is False
+    assert ops.IOTA_STATS["cached"] == s0["cached"] + 3 and ops.IOTA_STATS["tagged"] == s0["tagged"]
+    assert ops.offsets_iota_state([a, ops.mark_one_lookup_per_bag(torch.arange(8))]) is True        # tagged + cached: known, booked as cached
+    assert ops.IOTA_STATS["cached"] == s0["cached"] + 4
+    a[0] = 5                                                  # a versioned in-place write: the verdict is void
+    assert iota._iota_cached(a) is None and iota._iota_cached(b) is False
+    # a different object at a recycled id: the entry's weak reference names the OLD object
+    c = torch.arange(8)
+    cache[id(c)] = (weakref.ref(b), c._version, True)
+    assert iota._iota_cached(c) is None
+    cache[id(c)] = (lambda: None, c._version, True)           # ... or nothing any more
+    assert iota._iota_cached(c) is None
+    # eviction at > 256 entries: dead references go first, the live verdicts stay
+    cache.clear()
+    live = [torch.arange(2) for _ in range(200)]
+    for t in live:
+        iota._iota_remember(t, True)
+    for _ in range(57):
+        iota._iota_remember(torch.arange(2), False)           # (each dies at once; ids may repeat, so plant the entries by hand too)
+    for k in range(57):
+        cache[-1 - k] = (lambda: None, 0, False)
+    assert len(cache) > 256
+    iota._iota_remember(a, False)
+    assert len(cache) == 201 and all(iota._iota_cached(t) is True for t in live) and iota._iota_cached(a) is False
+    more = [torch.arange(2) for _ in range(56)]
+    for t in more:
+        iota._iota_remember(t, True)
+    assert len(cache) == 257
+    iota._iota_remember(b, True)                              # nothing dead to drop: the cache starts over
+    assert len(cache) == 1 and iota._iota_cached(b) is True and iota._iota_cached(live[0]) is None
+
+
+def test_pending_device_proofs_keep_their_pool_until_their_event_completes(monkeypatch):
+    """dlrm_amd/iota.py, rules 1 and 2: an entry whose event is incomplete survives every drain and any number of newer entries, and
+    holds its flag pool; only its weak references are forgotten beyond the bound.  A complete entry is resolved and dropped."""
+    import gc
+    import weakref
+    from dlrm_amd import iota
+    monkeypatch.setattr(iota, "_iota_cache", {})
+    pending = []
+    pool = _StubPool()
+    pool_alive = weakref.ref(pool)
+    t_old = torch.arange(8)
+    old = iota._Pending(_StubEvent(), pool, 0, [weakref.ref(t_old)])
+    pending.append(old)
+    del pool
+    for _ in range(5):
+        iota._drain(pending)
+    assert pending == [old] and old.refs and iota._iota_cached(t_old) is None
+    newer_pool = _StubPool()
+    newer_pool.host[2] = 3                                     # slot 2: three bags did not start at their own number
+    tensors = [torch.arange(8) for _ in range(iota.PENDING_REMEMBERED + 6)]
+    for k, t in enumerate(tensors):
+        pending.append(iota._Pending(_StubEvent(), newer_pool, 1 + k % 2, [weakref.ref(t)]))
+        iota._drain(pending)
+    gc.collect()
+    assert len(pending) == len(tensors) + 1 and pending[0] is old and pool_alive() is not None and pending[0].pool is pool_alive()
+    assert not old.refs and not pending[6].refs and pending[7].refs and len(pending[-1].refs) == 1      # the bound forgets references, not entries
+    # the old proof completes: nothing to remember any more (its references were forgotten), the entry and with it the pool go
+    old.event.complete = True
+    iota._drain(pending)
+    del old
+    gc.collect()
+    assert len(pending) == len(tensors) and pool_alive() is None and iota._iota_cached(t_old) is None
+    # the newest two complete: verdicts remembered for the tensors still alive; one whose tensor has died resolves without error
+    pending[-1].event.complete = pending[-2].event.complete = pending[-3].event.complete = True
+    slots = [pending[-3].slot, pending[-2].slot, pending[-1].slot]
+    t_a, t_b = tensors[-2], tensors[-1]
+    del tensors[-3:], t
+    gc.collect()
+    assert pending[-3].refs[0]() is None
+    iota._drain(pending)
+    assert len(pending) == iota.PENDING_REMEMBERED + 3
+    assert iota._iota_cached(t_a) is (slots[1] != 2) and iota._iota_cached(t_b) is (slots[2] != 2) and slots[1] != slots[2]
+    assert all(not p.event.query() for p in pending)
+
+
+def test_scratch_cache_is_grow_only_per_kind_and_stream(monkeypatch):
+    from dlrm_amd import ops
+    monkeypatch.setattr(ops, "_scratch_ws", {})
+    cpu = torch.device("cpu")
+    e = ops._scratch("emb", 10, cpu, stream=1)
+    assert e.dtype == torch.uint8 and e.numel() == 256                        # the sort workspace is at least 256 bytes
+    assert ops._scratch("emb", 200, cpu, stream=1) is e and ops._scratch("emb", 0, cpu, stream=1) is e
+    big = ops._scratch("emb", 1000, cpu, stream=1)
+    assert big is not e and big.numel() == 1000 and ops._scratch("emb", 10, cpu, stream=1) is big       # grow-only: never shrinks
+    assert ops._scratch("emb", 10, cpu, stream=2) is not big and ops._scratch("emb", 10, cpu, stream=2).numel() == 256
+    assert ops._scratch("wgrad", 0, cpu, stream=1) is None and ops._scratch("wgrad", -1, cpu, stream=1) is None
+    w = ops._scratch("wgrad", 10, cpu, stream=1)
+    t = ops._scratch("tower", 10, cpu, stream=1)
+    assert w.numel() == 10 and t.numel() == 10 and w is not t and ops._scratch("wgrad", 5, cpu, stream=1) is w
+    assert ops._scratch("tower", 0, cpu, stream=3).numel() == 0
+    assert set(ops._scratch_ws) == {("emb", cpu, 1), ("emb", cpu, 2), ("wgrad", cpu, 1), ("tower", cpu, 1), ("tower", cpu, 3)}
+    assert [w_ for (_, d_, _), w_ in ops._scratch_ws.items() if d_ == cpu and w_ is big] == [big]     # what GraphedTrainStep pins

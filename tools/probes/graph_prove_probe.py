@@ -12,7 +12,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pytest  # noqa: E402
 
-from dlrm_amd import ops  # noqa: E402
+from dlrm_amd import iota, ops  # noqa: E402
 
 real = ops.offsets_are_iota
 
@@ -34,7 +34,7 @@ def v2(o):
 
 for name, fn in (("V0 none", v0), ("V1 sync only", v1), ("V2 kernel only", v2), ("V3 real", real)):
     ops.offsets_are_iota = fn
-    ops._iota_cache.clear()
+    iota._iota_cache.clear()
     rc = pytest.main(["-q", "-x", "-m", "gpu", os.path.join(ROOT, "tests/test_gpu_model.py"), "-k", "graphed_step_equals_eager_step and deterministic",
                       "-p", "no:cacheprovider"])
     print("RESULT", name, "rc =", int(rc), flush=True)
