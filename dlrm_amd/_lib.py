@@ -40,6 +40,8 @@ SIGNATURES = {
     "dlrm_stream_create_cu_range": (_i32, [_i32, _i32, C.POINTER(C.c_void_p)]),
     "dlrm_stream_destroy": (_i32, [_vp]),
     "dlrm_emb_fwd": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_quantize_rows": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp]),
+    "dlrm_emb_fwd_quant": (_i32, [_i32, _i64, _i32, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
     "dlrm_emb_bwd_workspace_bytes": (_i64, [_i32, _pi64, _pi64]),
     "dlrm_emb_sort_kind": (_i32, [_i32, _pi64, _pi64]),
     "dlrm_cast_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),

@@ -133,6 +133,9 @@ class EmbeddingUpdateHook:
     @staticmethod
     def _pre_step(optimizer, args, kwargs):
         for model in list(EmbeddingUpdateHook._models):
+            if getattr(model, "quantize_emb", False):
+                model._refuse_step_if_quantized(optimizer)
+                continue
             if (model.overlap_streams or model.update_in_backward) and model._bound_optimizer is None and model._owned_by(optimizer):
                 model._bound_optimizer = weakref.ref(optimizer)      # (what lets the NEXT backward pass launch / take the sparse update itself)
             if model._pending_emb:
@@ -357,10 +360,22 @@ class DLRM_Net(nn.Module):
     def apply_emb(self, lS_o, lS_i, emb_l, v_W_l):
         """Reference-shaped result: a list with one [B, D] tensor per table (dlrm_s_pytorch.py:407-462)."""
         if self.quantize_emb:
-            sys.exit("ERROR: quantized embeddings are a CPU-only inference option of the reference")
+            # (dlrm_s_pytorch.py:430-450, without its "quantized emb sizes" debug line; the tables are constants: no autograd node)
+            B = len(lS_o[0])
+            packed = self._emb_quant_into(lS_o, lS_i, v_W_l, torch.empty((B, len(self.emb_l_q) * self.emb_q_dim), dtype=torch.float32,
+                                                                         device=self.emb_l_q[0].device))
+            return list(packed.split(self.emb_q_dim, dim=1))
         packed = self._emb_packed(lS_o, lS_i, emb_l, v_W_l)
         D = emb_l[0].weight.size(1)
         return list(packed.split(D, dim=1))
+
+    def _emb_quant_into(self, lS_o, lS_i, v_W_l, out):
+        """pooled rows of the packed tables (dlrm_emb_fwd_quant), all tables in one launch, written into `out` ([B, >= T*D], row stride free)"""
+        bags = self._bags(lS_o, lS_i, v_W_l)
+        vws = self._pool_weights(v_W_l, out.device)
+        if vws:
+            ops.pool_weights_gather([w.detach() for w in vws], bags)       # psw = v_W[idx], on the device (dlrm_s_pytorch.py:425-426)
+        return ops.emb_fwd_quant(self.emb_l_q, self.emb_q_rows, self.emb_q_dim, self.quantize_bits, bags, out)
 
     def weighted_bce(self, Z, T):
         """The whole wbce loss of the reference's loss_fn_wrap (mean of loss_ws[T.long()] * BCE(Z, T), dlrm_s_pytorch.py:
@@ -377,7 +392,46 @@ class DLRM_Net(nn.Module):
         sys.exit("ERROR: --arch-interaction-op=" + str(self.arch_interaction_op) + " is not supported")
 
     def quantize_embedding(self, bits):
-        sys.exit("ERROR: quantized embeddings are a CPU-only inference option of the reference")
+        """dlrm_s_pytorch.py:465-481 on the device: emb_l_q[k] = table k in torch's fused row-wise format (uint8 [rows, D + 8] at 8 bits,
+        [rows, D/2 + 4] at 4 bits: byte for byte `ops.quantized.embedding_bag_{byte,4bit}_prepack` of the same weights), emb_l = None.
+        Any other `bits` returns without change, as in the reference.  Tables are packed and released one by one (peak: the fp32 tables
+        plus one packed table).  From here on the model is an inference model: its lookups go through dlrm_emb_fwd_quant."""
+        if bits not in (4, 8):
+            return
+        if self.quantize_emb:
+            sys.exit("ERROR: the embedding tables are quantized already (%d bits)" % self.quantize_bits)
+        if ext_dist.is_distributed():
+            sys.exit("ERROR: quantized embedding tables are single-process inference only (distributed quantized inference is not built)")
+        if self.update_in_backward:
+            sys.exit("ERROR: update_in_backward trains the embedding tables; quantized tables are constants (inference only)")
+        if self._pending_emb:
+            sys.exit("ERROR: an embedding update is still parked (backward without optimizer.step()); step or drop it before quantize_embedding")
+        weights = self._emb_weights(self.emb_l)
+        if not weights or any(not w.is_cuda for w in weights):
+            raise RuntimeError("dlrm_amd: quantize_embedding packs the tables on the GPU and the quantized lookup has no CPU path; "
+                               "move the model to the device first (model.to('cuda'))")
+        self._join_side_stream()
+        n = len(self.emb_l)
+        self.emb_q_rows = [int(w.size(0)) for w in weights]
+        self.emb_q_dim = int(weights[0].size(1))
+        ops.quant_row_bytes(self.emb_q_dim, bits)                       # (4 bits need an even dimension: refused before anything changes)
+        self._emb_fp32_refs = [weakref.ref(w) for w in weights]         # an optimizer that still holds one of them must not step: _refuse_step
+        del weights
+        self.emb_l_q = [None] * n
+        for k in range(n):
+            self.emb_l_q[k] = ops.emb_quantize(self.emb_l[k].weight.detach(), bits)
+            self.emb_l[k].weight = None                                  # release the fp32 rows of this table before the next one is packed
+        self.emb_l = None
+        self.quantize_emb = True
+        self.quantize_bits = bits
+
+    def _refuse_step_if_quantized(self, optimizer) -> None:
+        if not self.quantize_emb:
+            return
+        old = {id(w) for w in (r() for r in getattr(self, "_emb_fp32_refs", [])) if w is not None}
+        if old and any(id(p) in old for g in optimizer.param_groups for p in g["params"]):
+            sys.exit("ERROR: this optimizer holds the fp32 embedding tables of a model whose tables are quantized now; quantized tables "
+                     "are constants (inference only) — build the optimizer over model.parameters() after quantize_embedding")
 
     # ---------------------------------------------------------------- fused sparse update
     def _owned_by(self, optimizer) -> bool:
@@ -519,13 +573,29 @@ class DLRM_Net(nn.Module):
             sys.exit("ERROR: --arch-interaction-op=" + str(self.arch_interaction_op) + " is not supported")
         ops.check_index_errors()          # host memory read, no synchronisation: bad indices of earlier steps surface here
         B = dense_x.size(0)
-        T = len(self.emb_l)
-        D = self.emb_l[0].weight.size(1)
+        if self.quantize_emb:
+            T, D = len(self.emb_l_q), self.emb_q_dim
+        else:
+            T = len(self.emb_l)
+            D = self.emb_l[0].weight.size(1)
         n_out = self.bot_l[-2].out_features if isinstance(self.bot_l[-2], nn.Linear) else D
         if self.arch_interaction_op == "dot" and n_out != D:
             sys.exit("ERROR: bottom MLP output (%d) and embedding dimension (%d) differ" % (n_out, D))
         # the last ReLU of the bottom tower is differentiated inside the interaction backward (which has x staged): see _relu_x
         rx = self._relu_x() if dense_x.is_cuda else 0
+        if self.quantize_emb:
+            # the two-kernel form only: the fused lookup + interaction kernels fetch fp32 rows.  The bottom tower writes its
+            # slot of the feature buffer, dlrm_emb_fwd_quant the rest; interaction and top tower as below.
+            if self.update_in_backward:
+                sys.exit("ERROR: update_in_backward trains the embedding tables; quantized tables are constants (inference only)")
+            feat = torch.empty((B, n_out + T * D), dtype=torch.float32, device=dense_x.device)
+            x = self.apply_mlp(dense_x, self.bot_l, out_slot=OutSlot(feat[:, :n_out]), consumer_applies_last_act=bool(rx))
+            E = self._emb_quant_into(lS_o, lS_i, self.v_W_l, feat[:, n_out:])
+            if self.arch_interaction_op == "cat":
+                z = CatFunction.apply(OutSlot(feat), x, E)
+            else:
+                z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)
+            return self._clamp(self.apply_mlp(z, self.top_l))
         if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and ops.gather_ok(1 + T, D)
                 and not any(w is not None for w in (self.v_W_l or []))):
             bags = self._bags(lS_o, lS_i, None)
@@ -581,6 +651,8 @@ class DLRM_Net(nn.Module):
         """Table-wise sharded embeddings + batch-split MLPs (dlrm_s_pytorch.py:528-585): every rank pools
         the WHOLE batch for its tables, one all-to-all turns table-split into batch-split, the bottom
         MLP runs while the exchange is in flight."""
+        if self.quantize_emb:
+            sys.exit("ERROR: quantized embedding tables are single-process inference only (distributed quantized inference is not built)")
         batch_size = dense_x.size(0)
         if batch_size < ext_dist.my_size:
             sys.exit("ERROR: batch_size (%d) must be larger than number of ranks (%d)" % (batch_size, ext_dist.my_size))

@@ -35,6 +35,7 @@ from __future__ import annotations
 from typing import List, Optional, Sequence, Union
 
 import os as _os
+import sys
 
 import torch
 
@@ -100,6 +101,8 @@ class GraphedTrainStep:
         if ext_dist.is_distributed():       # (a forced one-rank group routes through distributed_forward as well: its RCCL calls must not be captured)
             raise RuntimeError("dlrm_amd.graph: the whole-step HIP graph is single-process only "
                                "(RCCL all-to-all / DDP all-reduce are not captured)")
+        if getattr(model, "quantize_emb", False):
+            sys.exit("ERROR: GraphedTrainStep captures a training step; a model with quantized embedding tables is inference only")
         self.model, self.optimizer = model, optimizer
         for g in optimizer.param_groups:
             # a decaying step size (RWSAdagrad: clr = lr / (1 + (step - 1) * lr_decay)) is computed on the host at capture time

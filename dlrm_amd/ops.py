@@ -348,6 +348,58 @@ def emb_fwd(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor, 
     return out
 
 
+def quant_row_bytes(D: int, bits: int) -> int:
+    """bytes of one packed row in torch's fused row-wise format: D codes + fp32 scale, bias (8 bits); D/2 + fp16 scale, bias (4 bits)"""
+    if bits == 8:
+        return int(D) + 8
+    if bits == 4:
+        if D % 2:
+            raise RuntimeError("dlrm_amd: the 4-bit row format needs an even embedding dimension, got %d" % D)
+        return int(D) // 2 + 4
+    raise RuntimeError("dlrm_amd: quantised embedding rows have 4 or 8 bits, got %r" % (bits,))
+
+
+def emb_quantize(weight: torch.Tensor, bits: int) -> torch.Tensor:
+    """uint8 [rows, quant_row_bytes(D, bits)]: `weight` ([rows, D] fp32) in torch's fused row-wise format, byte for byte what
+    `torch.ops.quantized.embedding_bag_{byte,4bit}_prepack` gives on the CPU (dlrm_s_pytorch.py:465-481), packed on the device."""
+    _req(weight, "embedding weight", ndim=2)
+    if not weight.is_contiguous():
+        raise RuntimeError("dlrm_amd: embedding tables must be contiguous [rows, D]")
+    rows, D = weight.shape
+    out = torch.empty((rows, quant_row_bytes(D, bits)), dtype=torch.uint8, device=weight.device)
+    if rows == 0:
+        return out
+    lib = _lib.load()
+    with _timed("emb_quantize"):
+        rc = lib.dlrm_emb_quantize_rows(rows, D, bits, C.c_void_p(weight.data_ptr()), C.c_void_p(out.data_ptr()), _stream(weight))
+    _lib.check(rc, "dlrm_emb_quantize_rows")
+    return out
+
+
+def emb_fwd_quant(qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, bags: BagBatch, out: torch.Tensor) -> torch.Tensor:
+    """emb_fwd over packed tables (emb_quantize): out[b, t*D:(t+1)*D] = sum_i psw_i * (scale_r * q_r + bias_r).  qweights[t] is the
+    uint8 [rows[t], quant_row_bytes(D, bits)] tensor of table t; `out` is a [B, >= T*D] view (row stride free)."""
+    lib = _lib.load()
+    rb = quant_row_bytes(D, bits)
+    if len(qweights) != bags.T or len(rows) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_fwd_quant needs one packed table and one row count per table")
+    for q, n in zip(qweights, rows):
+        _req(q, "packed embedding table", dtype=torch.uint8, ndim=2)
+        if not q.is_contiguous() or q.size(0) != int(n) or q.size(1) != rb:
+            raise RuntimeError("dlrm_amd: a packed %d-bit table of %d rows and dimension %d is a contiguous uint8 [%d, %d] tensor, got %s"
+                               % (bits, n, D, n, rb, tuple(q.shape)))
+    _req(out, "out", ndim=2)
+    if out.size(0) != bags.B or out.size(1) < bags.T * D:
+        raise RuntimeError("dlrm_amd: emb_fwd_quant shape mismatch")
+    err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
+    with _timed("emb_fwd_quant"):
+        rc = lib.dlrm_emb_fwd_quant(bags.T, bags.B, D, bits, _lib.ptr_array([q.data_ptr() for q in qweights]), _lib.i64_array(rows),
+                                    bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out),
+                                    err, _stream(out))
+    _lib.check(rc, "dlrm_emb_fwd_quant")
+    return out
+
+
 _scratch_ws = {}   # (kind, device, stream) -> cached uint8 scratch: "emb" the workspace of the sort-based updates, "wgrad" the split-K slabs
                    # of the weight gradients, "tower" the slabs of tower_wgrad.  Per stream: kernels of one stream are ordered, so one buffer per
                    # kind suffices — and a buffer allocated under one stream is never handed to kernels of another (the caching allocator

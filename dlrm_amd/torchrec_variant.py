@@ -15,6 +15,7 @@ Inputs are the multi-hot batches of `dlrm_amd.multihot.Multihot` (int32 ids, per
 """
 from __future__ import annotations
 
+import sys
 from typing import Sequence
 
 import numpy as np
@@ -30,9 +31,15 @@ class FusedBCEWithLogitsLoss(nn.Module):
         return BCEWithLogitsLossFunction.apply(logits, target)
 
 
+def _no_quantized_tables(self, bits):
+    sys.exit("ERROR: quantized embedding tables are built for DLRM_Net only, not for the torchrec variants (%s)" % type(self).__name__)
+
+
 class DLRM(DLRM_Net):
     """torchrec.models.dlrm.DLRM(embedding_bag_collection, dense_in_features, dense_arch_layer_sizes, over_arch_layer_sizes):
     the embedding bag collection is given by its table sizes and the embedding dimension."""
+
+    quantize_embedding = _no_quantized_tables
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
                  dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int]):
@@ -83,6 +90,8 @@ class ShardedDLRM(DLRM_Net):
         order through the kernel's {pointer, stride} table (`InteractFunction(order=...)`).
     Embedding gradients are not divided by N (the reference's behaviour in both trainers: the loss is the mean over the LOCAL
     batch; DDP averages only the dense parameters)."""
+
+    quantize_embedding = _no_quantized_tables
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], multi_hot_sizes: Sequence[int], embedding_dim: int,
                  dense_in_features: int, dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int],
@@ -221,6 +230,8 @@ class DLRM_DCN(DLRM_Net):
     """torchrec.models.dlrm.DLRM_DCN (the MLPerf-v2 model, torchrec_dlrm/dlrm_main.py:608-619): dense arch and pooled embeddings
     are concatenated to [B, F*D] — the feature buffer the bottom tower and the embedding kernel write side by side — and passed
     through a DCN-v2 low-rank cross network; the over-arch takes its [B, F*D] output and ends with a bare Linear (logits)."""
+
+    quantize_embedding = _no_quantized_tables
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
                  dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int], dcn_num_layers: int,

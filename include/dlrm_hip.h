@@ -92,6 +92,32 @@ int dlrm_emb_fwd(int T, int64_t B, int D,
                  const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
                  float* out, int64_t out_ld, int64_t* err, void* stream);
 
+/* Row-wise quantised embedding tables for inference (8 and 4 bits), on the device.
+ * Replaces: DLRM_Net.quantize_embedding / the quantised branch of apply_emb, which the reference runs on the CPU only
+ *           (`ops.quantized.embedding_bag_{byte,4bit}_prepack`, `..._rowwise_offsets`; dlrm_s_pytorch.py:430-450, 465-481).
+ * Packed row = torch's fused format, byte for byte:
+ *   bits = 8: D code bytes, fp32 scale, fp32 bias (D + 8 bytes);
+ *   bits = 4: D/2 code bytes (column 2k in the low nibble of byte k), fp16 scale, fp16 bias (D/2 + 4 bytes; D even, else DLRM_E_ARG).
+ * dlrm_emb_quantize_rows: packed[r] = prepack(weight[r, :]) for r < rows, with torch's arithmetic (min / max per row; 8 bits: scale = range / 255,
+ *   bias = min, q = clamp(rint((x - min) * (255 / (range + 1e-8))), 0, 255); 4 bits: min rounded to fp16, scale = fp16(range / 15) with 0 -> 1,
+ *   q = clamp(rint((x - min) * (1 / scale)), 0, 15); round to nearest even).  64-bit offsets throughout.
+ *   weight : device float* [rows, D];  packed : device uint8* [rows, row bytes]
+ * dlrm_emb_fwd_quant: dlrm_emb_fwd over packed tables — same operands and conventions (all tables in one launch, idx_bits, off_t[B] := nnz[t],
+ *   psw_host, out / out_ld, empty bags give zeros, out-of-range indices skipped and reported through `err`), weight_host[t] = packed rows:
+ *     out[b*out_ld + t*D + d] = sum_{i in bag(t,b)} psw_t[i] * (scale_r * q_r[d] + bias_r),   r = idx_t[i]
+ *   evaluated as acc = fmaf(psw_t[i], fmaf(scale_r, (float)q_r[d], bias_r), acc) from +0.0 in index order per column (psw = 1.0f when absent):
+ *   deterministic, independent of the launch shape; not torch's operation order (which differs between its two CPU paths) — within
+ *   (L + 2) * 2^-23 * sum_i |psw_i| (|scale_r| q + |bias_r|) of the exact value for a bag of L rows.
+ *   D % 8 == 0 (D <= 512) with 8-byte (8 bits) / 4-byte (4 bits) aligned tables and a 16-byte aligned out takes the 8-columns-per-lane
+ *   kernel, everything else a byte-wise one.
+ */
+int dlrm_emb_quantize_rows(int64_t rows, int D, int bits, const float* weight, void* packed, void* stream);
+int dlrm_emb_fwd_quant(int T, int64_t B, int D, int bits,
+                       const void* const* weight_host, const int64_t* rows_host,
+                       const void* const* indices_host, const void* const* offsets_host,
+                       const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                       float* out, int64_t out_ld, int64_t* err, void* stream);
+
 /* K2+K3  fused EmbeddingBag backward + sparse SGD step, all tables, no gradient materialised.
  * Replaces: autograd `EmbeddingBagBackward` (sparse COO grad) followed by
  *           `torch.optim.SGD.step` on that grad (dlrm_s_pytorch.py:1613,1620; optimizer :1343-1369).
