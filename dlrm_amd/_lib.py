@@ -20,6 +20,7 @@ CSRC = os.path.join(_HERE, "csrc")
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 UPD_ATOMIC, UPD_DETERMINISTIC, UPD_SORTED = 0, 1, 2
 ARITH_F32, ARITH_BF16X6, ARITH_BF16 = 0, 1, 2
+QR_MULT, QR_ADD = 0, 1
 EXPECTED_ABI = 17          # dlrm_hip_abi_version() of the library these bindings (SIGNATURES) were written against
 
 _lock = threading.Lock()
@@ -42,6 +43,9 @@ SIGNATURES = {
     "dlrm_emb_fwd": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
     "dlrm_emb_quantize_rows": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp]),
     "dlrm_emb_fwd_quant": (_i32, [_i32, _i64, _i32, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_fwd_qr": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _pi64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_qr_bwd_split": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "dlrm_emb_qr_split_indices": (_i32, [_i32, _pi64, C.POINTER(_i32), _pp, _pi64, _i32, _pp, _pp, _vp]),
     "dlrm_emb_bwd_workspace_bytes": (_i64, [_i32, _pi64, _pi64]),
     "dlrm_emb_sort_kind": (_i32, [_i32, _pi64, _pi64]),
     "dlrm_cast_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),

@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
                          EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
-                         OutSlot)
+                         OutSlot, QREmbeddingBagsFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
 
@@ -109,6 +109,41 @@ class FusedMSELoss(nn.Module):
         return MSELossFunction.apply(p, target)
 
 
+class QREmbeddingBagHolder(nn.Module):
+    """Parameter holder of one quotient-remainder table (the reference's tricks/qr_embedding_bag.py QREmbeddingBag, mode="sum", sparse):
+    `weight_q` [ceil(n / c), D] and `weight_r` [c, D], so that state_dict has the reference's keys `emb_l.{k}.weight_q|weight_r`, plus the
+    reference's constants.  Both are drawn U(sqrt(1 / n), 1) from TORCH's generator, q then r: the reference calls
+    `nn.init.uniform_(w, np.sqrt(1 / n))`, whose second positional argument is the LOWER bound (the upper one stays 1.0) — restated
+    exactly, because equal seeds must give equal initial parameters.  Lookups of a model go through dlrm_emb_fwd_qr for all tables at once
+    (QREmbeddingBagsFunction) and are trained through the model's gradient sink; `forward` here is the same kernel for this table alone and is
+    FORWARD-ONLY: its result carries no autograd node (a holder on its own has no sink for the sparse gradients)."""
+
+    def __init__(self, num_categories: int, embedding_dim: int, num_collisions: int, operation: str = "mult", device=None):
+        super().__init__()
+        self.num_categories, self.num_collisions, self.operation = int(num_categories), int(num_collisions), operation
+        self.embedding_dim = [int(embedding_dim), int(embedding_dim)]
+        self.num_embeddings = [ops.qr_rows_q(num_categories, num_collisions), int(num_collisions)]
+        self.mode, self.sparse = "sum", True
+        low = float(np.sqrt(1 / num_categories))
+        self.weight_q = nn.Parameter(torch.empty((self.num_embeddings[0], embedding_dim), dtype=torch.float32, device=device))
+        self.weight_r = nn.Parameter(torch.empty((self.num_embeddings[1], embedding_dim), dtype=torch.float32, device=device))
+        with torch.no_grad():
+            self.weight_q.uniform_(low, 1.0)
+            self.weight_r.uniform_(low, 1.0)
+
+    def forward(self, input, offsets=None, per_sample_weights=None):
+        if per_sample_weights is not None:
+            sys.exit("ERROR: quotient remainder with weighted pooling is not supported")
+        if offsets is None:
+            raise RuntimeError("dlrm_amd: QREmbeddingBagHolder takes 1-D indices with bag offsets")
+        spec = ([self.num_categories], [self.num_collisions], self.operation, False)      # (no pooled sums kept: nothing flows back)
+        with torch.no_grad():
+            return QREmbeddingBagsFunction.apply(None, ops.BagBatch([offsets], [input]), None, spec, self.weight_q, self.weight_r)
+
+    def extra_repr(self):
+        return "%d, %d, collisions=%d, operation=%s" % (self.num_categories, self.embedding_dim[0], self.num_collisions, self.operation)
+
+
 class EmbeddingUpdateHook:
     """Applies the fused sparse embedding update when an optimizer steps.
 
@@ -158,6 +193,10 @@ class _NullCtx:
 
 
 class DLRM_Net(nn.Module):
+    # the torchrec variants set it False: their constructors take no qr_* argument, so the refusal in create_emb guards a subclass or a caller
+    # that sets the qr_* attributes itself (ShardedDLRM calls create_emb directly)
+    _qr_supported = True
+
     # ---------------------------------------------------------------- parameter construction
     def create_mlp(self, ln, sigmoid_layer):
         """Tower with ln[i] -> ln[i+1] Linear layers; Sigmoid after layer `sigmoid_layer`, ReLU after
@@ -186,10 +225,29 @@ class DLRM_Net(nn.Module):
                 continue
             n = int(ln[i])
             if getattr(self, "qr_flag", False) and n > self.qr_threshold:
-                sys.exit("ERROR: QR embeddings are not supported by the MI355X DLRM_Net")
+                # the reference's QREmbeddingBag (dlrm_s_pytorch.py:258-266): drawn from torch's generator, not numpy's (see the holder)
+                if not self._qr_supported:
+                    sys.exit("ERROR: QR embeddings are built for DLRM_Net only, not for the torchrec variants (%s)" % type(self).__name__)
+                if weighted_pooling is not None:
+                    sys.exit("ERROR: quotient remainder with weighted pooling is not supported")
+                if self.qr_operation == "concat":
+                    sys.exit("ERROR: --qr-operation=concat makes a QR table 2*D wide beside D-wide plain tables; the MI355X DLRM_Net keeps "
+                             "every feature in one uniform [B, (1+T)*D] buffer, so only mult and add are supported")
+                if self.qr_operation not in ops.QR_OPS:
+                    sys.exit("ERROR: --qr-operation=" + str(self.qr_operation) + " is not supported")
+                if int(self.qr_collisions) < 1:
+                    sys.exit("ERROR: --qr-collisions must be at least 1 with --qr-flag, got " + str(self.qr_collisions))
+                tables.append(QREmbeddingBagHolder(n, m, int(self.qr_collisions), self.qr_operation, device=_EMB_INIT_DEVICE))
+                pool_w.append(None)
+                continue
             if getattr(self, "md_flag", False) and n > self.md_threshold:
                 sys.exit("ERROR: mixed-dimension embeddings are not supported by the MI355X DLRM_Net")
             bound = np.sqrt(1 / n)
+            if getattr(self, "qr_flag", False) and _EMB_INIT_DEVICE is None:
+                # the reference constructs nn.EmbeddingBag(n, m) first, whose own N(0, 1) init consumes n*m draws of TORCH's generator before
+                # the numpy values replace it (dlrm_s_pytorch.py:277-284); the QR tables after this one are drawn from that generator, so
+                # equal seeds give equal QR tables only if the same draws are spent here
+                torch.empty((n, m), dtype=torch.float32).normal_()
             if _EMB_INIT_DEVICE is None:
                 w = torch.tensor(np.random.uniform(low=-bound, high=bound, size=(n, m)).astype(np.float32))
             else:
@@ -349,12 +407,44 @@ class DLRM_Net(nn.Module):
         return out
 
     def _emb_weights(self, emb_l) -> List[torch.Tensor]:
-        return [e.weight for e in emb_l]
+        """the tables as the kernels see them: the VIRTUAL table list, where a QR table is its weight_q followed by its weight_r"""
+        out = []
+        for e in emb_l:
+            if isinstance(e, QREmbeddingBagHolder):
+                out += [e.weight_q, e.weight_r]
+            else:
+                out.append(e.weight)
+        return out
+
+    @staticmethod
+    def _has_qr(emb_l) -> bool:
+        return emb_l is not None and any(isinstance(e, QREmbeddingBagHolder) for e in emb_l)
+
+    @staticmethod
+    def _emb_dim(emb_l) -> int:
+        e = emb_l[0]
+        return int((e.weight_q if isinstance(e, QREmbeddingBagHolder) else e.weight).size(1))
+
+    def _qr_spec(self, emb_l):
+        """(rows, collisions, operation, keep the two pooled sums for backward) of QREmbeddingBagsFunction"""
+        qr = [isinstance(e, QREmbeddingBagHolder) for e in emb_l]
+        rows = [e.num_categories if q else int(e.weight.size(0)) for e, q in zip(emb_l, qr)]
+        coll = [e.num_collisions if q else 0 for e, q in zip(emb_l, qr)]
+        ops_ = {e.operation for e, q in zip(emb_l, qr) if q}
+        if len(ops_) != 1:
+            sys.exit("ERROR: all QR tables of a model must share one --qr-operation")
+        return rows, coll, ops_.pop(), torch.is_grad_enabled()
 
     def _emb_packed(self, lS_o, lS_i, emb_l, v_W_l, out_slot: Optional[OutSlot] = None):
         """[B, T*D] pooled embeddings of all given tables, one kernel launch."""
         bags = self._bags(lS_o, lS_i, v_W_l)
         ws = self._emb_weights(emb_l)
+        if self._has_qr(emb_l):
+            # the QR lookup (dlrm_emb_fwd_qr) for ALL tables of the list, plain ones included; backward splits the gradient into the two
+            # component gradients and hands the virtual table list to the same sink
+            if v_W_l is not None and any(w is not None for w in v_W_l):
+                sys.exit("ERROR: quotient remainder with weighted pooling is not supported")
+            return QREmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, self._qr_spec(emb_l), *ws)
         return EmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, *ws, *self._pool_weights(v_W_l, ws[0].device))
 
     def apply_emb(self, lS_o, lS_i, emb_l, v_W_l):
@@ -366,7 +456,7 @@ class DLRM_Net(nn.Module):
                                                                          device=self.emb_l_q[0].device))
             return list(packed.split(self.emb_q_dim, dim=1))
         packed = self._emb_packed(lS_o, lS_i, emb_l, v_W_l)
-        D = emb_l[0].weight.size(1)
+        D = self._emb_dim(emb_l)
         return list(packed.split(D, dim=1))
 
     def _emb_quant_into(self, lS_o, lS_i, v_W_l, out):
@@ -398,6 +488,8 @@ class DLRM_Net(nn.Module):
         plus one packed table).  From here on the model is an inference model: its lookups go through dlrm_emb_fwd_quant."""
         if bits not in (4, 8):
             return
+        if self._has_qr(self.emb_l):
+            sys.exit("ERROR: 4 and 8-bit quantization with quotient remainder is not supported")
         if self.quantize_emb:
             sys.exit("ERROR: the embedding tables are quantized already (%d bits)" % self.quantize_bits)
         if ext_dist.is_distributed():
@@ -435,7 +527,7 @@ class DLRM_Net(nn.Module):
 
     # ---------------------------------------------------------------- fused sparse update
     def _owned_by(self, optimizer) -> bool:
-        mine = {id(e.weight) for e in self.emb_l}
+        mine = {id(w) for w in self._emb_weights(self.emb_l)}
         return any(id(p) in mine for g in optimizer.param_groups for p in g["params"])
 
     def _join_side_stream(self) -> None:
@@ -552,6 +644,9 @@ class DLRM_Net(nn.Module):
             elif plan[0] == "sgd":
                 ops.emb_bwd_sgd(weights, bags, dout, plan[1], self.emb_update_mode)
             else:
+                if self._has_qr(self.emb_l):
+                    sys.exit("ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
+                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
                 _, clr, eps, states = plan
                 ops.emb_bwd_rowwise_adagrad(weights, states, bags, dout, clr, eps)
 
@@ -577,7 +672,7 @@ class DLRM_Net(nn.Module):
             T, D = len(self.emb_l_q), self.emb_q_dim
         else:
             T = len(self.emb_l)
-            D = self.emb_l[0].weight.size(1)
+            D = self._emb_dim(self.emb_l)
         n_out = self.bot_l[-2].out_features if isinstance(self.bot_l[-2], nn.Linear) else D
         if self.arch_interaction_op == "dot" and n_out != D:
             sys.exit("ERROR: bottom MLP output (%d) and embedding dimension (%d) differ" % (n_out, D))
@@ -596,8 +691,10 @@ class DLRM_Net(nn.Module):
             else:
                 z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)
             return self._clamp(self.apply_mlp(z, self.top_l))
+        # (a model with a QR table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it the
+        # step-time update, update_in_backward included)
         if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and ops.gather_ok(1 + T, D)
-                and not any(w is not None for w in (self.v_W_l or []))):
+                and not self._has_qr(self.emb_l) and not any(w is not None for w in (self.v_W_l or []))):
             bags = self._bags(lS_o, lS_i, None)
             # nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the
             # reference computes it): ops.offsets_are_iota (dlrm_amd/iota.py) proves offsets == arange(B) on the device, once per offsets tensor
@@ -653,6 +750,8 @@ class DLRM_Net(nn.Module):
         MLP runs while the exchange is in flight."""
         if self.quantize_emb:
             sys.exit("ERROR: quantized embedding tables are single-process inference only (distributed quantized inference is not built)")
+        if self._has_qr(self.emb_l):
+            sys.exit("ERROR: QR embedding tables are single-process only (the table-sharded distributed forward is not built for them)")
         batch_size = dense_x.size(0)
         if batch_size < ext_dist.my_size:
             sys.exit("ERROR: batch_size (%d) must be larger than number of ranks (%d)" % (batch_size, ext_dist.my_size))

@@ -550,6 +550,44 @@ class EmbeddingBagsFunction(Function):
         return (None, None, None) + (None,) * len(ctx.weights) + dvw
 
 
+class QREmbeddingBagsFunction(Function):
+    """EmbeddingBagsFunction for a table list with quotient-remainder tables (tricks/qr_embedding_bag.py; dlrm_s_pytorch.py:258-266): one
+    dlrm_emb_fwd_qr launch pools every table, QR or plain.  spec = (rows, collisions, operation, keep_sums); `vweights` is the VIRTUAL table
+    list — weight_q then weight_r for a QR table, the weight of a plain one.  Backward runs one streaming pass (dlrm_emb_qr_bwd_split) from
+    d_out and the two pooled sums the forward kept to the gradient buffer of the virtual list, derives the q / r ids
+    (dlrm_emb_qr_split_indices) and hands (virtual weights, virtual bags, buffer) to `sink`: the sparse updates are the existing ones."""
+
+    @staticmethod
+    def forward(ctx, sink, bags, out_slot, spec, *vweights):
+        rows, collisions, op, keep_sums = spec
+        weights, weights_r = [], []
+        it = iter(vweights)
+        for c in collisions:
+            weights.append(next(it))
+            weights_r.append(next(it) if c else None)
+        D = weights[0].size(1)
+        out = out_slot.get() if out_slot is not None else alloc2d(bags.B, bags.T * D, weights[0])
+        saved = None
+        if keep_sums and op == "mult":
+            saved = torch.empty((bags.B, 2 * D * sum(1 for c in collisions if c)), dtype=torch.float32, device=out.device)
+        ops.emb_fwd_qr(weights, weights_r, rows, collisions, op, bags, out, saved)
+        ctx.sink, ctx.bags, ctx.spec, ctx.D = sink, bags, spec, D
+        ctx.vweights = vweights      # parameters (leaves) — kept by reference, not via save_for_backward
+        ctx.saved = saved
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.sink is None:
+            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+        rows, collisions, op, _ = ctx.spec
+        if op == "mult" and ctx.saved is None:
+            raise RuntimeError("dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept")
+        gout = ops.emb_qr_bwd_split(collisions, op, ctx.D, _rowmajor(dout), ctx.saved)     # (the sums stay with the node: a retained graph may run again)
+        ctx.sink(ctx.vweights, ops.qr_virtual_bags(rows, collisions, ctx.bags), gout)
+        return (None, None, None, None) + (None,) * len(ctx.vweights)
+
+
 class InteractFunction(Function):
     """R = [x | strictly-lower-triangular pairwise dots of the F feature vectors].
 

@@ -214,11 +214,13 @@ class BagBatch:
             off_ptrs = [lS_o.data_ptr() + k * lS_o.stride(0) * isz for k in range(T)]
             nnz = [n_i] * T
             self._idx_src = lS_i
+            self._off_src = lS_o
         else:
             idx_ptrs, off_ptrs, nnz = [], [], []
             dt = None
             B = None
             self._idx_src = []
+            self._off_src = []
             for k in range(T):
                 i_k, o_k = lS_i[k], lS_o[k]
                 if i_k.dtype not in (torch.int64, torch.int32) or o_k.dtype != i_k.dtype:
@@ -239,6 +241,7 @@ class BagBatch:
                     raise RuntimeError("dlrm_amd: every table must have the same number of bags")
                 self.keep += [i_k, o_k]
                 self._idx_src.append(i_k)
+                self._off_src.append(o_k)
                 idx_ptrs.append(i_k.data_ptr() if i_k.numel() else 0)
                 off_ptrs.append(o_k.data_ptr())
                 nnz.append(i_k.numel())
@@ -398,6 +401,141 @@ def emb_fwd_quant(qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int,
                                     err, _stream(out))
     _lib.check(rc, "dlrm_emb_fwd_quant")
     return out
+
+
+# ---- quotient-remainder (QR) tables: csrc/emb_qr.hip.  A table list is described by three parallel lists: `weights` (weight_q of a QR table,
+# the table itself for a plain one), `weights_r` (weight_r or None), `rows` (the number of CATEGORIES n of a QR table — weight_q has
+# ceil(n / c) rows —, the row count of a plain one) and `collisions` (c, 0 for a plain table).
+QR_OPS = {"mult": _lib.QR_MULT, "add": _lib.QR_ADD}
+
+
+def _qr_op(op) -> int:
+    try:
+        return QR_OPS[op]
+    except KeyError:
+        raise RuntimeError("dlrm_amd: the QR composition is 'mult' or 'add', got %r" % (op,)) from None
+
+
+def _i32_array(vals):
+    return (C.c_int * len(vals))(*[int(v) for v in vals])
+
+
+def qr_rows_q(n: int, collisions: int) -> int:
+    """rows of weight_q: ceil(n / c) (qr_embedding_bag.py:155-158)"""
+    return -(-int(n) // int(collisions))
+
+
+def _qr_desc(weights, weights_r, rows, collisions):
+    T = len(weights)
+    if not (len(weights_r) == len(rows) == len(collisions) == T) or T == 0:
+        raise RuntimeError("dlrm_amd: a QR table list needs one weight, weight_r (or None), row count and collision count per table")
+    D = int(weights[0].size(1))
+    for w, wr, n, c in zip(weights, weights_r, rows, collisions):
+        _req(w, "embedding weight", ndim=2)
+        want = (qr_rows_q(n, c) if c else int(n), D)
+        if not w.is_contiguous() or tuple(w.shape) != want:
+            raise RuntimeError("dlrm_amd: a table of %d rows with %d collisions needs a contiguous weight of shape %s, got %s" % (n, c, want, tuple(w.shape)))
+        if c:
+            _req(wr, "embedding weight_r", ndim=2)
+            if not wr.is_contiguous() or tuple(wr.shape) != (int(c), D):
+                raise RuntimeError("dlrm_amd: weight_r of a table with %d collisions is a contiguous [%d, %d] tensor, got %s" % (c, c, D, tuple(wr.shape)))
+    return (D, _lib.ptr_array([w.data_ptr() for w in weights]), _lib.ptr_array([wr.data_ptr() if c else 0 for wr, c in zip(weights_r, collisions)]),
+            _lib.i64_array(rows), _i32_array(collisions))
+
+
+def emb_fwd_qr(weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]], rows: Sequence[int], collisions: Sequence[int],
+               op: str, bags: BagBatch, out: torch.Tensor, saved: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """emb_fwd over a table list with QR tables: out[b, t*D:(t+1)*D] = (sum Wq[q_i]) op (sum Wr[r_i]) for a QR table, the pooled sum for a plain
+    one.  saved: a [B, >= 2*Tq*D] buffer that receives the two sums of every QR table (what emb_qr_bwd_split reads)."""
+    lib = _lib.load()
+    D, wp, wrp, rows_a, coll_a = _qr_desc(weights, weights_r, rows, collisions)
+    _req(out, "out", ndim=2)
+    if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_fwd_qr shape mismatch")
+    if bags._psw is not None:
+        raise RuntimeError("dlrm_amd: QR tables take no per-sample (pooling) weights")
+    sv_p, sv_ld = None, 0
+    if saved is not None:
+        _req(saved, "saved", ndim=2)
+        if saved.size(0) != bags.B or saved.size(1) < 2 * D * sum(1 for c in collisions if c):
+            raise RuntimeError("dlrm_amd: emb_fwd_qr `saved` is a [B, >= 2 * (QR tables) * D] buffer")
+        sv_p, sv_ld = C.c_void_p(saved.data_ptr()), _ld(saved)
+    err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
+    with _timed("emb_fwd"):
+        rc = lib.dlrm_emb_fwd_qr(bags.T, bags.B, D, wp, wrp, rows_a, coll_a, _qr_op(op), bags._idx, bags._off, bags._nnz, bags.idx_bits,
+                                 C.c_void_p(out.data_ptr()), _ld(out), sv_p, sv_ld, err, _stream(out))
+    _lib.check(rc, "dlrm_emb_fwd_qr")
+    return out
+
+
+def emb_qr_bwd_split(collisions: Sequence[int], op: str, D: int, dout: torch.Tensor, saved: Optional[torch.Tensor],
+                     gout: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, Tv*D] gradient buffer of the virtual table list (a QR table = its q table, then its r table) from dout [B, >= T*D]:
+    dout * sr, dout * sq ("mult"; `saved` of emb_fwd_qr) | dout, dout ("add") | a copy for plain tables."""
+    lib = _lib.load()
+    T = len(collisions)
+    Tv = T + sum(1 for c in collisions if c)
+    _req(dout, "dout", ndim=2)
+    if dout.size(1) < T * D:
+        raise RuntimeError("dlrm_amd: emb_qr_bwd_split shape mismatch")
+    B = dout.size(0)
+    if gout is None:
+        gout = torch.empty((B, Tv * D), dtype=torch.float32, device=dout.device)
+    _req(gout, "gout", ndim=2)
+    if gout.size(0) != B or gout.size(1) < Tv * D:
+        raise RuntimeError("dlrm_amd: emb_qr_bwd_split needs a [B, >= Tv*D] output")
+    sv_p, sv_ld = None, 0
+    if saved is not None:
+        _req(saved, "saved", ndim=2)
+        if saved.size(0) != B or saved.size(1) < 2 * D * (Tv - T):
+            raise RuntimeError("dlrm_amd: emb_qr_bwd_split `saved` is a [B, >= 2 * (QR tables) * D] buffer")
+        sv_p, sv_ld = C.c_void_p(saved.data_ptr()), _ld(saved)
+    with _timed("emb_qr_bwd_split"):
+        rc = lib.dlrm_emb_qr_bwd_split(T, B, D, _i32_array(collisions), _qr_op(op), C.c_void_p(dout.data_ptr()), _ld(dout), sv_p, sv_ld,
+                                       C.c_void_p(gout.data_ptr()), _ld(gout), _stream(dout))
+    _lib.check(rc, "dlrm_emb_qr_bwd_split")
+    return gout
+
+
+def emb_qr_split_indices(rows: Sequence[int], collisions: Sequence[int], bags: BagBatch):
+    """(q ids, r ids) per table — None, None for a plain table — in the dtype of the ids; q = (id / c).long() with the reference's float32
+    division, r = id mod c; -1 / -1 for a lookup the forward skips."""
+    lib = _lib.load()
+    if len(rows) != bags.T or len(collisions) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_qr_split_indices needs one row count and one collision count per table")
+    ks = [k for k, c in enumerate(collisions) if c]
+    qs, rs = [None] * bags.T, [None] * bags.T
+    if not ks:
+        return qs, rs
+    src = [bag_index_tensor(bags, k) for k in ks]
+    for k, i_k in zip(ks, src):
+        qs[k], rs[k] = torch.empty_like(i_k), torch.empty_like(i_k)
+    with _timed("emb_qr_split_indices"):
+        rc = lib.dlrm_emb_qr_split_indices(len(ks), _lib.i64_array([rows[k] for k in ks]), _i32_array([collisions[k] for k in ks]),
+                                           _lib.ptr_array([i_k.data_ptr() if i_k.numel() else 0 for i_k in src]),
+                                           _lib.i64_array([i_k.numel() for i_k in src]), bags.idx_bits,
+                                           _lib.ptr_array([qs[k].data_ptr() if qs[k].numel() else 0 for k in ks]),
+                                           _lib.ptr_array([rs[k].data_ptr() if rs[k].numel() else 0 for k in ks]), _stream(src[0]))
+    _lib.check(rc, "dlrm_emb_qr_split_indices")
+    return qs, rs
+
+
+def qr_virtual_bags(rows: Sequence[int], collisions: Sequence[int], bags: BagBatch) -> BagBatch:
+    """The bags of the virtual table list: a QR table becomes two plain tables (its q ids, then its r ids) that share its bag offsets; a
+    plain table stays one.  What the sparse updates (emb_bwd_sgd, emb_bwd_coo, ...) take together with emb_qr_bwd_split's buffer."""
+    qs, rs = emb_qr_split_indices(rows, collisions, bags)
+    lS_o, lS_i = [], []
+    for k, c in enumerate(collisions):
+        off, idx = bags._off_src[k], bag_index_tensor(bags, k)
+        if c:
+            lS_o += [off, off]
+            lS_i += [qs[k], rs[k]]
+        else:
+            lS_o.append(off)
+            lS_i.append(idx)
+    vb = BagBatch(lS_o, lS_i, None)
+    vb.ignore_oob = bags.ignore_oob
+    return vb
 
 
 _scratch_ws = {}   # (kind, device, stream) -> cached uint8 scratch: "emb" the workspace of the sort-based updates, "wgrad" the split-K slabs

@@ -40,6 +40,7 @@ class DLRM(DLRM_Net):
     the embedding bag collection is given by its table sizes and the embedding dimension."""
 
     quantize_embedding = _no_quantized_tables
+    _qr_supported = False
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
                  dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int]):
@@ -92,6 +93,7 @@ class ShardedDLRM(DLRM_Net):
     batch; DDP averages only the dense parameters)."""
 
     quantize_embedding = _no_quantized_tables
+    _qr_supported = False
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], multi_hot_sizes: Sequence[int], embedding_dim: int,
                  dense_in_features: int, dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int],
@@ -232,6 +234,7 @@ class DLRM_DCN(DLRM_Net):
     through a DCN-v2 low-rank cross network; the over-arch takes its [B, F*D] output and ends with a bare Linear (logits)."""
 
     quantize_embedding = _no_quantized_tables
+    _qr_supported = False
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
                  dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int], dcn_num_layers: int,

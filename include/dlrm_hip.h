@@ -118,6 +118,39 @@ int dlrm_emb_fwd_quant(int T, int64_t B, int D, int bits,
                        const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
                        float* out, int64_t out_ld, int64_t* err, void* stream);
 
+/* Quotient-remainder (QR, compositional) embedding tables: csrc/emb_qr.hip.
+ * Replaces: tricks/qr_embedding_bag.py (QREmbeddingBag.forward and its autograd), built by DLRM_Net.create_emb for every table with more than
+ *           qr_threshold rows under --qr-flag (dlrm_s_pytorch.py:258-266).
+ * A QR table of n categories and c = collisions keeps weight_q [ceil(n / c), D] and weight_r [c, D]:
+ *     sq[b] = sum_{i in bag} Wq[q_i],  sr[b] = sum_{i in bag} Wr[r_i],  out[b] = sq[b] * sr[b] (DLRM_QR_MULT) | sq[b] + sr[b] (DLRM_QR_ADD)
+ *   — the composition of the two POOLED sums; each sum in index order per column from +0.0, one multiply / add: bit-identical to the two
+ *   F.embedding_bag(mode="sum") calls of the reference on the CPU.
+ *   q_i = (int64)((float)id / (float)c) — the reference's `(input / c).long()`: a FLOAT32 division (operands rounded to nearest, IEEE divide,
+ *   truncation).  It equals id / c for id < 2^24 and chooses other rows above; r_i = id mod c (integer).  An id outside [0, n), or one whose
+ *   quotient is >= ceil(n / c) (possible only above 2^24), is skipped in both components and reported through `err` as {1, table, id, n}.
+ * dlrm_emb_fwd_qr: dlrm_emb_fwd's operands and conventions (all tables in one launch, idx_bits, off_t[B] := nnz[t], out / out_ld, empty bags give
+ *   zeros; no pooling weights).  collisions_host[t] = 0: a plain table (weight_host[t] [rows_host[t], D], weight_r_host[t] ignored; the bits of
+ *   dlrm_emb_fwd); > 0: a QR table, weight_host[t] = weight_q, weight_r_host[t] = weight_r, rows_host[t] = n.
+ *   saved (nullable): device float* [B, >= 2*Tq*D] at pitch saved_ld, Tq = number of QR tables; the j-th QR table's sq goes to columns
+ *   [2j*D, 2j*D + D), its sr to the next D — what dlrm_emb_qr_bwd_split reads, so that the backward pass gathers nothing.
+ *   D <= 512.  D % 4 == 0 with 16-byte aligned operands (pitches % 4 == 0) takes the 16-bytes-per-lane kernel, everything else a scalar one.
+ * dlrm_emb_qr_bwd_split: the gradient buffer of the VIRTUAL table list — a QR table is two plain tables (q, then r) sharing the bag offsets, a
+ *   plain table stays one; Tv = T + Tq.  From dout [B, >= T*D]:  gout[b, v*D ..] = dout * sr, gout[b, (v+1)*D ..] = dout * sq (MULT; `saved` as
+ *   written by the forward) | dout, dout (ADD; saved may be NULL) | a copy for a plain table.  gout: [B, >= Tv*D] at pitch gout_ld.
+ *   dlrm_emb_bwd_sgd / dlrm_emb_bwd_coo / ... over the virtual tables then are the reference's sparse per-component update.
+ * dlrm_emb_qr_split_indices: T QR tables (all collisions > 0): q_out_host[t][i], r_out_host[t][i] = the split of indices_host[t][i], in the width
+ *   of the ids; a lookup the forward skips gets -1 / -1 (which the update kernels skip and report in turn). */
+#define DLRM_QR_MULT 0
+#define DLRM_QR_ADD  1
+int dlrm_emb_fwd_qr(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
+                    const int64_t* rows_host, const int32_t* collisions_host, int op,
+                    const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
+                    float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err, void* stream);
+int dlrm_emb_qr_bwd_split(int T, int64_t B, int D, const int32_t* collisions_host, int op, const float* dout, int64_t dout_ld,
+                          const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld, void* stream);
+int dlrm_emb_qr_split_indices(int T, const int64_t* rows_host, const int32_t* collisions_host, const void* const* indices_host,
+                              const int64_t* nnz_host, int idx_bits, void* const* q_out_host, void* const* r_out_host, void* stream);
+
 /* K2+K3  fused EmbeddingBag backward + sparse SGD step, all tables, no gradient materialised.
  * Replaces: autograd `EmbeddingBagBackward` (sparse COO grad) followed by
  *           `torch.optim.SGD.step` on that grad (dlrm_s_pytorch.py:1613,1620; optimizer :1343-1369).
