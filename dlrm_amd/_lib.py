@@ -46,6 +46,9 @@ SIGNATURES = {
     "dlrm_emb_fwd_qr": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _pi64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
     "dlrm_emb_qr_bwd_split": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "dlrm_emb_qr_split_indices": (_i32, [_i32, _pi64, C.POINTER(_i32), _pp, _pi64, _i32, _pp, _pp, _vp]),
+    "dlrm_emb_fwd_md": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _pp, _pp, _pi64, _pp, _pp, _pi64, _i32, _vp, _i64, _vp, _i64, C.POINTER(_i32), _vp, _vp]),
+    "dlrm_emb_md_bwd_workspace_bytes": (_i64, [_i32, _i64, _i32, C.POINTER(_i32)]),
+    "dlrm_emb_md_bwd": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _pp, _vp, _i64, _vp, _i64, C.POINTER(_i32), _vp, _i64, _pp, _vp, _i64, _vp]),
     "dlrm_emb_bwd_workspace_bytes": (_i64, [_i32, _pi64, _pi64]),
     "dlrm_emb_sort_kind": (_i32, [_i32, _pi64, _pi64]),
     "dlrm_cast_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),

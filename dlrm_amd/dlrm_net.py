@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
                          EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
-                         OutSlot, QREmbeddingBagsFunction)
+                         MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
 
@@ -144,6 +144,52 @@ class QREmbeddingBagHolder(nn.Module):
         return "%d, %d, collisions=%d, operation=%s" % (self.num_categories, self.embedding_dim[0], self.num_collisions, self.operation)
 
 
+class PrEmbeddingBagHolder(nn.Module):
+    """Parameter holder of one mixed-dimension table (the reference's tricks/md_embedding_bag.py PrEmbeddingBag): `embs`, an
+    nn.EmbeddingBag(n, d, mode="sum", sparse=True) holder, and `proj`, nn.Linear(d, base, bias=False) when d < base and nn.Identity() when
+    equal — state_dict has the reference's keys `emb_l.{k}.embs.weight` and `emb_l.{k}.proj.weight`.  On the CPU (device None) it is built by
+    the reference's own calls in the reference's order, because equal seeds must give equal initial parameters: nn.EmbeddingBag's N(0, 1)
+    init and xavier_uniform_ on the table (both replaced below, both spend torch's generator), nn.Linear's init and xavier_uniform_ on the
+    projection, then the table from numpy's U(-sqrt(1/n), sqrt(1/n)) (dlrm_s_pytorch.py:270-275).  With a device the table is drawn there
+    from the same distribution (no parity claim).  Lookups of a model go through dlrm_emb_fwd_md for all tables at once
+    (MDEmbeddingBagsFunction); `forward` here is the same kernel for this table alone and is FORWARD-ONLY, like the QR holder's."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, base_dim: int, device=None):
+        super().__init__()
+        n, d, base = int(num_embeddings), int(embedding_dim), int(base_dim)
+        if d > base:
+            raise ValueError("Embedding dim " + str(d) + " > base dim " + str(base))
+        self.base_dim = base
+        bound = np.sqrt(1 / n)
+        if device is None:
+            self.embs = nn.EmbeddingBag(n, d, mode="sum", sparse=True)
+            torch.nn.init.xavier_uniform_(self.embs.weight)
+        if d < base:
+            self.proj = nn.Linear(d, base, bias=False)
+            torch.nn.init.xavier_uniform_(self.proj.weight)
+        else:
+            self.proj = nn.Identity()
+        if device is None:
+            w = np.random.uniform(low=-bound, high=bound, size=(n, d)).astype(np.float32)
+            self.embs.weight.data = torch.tensor(w, requires_grad=True)
+        else:
+            w = torch.empty((n, d), dtype=torch.float32, device=device).uniform_(-bound, bound)
+            self.embs = nn.EmbeddingBag(n, d, mode="sum", sparse=True, _weight=w)
+
+    def proj_weight(self):
+        return self.proj.weight if isinstance(self.proj, nn.Linear) else None
+
+    def forward(self, input, offsets=None, per_sample_weights=None):
+        if per_sample_weights is not None:
+            sys.exit("ERROR: mixed dimensions with weighted pooling is not supported")
+        if offsets is None:
+            raise RuntimeError("dlrm_amd: PrEmbeddingBagHolder takes 1-D indices with bag offsets")
+        p = self.proj_weight()
+        spec = (self.base_dim, [p is not None], False)       # (no pooled sums kept: nothing flows back)
+        with torch.no_grad():
+            return MDEmbeddingBagsFunction.apply(None, ops.BagBatch([offsets], [input]), None, spec, self.embs.weight, *([p] if p is not None else []))
+
+
 class EmbeddingUpdateHook:
     """Applies the fused sparse embedding update when an optimizer steps.
 
@@ -196,6 +242,7 @@ class DLRM_Net(nn.Module):
     # the torchrec variants set it False: their constructors take no qr_* argument, so the refusal in create_emb guards a subclass or a caller
     # that sets the qr_* attributes itself (ShardedDLRM calls create_emb directly)
     _qr_supported = True
+    _md_supported = True        # (the same for mixed-dimension tables)
 
     # ---------------------------------------------------------------- parameter construction
     def create_mlp(self, ln, sigmoid_layer):
@@ -220,6 +267,23 @@ class DLRM_Net(nn.Module):
         parity); lookups go through the batched HIP kernel, not through the holders' forward."""
         tables = nn.ModuleList()
         pool_w = []
+        # --md-flag with per-table widths (dlrm_s_pytorch.py:1213-1219 turns m_spa into md_solver's list): every refusal before a table is built
+        md = bool(getattr(self, "md_flag", False)) and not np.isscalar(m) and np.ndim(m) == 1
+        m_plain, base = m, None
+        if md:
+            m = [int(d) for d in (m.tolist() if hasattr(m, "tolist") else m)]
+            base = max(m)
+            if len(m) != ln.size or min(m) < 1:
+                sys.exit("ERROR: --md-flag needs one embedding dimension >= 1 per table, got %d for %d tables" % (len(m), ln.size))
+            if not self._md_supported:
+                sys.exit("ERROR: mixed-dimension embeddings are built for DLRM_Net only, not for the torchrec variants (%s)" % type(self).__name__)
+            if weighted_pooling is not None:
+                sys.exit("ERROR: mixed dimensions with weighted pooling is not supported")
+            if getattr(self, "qr_flag", False):
+                sys.exit("ERROR: --md-flag and --qr-flag cannot be combined (the reference builds QR tables only, with a list-valued dimension)")
+            if ext_dist.is_distributed():
+                sys.exit("ERROR: mixed-dimension embedding tables are single-process only (the table-sharded distributed forward is not "
+                         "built for them)")
         for i in range(ln.size):
             if ext_dist.is_distributed() and i not in self.local_emb_indices:
                 continue
@@ -241,20 +305,30 @@ class DLRM_Net(nn.Module):
                 pool_w.append(None)
                 continue
             if getattr(self, "md_flag", False) and n > self.md_threshold:
-                sys.exit("ERROR: mixed-dimension embeddings are not supported by the MI355X DLRM_Net")
+                if not md:
+                    # (a scalar width with a table above the threshold: the reference raises TypeError at max(m) there)
+                    sys.exit("ERROR: mixed-dimension embeddings are not supported by the MI355X DLRM_Net")
+                # the reference's PrEmbeddingBag (dlrm_s_pytorch.py:267-275)
+                tables.append(PrEmbeddingBagHolder(n, int(m[i]), base, device=_EMB_INIT_DEVICE))
+                pool_w.append(None)
+                continue
+            if md:
+                # a table at or below md_threshold: the reference hands the LIST m to nn.EmbeddingBag and raises; built here as the plain
+                # [n, base] table its line 269 (`else base`) evidently meant — no reference counterpart
+                m_plain = base
             bound = np.sqrt(1 / n)
             if getattr(self, "qr_flag", False) and _EMB_INIT_DEVICE is None:
                 # the reference constructs nn.EmbeddingBag(n, m) first, whose own N(0, 1) init consumes n*m draws of TORCH's generator before
                 # the numpy values replace it (dlrm_s_pytorch.py:277-284); the QR tables after this one are drawn from that generator, so
                 # equal seeds give equal QR tables only if the same draws are spent here
-                torch.empty((n, m), dtype=torch.float32).normal_()
+                torch.empty((n, m_plain), dtype=torch.float32).normal_()
             if _EMB_INIT_DEVICE is None:
-                w = torch.tensor(np.random.uniform(low=-bound, high=bound, size=(n, m)).astype(np.float32))
+                w = torch.tensor(np.random.uniform(low=-bound, high=bound, size=(n, m_plain)).astype(np.float32))
             else:
                 # benchmark-scale tables (tens of GB) cannot go through a float64 numpy temporary on the
                 # host: same distribution, drawn on the device (see set_embedding_init)
-                w = torch.empty((n, m), dtype=torch.float32, device=_EMB_INIT_DEVICE).uniform_(-bound, bound)
-            holder = nn.EmbeddingBag(n, m, mode="sum", sparse=True, _weight=w)
+                w = torch.empty((n, m_plain), dtype=torch.float32, device=_EMB_INIT_DEVICE).uniform_(-bound, bound)
+            holder = nn.EmbeddingBag(n, m_plain, mode="sum", sparse=True, _weight=w)
             pool_w.append(None if weighted_pooling is None else torch.ones(n, dtype=torch.float32))
             tables.append(holder)
         return tables, pool_w
@@ -333,6 +407,9 @@ class DLRM_Net(nn.Module):
         if ndevices > 1:
             sys.exit("ERROR: single-process multi-GPU (ndevices=%d) is not supported; launch one process per "
                      "GPU (torchrun) to use table-sharded embeddings over RCCL" % ndevices)
+        if md_flag and not np.isscalar(m_spa) and np.ndim(m_spa) == 1 and len(m_spa) and int(ln_bot[-1]) != int(max(m_spa)):
+            # (run() checks the scalar before md_solver replaces it, dlrm_s_pytorch.py:1197-1219; the smallest table keeps it: base = max(m))
+            sys.exit("ERROR: arch-sparse-feature-size " + str(int(max(m_spa))) + " does not match last dim of bottom mlp " + str(int(ln_bot[-1])))
         self.emb_l, pool_w = self.create_emb(m_spa, ln_emb, weighted_pooling)
         if self.weighted_pooling == "learned":
             # dlrm_s_pytorch.py:370-375: the per-row pooling weights become parameters (state_dict keys v_W_l.{k})
@@ -412,9 +489,15 @@ class DLRM_Net(nn.Module):
         for e in emb_l:
             if isinstance(e, QREmbeddingBagHolder):
                 out += [e.weight_q, e.weight_r]
+            elif isinstance(e, PrEmbeddingBagHolder):
+                out.append(e.embs.weight)                # (its projection is a dense parameter: the optimizer's own business)
             else:
                 out.append(e.weight)
         return out
+
+    @staticmethod
+    def _has_md(emb_l) -> bool:
+        return emb_l is not None and any(isinstance(e, PrEmbeddingBagHolder) for e in emb_l)
 
     @staticmethod
     def _has_qr(emb_l) -> bool:
@@ -423,7 +506,13 @@ class DLRM_Net(nn.Module):
     @staticmethod
     def _emb_dim(emb_l) -> int:
         e = emb_l[0]
+        if isinstance(e, PrEmbeddingBagHolder):
+            return e.base_dim
         return int((e.weight_q if isinstance(e, QREmbeddingBagHolder) else e.weight).size(1))
+
+    @staticmethod
+    def _md_base(emb_l) -> int:
+        return next(e.base_dim for e in emb_l if isinstance(e, PrEmbeddingBagHolder))
 
     def _qr_spec(self, emb_l):
         """(rows, collisions, operation, keep the two pooled sums for backward) of QREmbeddingBagsFunction"""
@@ -445,6 +534,14 @@ class DLRM_Net(nn.Module):
             if v_W_l is not None and any(w is not None for w in v_W_l):
                 sys.exit("ERROR: quotient remainder with weighted pooling is not supported")
             return QREmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, self._qr_spec(emb_l), *ws)
+        if self._has_md(emb_l):
+            # the MD lookup + projection (dlrm_emb_fwd_md) for ALL tables of the list, plain ones included (identity); backward hands each
+            # width group to the same sink and returns the dense projection gradients
+            if v_W_l is not None and any(w is not None for w in v_W_l):
+                sys.exit("ERROR: mixed dimensions with weighted pooling is not supported")
+            projs = [e.proj_weight() if isinstance(e, PrEmbeddingBagHolder) else None for e in emb_l]
+            spec = (self._md_base(emb_l), [p is not None for p in projs], torch.is_grad_enabled())
+            return MDEmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, spec, *ws, *[p for p in projs if p is not None])
         return EmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, *ws, *self._pool_weights(v_W_l, ws[0].device))
 
     def apply_emb(self, lS_o, lS_i, emb_l, v_W_l):
@@ -490,6 +587,8 @@ class DLRM_Net(nn.Module):
             return
         if self._has_qr(self.emb_l):
             sys.exit("ERROR: 4 and 8-bit quantization with quotient remainder is not supported")
+        if self._has_md(self.emb_l):
+            sys.exit("ERROR: 4 and 8-bit quantization with mixed dimensions is not supported")
         if self.quantize_emb:
             sys.exit("ERROR: the embedding tables are quantized already (%d bits)" % self.quantize_bits)
         if ext_dist.is_distributed():
@@ -647,6 +746,9 @@ class DLRM_Net(nn.Module):
                 if self._has_qr(self.emb_l):
                     sys.exit("ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
                              "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
+                if self._has_md(self.emb_l):
+                    sys.exit("ERROR: the fused row-wise Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
+                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
                 _, clr, eps, states = plan
                 ops.emb_bwd_rowwise_adagrad(weights, states, bags, dout, clr, eps)
 
@@ -691,10 +793,10 @@ class DLRM_Net(nn.Module):
             else:
                 z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)
             return self._clamp(self.apply_mlp(z, self.top_l))
-        # (a model with a QR table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it the
+        # (a model with a QR or a mixed-dimension table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it the
         # step-time update, update_in_backward included)
         if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and ops.gather_ok(1 + T, D)
-                and not self._has_qr(self.emb_l) and not any(w is not None for w in (self.v_W_l or []))):
+                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l) and not any(w is not None for w in (self.v_W_l or []))):
             bags = self._bags(lS_o, lS_i, None)
             # nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the
             # reference computes it): ops.offsets_are_iota (dlrm_amd/iota.py) proves offsets == arange(B) on the device, once per offsets tensor
@@ -752,6 +854,9 @@ class DLRM_Net(nn.Module):
             sys.exit("ERROR: quantized embedding tables are single-process inference only (distributed quantized inference is not built)")
         if self._has_qr(self.emb_l):
             sys.exit("ERROR: QR embedding tables are single-process only (the table-sharded distributed forward is not built for them)")
+        if self._has_md(self.emb_l):
+            sys.exit("ERROR: mixed-dimension embedding tables are single-process only (the table-sharded distributed forward is not built "
+                     "for them)")
         batch_size = dense_x.size(0)
         if batch_size < ext_dist.my_size:
             sys.exit("ERROR: batch_size (%d) must be larger than number of ranks (%d)" % (batch_size, ext_dist.my_size))

@@ -588,6 +588,45 @@ class QREmbeddingBagsFunction(Function):
         return (None, None, None, None) + (None,) * len(ctx.vweights)
 
 
+class MDEmbeddingBagsFunction(Function):
+    """EmbeddingBagsFunction for a table list with mixed-dimension tables (tricks/md_embedding_bag.py PrEmbeddingBag; dlrm_s_pytorch.py:267-275):
+    one dlrm_emb_fwd_md launch pools every table at its own width and projects it to the common width D.  spec = (D, has_proj, keep_sums);
+    `tensors` = the T tables, then the [D, d_t] projection weight of every table with has_proj[t], in table order.  Backward is one
+    dlrm_emb_md_bwd call: the dense projection gradients come back as the gradients of the projection inputs, and the gradient of the pooled
+    sums — laid out by ops.MDLayout, tables of equal width contiguous — is handed to `sink` once per width, with that group's tables and bags:
+    the sparse updates are the existing ones."""
+
+    @staticmethod
+    def forward(ctx, sink, bags, out_slot, spec, *tensors):
+        D, has_proj, keep_sums = spec
+        T = bags.T
+        weights = tensors[:T]
+        it = iter(tensors[T:])
+        projs = [next(it) if h else None for h in has_proj]
+        layout = ops.MDLayout([w.size(1) for w in weights])
+        out = out_slot.get() if out_slot is not None else alloc2d(bags.B, T * D, weights[0])
+        saved = torch.empty((bags.B, layout.width), dtype=torch.float32, device=out.device) if keep_sums else None
+        ops.emb_fwd_md(weights, projs, D, bags, out, saved, layout.cols if keep_sums else None)
+        ctx.sink, ctx.bags, ctx.D, ctx.layout = sink, bags, D, layout
+        ctx.weights, ctx.projs = weights, projs      # parameters (leaves) — kept by reference, not via save_for_backward
+        ctx.saved = saved
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.sink is None:
+            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+        T, layout = len(ctx.weights), ctx.layout
+        need = iter(ctx.needs_input_grad[4 + T:])
+        want = [p_ is not None and next(need) for p_ in ctx.projs]
+        dout = _rowmajor(dout)
+        gout = torch.empty((dout.size(0), layout.width), dtype=torch.float32, device=dout.device)
+        _, dprojs = ops.emb_md_bwd(ctx.projs, layout.dims, ctx.D, dout, ctx.saved, layout.cols, gout, want)   # (the sums stay with the node)
+        for d, ks, c0 in layout.groups:
+            ctx.sink(tuple(ctx.weights[k] for k in ks), ops.bag_subset(ctx.bags, ks), gout[:, c0:c0 + len(ks) * d])
+        return (None, None, None, None) + (None,) * T + tuple(g for g, p_ in zip(dprojs, ctx.projs) if p_ is not None)
+
+
 class InteractFunction(Function):
     """R = [x | strictly-lower-triangular pairwise dots of the F feature vectors].
 

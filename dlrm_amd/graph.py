@@ -105,6 +105,8 @@ class GraphedTrainStep:
             sys.exit("ERROR: GraphedTrainStep captures a training step; a model with quantized embedding tables is inference only")
         if getattr(model, "_has_qr", None) is not None and model._has_qr(getattr(model, "emb_l", None)):
             sys.exit("ERROR: GraphedTrainStep is not built for QR embedding tables (their backward allocates the split index arrays per step)")
+        if getattr(model, "_has_md", None) is not None and model._has_md(getattr(model, "emb_l", None)):
+            sys.exit("ERROR: GraphedTrainStep is not built for mixed-dimension embedding tables (their backward builds the per-width bag lists per step)")
         self.model, self.optimizer = model, optimizer
         for g in optimizer.param_groups:
             # a decaying step size (RWSAdagrad: clr = lr / (1 + (step - 1) * lr_decay)) is computed on the host at capture time

@@ -538,9 +538,158 @@ def qr_virtual_bags(rows: Sequence[int], collisions: Sequence[int], bags: BagBat
     return vb
 
 
+# ---- mixed-dimension (MD) tables: csrc/emb_md.hip.  Table t is `weights[t]` [rows_t, d_t] with its own width and `projs[t]`, the [D, d_t] weight
+# of a bias-free nn.Linear(d_t, D), or None (nn.Identity: d_t == D).
+def alpha_power_rule(n: torch.Tensor, alpha: float, d0=None, B=None) -> torch.Tensor:
+    """d_k = lambda * n_k^-alpha over the SORTED row counts `n` (float32 arithmetic, as tricks/md_embedding_bag.py:45-58): lambda =
+    d0 * n_0^alpha (the smallest table keeps d0) or B / sum n^(1 - alpha) (parameter budget); never below 1; rounded half to even."""
+    n = n.to(torch.float32)
+    if d0 is not None:
+        lamb = d0 * n[0] ** alpha
+    elif B is not None:
+        lamb = B / torch.sum(n ** (1 - alpha))
+    else:
+        raise ValueError("Must specify either d0 or B")
+    d = torch.ones(len(n)) * lamb * n ** (-alpha)
+    d = torch.where(d < 1, torch.ones_like(d), d)
+    if d0 is not None:
+        d[0] = d0
+    return torch.round(d).to(torch.long)
+
+
+def pow_2_round(dims: torch.Tensor) -> torch.Tensor:
+    """the nearest power of two in log scale (md_embedding_bag.py:61-62); an integer tensor here (the reference returns floats)"""
+    return (2 ** torch.round(torch.log2(dims.to(torch.float32)))).to(torch.long)
+
+
+def md_solver(n, alpha: float, d0=None, B=None, round_dim: bool = True, k=None) -> torch.Tensor:
+    """Per-table embedding widths of the mixed-dimension trick (md_embedding_bag.py:22-42; dlrm_s_pytorch.py:1213-1219 calls it with the table
+    sizes, --md-temperature, d0 = --arch-sparse-feature-size and --md-round-dims), in the order of `n`.  Returns an int64 tensor."""
+    n = torch.as_tensor(n)
+    n_sorted, order = torch.sort(n)
+    kk = k[order] if k is not None else torch.ones(len(n))
+    d = alpha_power_rule(n_sorted.to(torch.float32) / kk, alpha, d0=d0, B=B)
+    if round_dim:
+        d = pow_2_round(d)
+    out = torch.empty_like(d)
+    out[order] = d
+    return out
+
+
+class MDLayout:
+    """Columns of the pooled sums (`saved`) and of their gradients (`gout`) for per-table widths `dims`: tables of equal width are contiguous,
+    widths descending, every group starts at a multiple of 4 floats.  cols[t]: first column of table t; groups: (d, [tables], first column) —
+    gout[:, c0 : c0 + len(tables) * d] is the [B, n * d] gradient buffer of the group's tables for the sparse updates; width: columns in all
+    (a multiple of 4)."""
+
+    def __init__(self, dims: Sequence[int]):
+        self.dims = [int(d) for d in dims]
+        self.cols = [0] * len(self.dims)
+        self.groups = []
+        c = 0
+        for d in sorted(set(self.dims), reverse=True):
+            ks = [t for t, dt in enumerate(self.dims) if dt == d]
+            self.groups.append((d, ks, c))
+            for i, t in enumerate(ks):
+                self.cols[t] = c + i * d
+            c = (c + len(ks) * d + 3) // 4 * 4
+        self.width = max(c, 4)
+
+
+def bag_subset(bags: BagBatch, ks: Sequence[int]) -> BagBatch:
+    """the bags of tables `ks` (one width group of an MD table list) as a BagBatch of their own"""
+    sub = BagBatch([bags._off_src[k] for k in ks], [bags._idx_src[k] for k in ks], None)
+    sub.ignore_oob = bags.ignore_oob
+    return sub
+
+
+def _md_desc(weights, projs, D):
+    T = len(weights)
+    if T == 0 or len(projs) != T:
+        raise RuntimeError("dlrm_amd: an MD table list needs one weight and one projection (or None) per table")
+    dims = []
+    for w, p_ in zip(weights, projs):
+        _req(w, "embedding weight", ndim=2)
+        if not w.is_contiguous():
+            raise RuntimeError("dlrm_amd: embedding tables must be contiguous [rows, d]")
+        d = int(w.size(1))
+        if p_ is None:
+            if d != D:
+                raise RuntimeError("dlrm_amd: an MD table without projection must have the common width %d, got %d" % (D, d))
+        else:
+            _req(p_, "projection weight", ndim=2)
+            if not p_.is_contiguous() or tuple(p_.shape) != (D, d):
+                raise RuntimeError("dlrm_amd: the projection of a table of width %d is a contiguous [%d, %d] tensor, got %s" % (d, D, d, tuple(p_.shape)))
+        dims.append(d)
+    return dims
+
+
+def emb_fwd_md(weights: Sequence[torch.Tensor], projs: Sequence[Optional[torch.Tensor]], D: int, bags: BagBatch, out: torch.Tensor,
+               saved: Optional[torch.Tensor] = None, cols: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """out[b, t*D:(t+1)*D] = (sum-pooled bag (t, b) of weights[t]) @ projs[t].T (projs[t] None: the pooled bag itself) for all tables in one launch.
+    `out` is a [B, >= T*D] view (row stride free).  saved + cols (MDLayout.cols): the pooled sums go to saved[:, cols[t] : cols[t] + d_t]."""
+    lib = _lib.load()
+    D = int(D)
+    dims = _md_desc(weights, projs, D)
+    _req(out, "out", ndim=2)
+    if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_fwd_md shape mismatch")
+    if bags._psw is not None:
+        raise RuntimeError("dlrm_amd: MD tables take no per-sample (pooling) weights")
+    sv_p, sv_ld, col_a = None, 0, None
+    if saved is not None:
+        _req(saved, "saved", ndim=2)
+        if cols is None or len(cols) != bags.T or saved.size(0) != bags.B or any(c < 0 or c + d > saved.size(1) for c, d in zip(cols, dims)):
+            raise RuntimeError("dlrm_amd: emb_fwd_md `saved` is a [B, >= max(cols[t] + d_t)] buffer with one first column per table")
+        sv_p, sv_ld, col_a = C.c_void_p(saved.data_ptr()), _ld(saved), _i32_array(cols)
+    err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
+    with _timed("emb_fwd"):
+        rc = lib.dlrm_emb_fwd_md(bags.T, bags.B, D, _i32_array(dims), _lib.ptr_array([w.data_ptr() for w in weights]),
+                                 _lib.ptr_array([p_.data_ptr() if p_ is not None else 0 for p_ in projs]),
+                                 _lib.i64_array([w.size(0) for w in weights]), bags._idx, bags._off, bags._nnz, bags.idx_bits,
+                                 C.c_void_p(out.data_ptr()), _ld(out), sv_p, sv_ld, col_a, err, _stream(out))
+    _lib.check(rc, "dlrm_emb_fwd_md")
+    return out
+
+
+def emb_md_bwd(projs: Sequence[Optional[torch.Tensor]], dims: Sequence[int], D: int, dout: torch.Tensor, saved: Optional[torch.Tensor],
+               cols: Sequence[int], gout: torch.Tensor, want_dproj: Optional[Sequence[bool]] = None):
+    """Backward of emb_fwd_md in one call: gout[:, cols[t] : cols[t] + d_t] = dout[:, t*D:(t+1)*D] @ projs[t] (a copy for an identity table) and, for
+    every projected table with want_dproj[t] (default: all), dproj[t] = dout[:, t*D:(t+1)*D].T @ saved[:, cols[t] : cols[t] + d_t] — a fresh [D, d_t]
+    tensor, deterministic.  Returns (gout, [dproj or None per table])."""
+    lib = _lib.load()
+    T, D = len(projs), int(D)
+    _req(dout, "dout", ndim=2)
+    _req(gout, "gout", ndim=2)
+    B = dout.size(0)
+    if len(dims) != T or len(cols) != T or dout.size(1) < T * D or gout.size(0) != B or any(c < 0 or c + d > gout.size(1) for c, d in zip(cols, dims)):
+        raise RuntimeError("dlrm_amd: emb_md_bwd shape mismatch")
+    want = [p_ is not None and (want_dproj is None or bool(want_dproj[t])) for t, p_ in enumerate(projs)]
+    dprojs = [torch.empty((D, int(d)), dtype=torch.float32, device=dout.device) if w_ else None for d, w_ in zip(dims, want)]
+    sv_p, sv_ld, ws_p, ws_n = None, 0, None, 0
+    if any(want):
+        if saved is None:
+            raise RuntimeError("dlrm_amd: this MD lookup ran without gradients enabled; its pooled sums were not kept")
+        _req(saved, "saved", ndim=2)
+        if saved.size(0) != B or any(c + d > saved.size(1) for c, d in zip(cols, dims)):
+            raise RuntimeError("dlrm_amd: emb_md_bwd `saved` is the [B, >= max(cols[t] + d_t)] buffer emb_fwd_md filled")
+        sv_p, sv_ld = C.c_void_p(saved.data_ptr()), _ld(saved)
+        need = lib.dlrm_emb_md_bwd_workspace_bytes(T, B, D, _i32_array(dims))
+        if need < 0:
+            raise RuntimeError("dlrm_amd: dlrm_emb_md_bwd_workspace_bytes failed")
+        ws = _scratch("md", need, dout.device)
+        ws_p, ws_n = C.c_void_p(ws.data_ptr()), ws.numel()
+    with _timed("emb_md_bwd"):
+        rc = lib.dlrm_emb_md_bwd(T, B, D, _i32_array(dims), _lib.ptr_array([p_.data_ptr() if p_ is not None else 0 for p_ in projs]),
+                                 C.c_void_p(dout.data_ptr()), _ld(dout), sv_p, sv_ld, _i32_array(cols), C.c_void_p(gout.data_ptr()), _ld(gout),
+                                 _lib.ptr_array([g.data_ptr() if g is not None else 0 for g in dprojs]), ws_p, ws_n, _stream(dout))
+    _lib.check(rc, "dlrm_emb_md_bwd")
+    return gout, dprojs
+
+
 _scratch_ws = {}   # (kind, device, stream) -> cached uint8 scratch: "emb" the workspace of the sort-based updates, "wgrad" the split-K slabs
-                   # of the weight gradients, "tower" the slabs of tower_wgrad.  Per stream: kernels of one stream are ordered, so one buffer per
-                   # kind suffices — and a buffer allocated under one stream is never handed to kernels of another (the caching allocator
+                   # of the weight gradients, "tower" the slabs of tower_wgrad, "md" the slab partials of emb_md_bwd.  Per stream: kernels of
+                   # one stream are ordered, so one buffer per kind suffices — and a buffer allocated under one stream is never handed to kernels of another (the caching allocator
                    # orders re-use of freed memory within the allocating stream only).  Grow-only; GraphedTrainStep pins what a capture used.
 
 

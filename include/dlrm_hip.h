@@ -151,6 +151,36 @@ int dlrm_emb_qr_bwd_split(int T, int64_t B, int D, const int32_t* collisions_hos
 int dlrm_emb_qr_split_indices(int T, const int64_t* rows_host, const int32_t* collisions_host, const void* const* indices_host,
                               const int64_t* nnz_host, int idx_bits, void* const* q_out_host, void* const* r_out_host, void* stream);
 
+/* Mixed-dimension (MD) embedding tables: csrc/emb_md.hip.
+ * Replaces: tricks/md_embedding_bag.py (PrEmbeddingBag.forward and its autograd), built by DLRM_Net.create_emb for every table with more than
+ *           md_threshold rows under --md-flag (dlrm_s_pytorch.py:267-275).
+ * Table t keeps W_t [rows_t, d_t] with its own width d_t = dims_host[t] <= D and a bias-free projection P_t = proj_host[t], [D, d_t] row-major
+ * (nn.Linear(d_t, D).weight); proj_host[t] == NULL is nn.Identity and needs d_t == D (else DLRM_E_ARG).
+ *     pooled_t[b, c] = sum_{i in bag(t,b)} W_t[idx_i, c]       in index order from +0.0: the bits of dlrm_emb_fwd at D = d_t
+ *     out[b*out_ld + t*D + j] = fmaf chain over c = 0 .. d_t-1 from +0.0 of pooled_t[b, c] * P_t[j, c]   (identity: pooled_t[b, j])
+ *   deterministic, independent of the launch shape, of B and of the path taken.
+ * dlrm_emb_fwd_md: dlrm_emb_fwd's operands and conventions (all tables in one launch, idx_bits, off_t[B] := nnz[t], out / out_ld, empty bags give
+ *   zeros, out-of-range ids skipped and reported through `err`; no pooling weights).  saved (nullable): device float* [B, >= max(col + d)] at pitch
+ *   saved_ld; pooled_t[b, :] goes to columns col_host[t] .. col_host[t] + d_t, so that the backward pass gathers nothing.  D <= 512.
+ *   Fast path: D % 4 == 0 with a 16-byte aligned out (out_ld % 4 == 0) and (D + 4) * d_t + 32 * (d_t | 1) floats within 64 KiB of LDS: P_t staged in
+ *   LDS, 16-byte stores; rows are read 16 bytes per lane when d_t % 4 == 0 and W_t / saved / col_host[t] are 16-byte aligned.  Everything else takes
+ *   a form of the same kernel that is correct, not fast (P_t read from global memory: D = 512 with d_t >= 32; 4-byte accesses).
+ * dlrm_emb_md_bwd: one call for all tables.
+ *   (a) gout[b*gout_ld + col_t + c] = fmaf chain over j = 0 .. D-1 from +0.0 of dout[b*dout_ld + t*D + j] * P_t[j, c]; identity: a copy.  gout has
+ *       saved's column layout: with tables of equal d_t contiguous in col_host, a column view of gout is the [B, n*d] gradient buffer that
+ *       dlrm_emb_bwd_sgd / dlrm_emb_bwd_coo take for that width group (dout_ld = gout_ld).
+ *   (b) dproj_host[t][j, c] = sum_b dout[b, t*D + j] * saved[b, col_t + c], OVERWRITTEN (NULL: not wanted; must be NULL for identity tables).  B is
+ *       cut into slabs of 512 bags; a slab partial is the fmaf chain over its bags in order, written to `workspace`
+ *       (dlrm_emb_md_bwd_workspace_bytes; 16-byte aligned) and the partials are summed in slab order by a second kernel: no atomics, bit-identical
+ *       from run to run.  Every shape takes these kernels (nothing goes through dlrm_linear_bwd_weight). */
+int dlrm_emb_fwd_md(int T, int64_t B, int D, const int32_t* dims_host, const void* const* weight_host, const void* const* proj_host,
+                    const int64_t* rows_host, const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                    int idx_bits, float* out, int64_t out_ld, float* saved, int64_t saved_ld, const int32_t* col_host, int64_t* err, void* stream);
+int64_t dlrm_emb_md_bwd_workspace_bytes(int T, int64_t B, int D, const int32_t* dims_host);
+int dlrm_emb_md_bwd(int T, int64_t B, int D, const int32_t* dims_host, const void* const* proj_host, const float* dout, int64_t dout_ld,
+                    const float* saved, int64_t saved_ld, const int32_t* col_host, float* gout, int64_t gout_ld, void* const* dproj_host,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 /* K2+K3  fused EmbeddingBag backward + sparse SGD step, all tables, no gradient materialised.
  * Replaces: autograd `EmbeddingBagBackward` (sparse COO grad) followed by
  *           `torch.optim.SGD.step` on that grad (dlrm_s_pytorch.py:1613,1620; optimizer :1343-1369).
