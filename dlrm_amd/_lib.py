@@ -125,6 +125,10 @@ SIGNATURES = {
     "dlrm_tower_wgrad": (_i32, [_i64, _i32, C.POINTER(_i32), C.POINTER(_i32), _pp, _pi64, _pp, _pi64, _pp, _pi64, _pp, _vp, _i64, _vp]),
     "dlrm_clamp": (_i32, [_i64, _vp, _f32, _f32, _vp, _vp]),
     "dlrm_clamp_bwd": (_i32, [_i64, _vp, _f32, _f32, _vp, _vp, _vp]),
+    "dlrm_q8_pack_weight": (_i32, [_i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "dlrm_q8_workspace_bytes": (_i64, [_i64, _i32]),
+    "dlrm_q8_quantize_act": (_i32, [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "dlrm_gemm_q8": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
 }
 
 _ERR = {-1: "DLRM_E_ARG (null pointer / bad size)", -2: "DLRM_E_ALIGN", -3: "DLRM_E_RANGE (compiled limit exceeded)",

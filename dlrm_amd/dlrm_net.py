@@ -58,6 +58,7 @@ class FusedMLP(nn.Sequential):
     property of the module and is handed to every C-ABI call — there is no process-wide switch."""
 
     arith = os.environ.get("DLRM_MLP_ARITH", "f32")
+    quant_bits = 32            # 8 / 16 after quantize(): an inference tower (see quantize)
 
     def _layers(self):
         mods = list(self.children())
@@ -80,9 +81,63 @@ class FusedMLP(nn.Sequential):
         """consumer_applies_last_act: the caller promises that the ONLY consumer of the output multiplies the gradient it sends back
         by the derivative of this tower's last ReLU (the interaction backward kernels do, ops.INTERACT_RELU_X) — the tower's
         backward then skips that pass.  Ignored (False) for towers that do not end in a ReLU."""
+        if self.quant_bits != 32:
+            return self._forward_quantized(x, out_slot)
         params, acts = self._layers()
         flag = MLP_CONSUMER_APPLIES_LAST_ACT if (consumer_applies_last_act and acts and acts[-1] == ACT_RELU) else 0
         return MLPFunction.apply(x, acts, out_slot, ops.arith_code(self.arith) | flag, *params)
+
+    def quantize(self, bits):
+        """torch.quantization.quantize_dynamic(tower, {nn.Linear}, qint8 | float16) on the device (dlrm_s_pytorch.py:1473-1480).
+        8: every Linear's weight is packed once as torch packs it (per tensor, symmetric: ops.q8_pack_weight) and forward runs, per layer,
+        the per-call activation quantisation and the int8 MFMA GEMM (ops.linear_q8).  16: the weights are rounded through fp16 in place
+        (saturating at 65504 like torch's packing) and stay fp32 operands of the fp32 GEMM path; activations stay fp32 as in the reference.
+        Any other value returns without change.  From here on the tower is an inference tower: its forward carries no autograd node.
+        The packed int8 weights are not parameters, buffers or state_dict entries (the state_dict keeps the reference's keys and the fp32
+        weights stay, so an int8 tower holds 1.25x the weight bytes, not less): `.to()` / `.cuda()` / `.half()` would leave them behind and
+        `load_state_dict` would change weights that forward no longer reads (or, at 16 bits, store unrounded ones), so both are refused."""
+        if bits not in (8, 16):
+            return
+        if self.quant_bits != 32:
+            sys.exit("ERROR: the MLP tower is quantized already (%d bits)" % self.quant_bits)
+        params, acts = self._layers()
+        if not params or any(not p.is_cuda for p in params):
+            raise RuntimeError("dlrm_amd: quantize packs the tower's weights on the GPU and the quantized layers have no CPU path; "
+                               "move the model to the device first (model.to('cuda'))")
+        if bits == 8:
+            self._q8 = [ops.q8_pack_weight(params[2 * i].detach()) for i in range(len(acts))]
+        else:
+            with torch.no_grad():
+                for i in range(len(acts)):
+                    W = params[2 * i]
+                    W.copy_(W.clamp(-65504.0, 65504.0).half().float())
+        self.quant_bits = bits
+
+    def _apply(self, fn, *args, **kwargs):
+        if self.quant_bits != 32:
+            sys.exit("ERROR: a quantized MLP tower (%d bits) cannot be moved or converted (.to / .cuda / .cpu / .half): its packed weights "
+                     "live on the device they were packed on" % self.quant_bits)
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        if self.quant_bits != 32:
+            sys.exit("ERROR: load_state_dict into a quantized MLP tower (%d bits): quantized towers are constants (inference only) — load "
+                     "the fp32 weights first, then quantize" % self.quant_bits)
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _forward_quantized(self, x, out_slot: Optional[OutSlot]):
+        params, acts = self._layers()
+        with torch.no_grad():
+            if self.quant_bits == 16:
+                return MLPFunction.apply(x.detach(), acts, out_slot, ops.arith_code("f32"), *[p.detach() for p in params])
+            cur = x.detach()
+            if cur.dim() != 2 or (cur.numel() and cur.stride(1) != 1):
+                cur = cur.contiguous()
+            L = len(acts)
+            for i in range(L):
+                out = out_slot.get() if (i == L - 1 and out_slot is not None) else None
+                cur = ops.linear_q8(cur, self._q8[i], params[2 * i + 1].detach(), acts[i], out)
+            return cur
 
     def ends_in_relu(self) -> bool:
         mods = list(self.children())
@@ -214,6 +269,8 @@ class EmbeddingUpdateHook:
     @staticmethod
     def _pre_step(optimizer, args, kwargs):
         for model in list(EmbeddingUpdateHook._models):
+            if getattr(model, "quantize_mlp_bits", 32) != 32:
+                model._refuse_step_if_mlp_quantized(optimizer)
             if getattr(model, "quantize_emb", False):
                 model._refuse_step_if_quantized(optimizer)
                 continue
@@ -243,6 +300,7 @@ class DLRM_Net(nn.Module):
     # that sets the qr_* attributes itself (ShardedDLRM calls create_emb directly)
     _qr_supported = True
     _md_supported = True        # (the same for mixed-dimension tables)
+    quantize_mlp_bits = 32      # 8 / 16 after quantize_mlp()
 
     # ---------------------------------------------------------------- parameter construction
     def create_mlp(self, ln, sigmoid_layer):
@@ -615,6 +673,54 @@ class DLRM_Net(nn.Module):
         self.emb_l = None
         self.quantize_emb = True
         self.quantize_bits = bits
+
+    def quantize_mlp(self, bits):
+        """The reference's `torch.quantization.quantize_dynamic(dlrm, {torch.nn.Linear}, qint8 | float16)` of --quantize-mlp-with-bit 8 | 16
+        (dlrm_s_pytorch.py:1473-1480) on the device: both towers become inference towers (FusedMLP.quantize).  Any other `bits` returns
+        without change, as the reference does for 32.  Every refusal comes before anything is modified."""
+        if bits not in (8, 16):
+            return
+        if self.quantize_mlp_bits != 32:
+            sys.exit("ERROR: the MLP towers are quantized already (%d bits)" % self.quantize_mlp_bits)
+        if self._has_md(self.emb_l):
+            sys.exit("ERROR: quantized MLP towers with mixed dimensions are not supported (quantize_dynamic would also quantize the "
+                     "tables' projections, which is not built)")
+        if ext_dist.is_distributed():
+            sys.exit("ERROR: quantized MLP towers are single-process inference only (distributed quantized inference is not built)")
+        towers = (self.bot_l, self.top_l)
+        if any(not isinstance(t, FusedMLP) for t in towers):
+            sys.exit("ERROR: quantized MLP towers are single-process inference only (a DistributedDataParallel-wrapped tower cannot be "
+                     "quantized)")
+        if any(t.quant_bits != 32 for t in towers):
+            sys.exit("ERROR: the MLP towers are quantized already")
+        if any(not p.is_cuda for t in towers for p in t.parameters()):
+            raise RuntimeError("dlrm_amd: quantize_mlp packs the towers on the GPU and the quantized layers have no CPU path; "
+                               "move the model to the device first (model.to('cuda'))")
+        for t in towers:
+            t._layers()                                               # (a tower that is not Linear + activation raises here)
+        self._join_side_stream()
+        for t in towers:
+            t.quantize(bits)
+        self.quantize_mlp_bits = bits
+
+    # (the towers refuse these themselves; asked here first, so that no table has been moved or loaded before the refusal)
+    def _apply(self, fn, *args, **kwargs):
+        if self.quantize_mlp_bits != 32:
+            sys.exit("ERROR: a model with quantized MLP towers (%d bits) cannot be moved or converted (.to / .cuda / .cpu / .half): the "
+                     "towers' packed weights live on the device they were packed on" % self.quantize_mlp_bits)
+        return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        if self.quantize_mlp_bits != 32:
+            sys.exit("ERROR: load_state_dict into a model with quantized MLP towers (%d bits): quantized towers are constants (inference "
+                     "only) — load the fp32 weights first, then quantize_mlp" % self.quantize_mlp_bits)
+        return super().load_state_dict(*args, **kwargs)
+
+    def _refuse_step_if_mlp_quantized(self, optimizer) -> None:
+        mine = {id(p) for t in (self.bot_l, self.top_l) for p in t.parameters()}
+        if any(id(p) in mine for g in optimizer.param_groups for p in g["params"]):
+            sys.exit("ERROR: this optimizer holds the parameters of MLP towers that are quantized now (%d bits); quantized towers are "
+                     "constants (inference only)" % self.quantize_mlp_bits)
 
     def _refuse_step_if_quantized(self, optimizer) -> None:
         if not self.quantize_emb:

@@ -103,6 +103,8 @@ class GraphedTrainStep:
                                "(RCCL all-to-all / DDP all-reduce are not captured)")
         if getattr(model, "quantize_emb", False):
             sys.exit("ERROR: GraphedTrainStep captures a training step; a model with quantized embedding tables is inference only")
+        if getattr(model, "quantize_mlp_bits", 32) != 32:
+            sys.exit("ERROR: GraphedTrainStep captures a training step; a model with quantized MLP towers is inference only")
         if getattr(model, "_has_qr", None) is not None and model._has_qr(getattr(model, "emb_l", None)):
             sys.exit("ERROR: GraphedTrainStep is not built for QR embedding tables (their backward allocates the split index arrays per step)")
         if getattr(model, "_has_md", None) is not None and model._has_md(getattr(model, "emb_l", None)):

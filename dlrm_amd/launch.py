@@ -36,6 +36,29 @@ def _stub_tensorboard_if_missing() -> None:
     sys.modules["torch.utils.tensorboard"] = tb
 
 
+def _wrap_quantize_dynamic() -> None:
+    """--quantize-mlp-with-bit 8 | 16: run() calls `torch.quantization.quantize_dynamic(dlrm, {torch.nn.Linear}, qint8 | float16)`
+    (dlrm_s_pytorch.py:1473-1480), which would swap the towers' layers for torch's CPU-only modules.  A dlrm_amd.DLRM_Net is answered with
+    its own quantize_mlp (the same model comes back); everything else goes to torch's function unchanged.  Wrapped once."""
+    import torch
+    import dlrm_amd
+
+    q = torch.quantization
+    inner = q.quantize_dynamic
+    if getattr(inner, "_dlrm_amd_wrapped", False):
+        return
+
+    def quantize_dynamic(model, qconfig_spec=None, dtype=torch.qint8, *args, **kwargs):
+        if isinstance(model, dlrm_amd.DLRM_Net):
+            model.quantize_mlp(8 if dtype is torch.qint8 else 16)
+            return model
+        return inner(model, qconfig_spec, dtype, *args, **kwargs)
+
+    quantize_dynamic._dlrm_amd_wrapped = True
+    quantize_dynamic._dlrm_amd_inner = inner
+    q.quantize_dynamic = quantize_dynamic
+
+
 def load_reference(reference_dir: str, device_tables: bool = False):
     """Import the reference's dlrm_s_pytorch with DLRM_Net / ext_dist replaced; returns the module."""
     import dlrm_amd
@@ -53,6 +76,7 @@ def load_reference(reference_dir: str, device_tables: bool = False):
     ref = importlib.import_module("dlrm_s_pytorch")
     ref.DLRM_Net = dlrm_amd.DLRM_Net
     ref.ext_dist = ext_dist
+    _wrap_quantize_dynamic()
     if device_tables:
         import torch
         dev = torch.device("cuda", max(int(os.environ.get("LOCAL_RANK", "0")), 0))

@@ -1096,6 +1096,91 @@ def linear_fwd(X: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], a
     return Y
 
 
+# ---- dynamically quantised int8 layers for inference: csrc/gemm_q8.hip (the reference's --quantize-mlp-with-bit 8)
+Q8_RANGE, Q8_QUANTIZE = 1, 2
+
+
+def q8_k64(K: int) -> int:
+    """reduction length of the int8 operands: K padded with zero codes to a multiple of 64"""
+    return (int(K) + 63) & ~63
+
+
+class Q8Weight:
+    """a Linear weight packed by q8_pack_weight: `codes` int8 [N, q8_k64(K)], `scale` device float[2] = {s_w, 1 / s_w}"""
+    __slots__ = ("codes", "scale", "N", "K")
+
+    def __init__(self, codes, scale, N, K):
+        self.codes, self.scale, self.N, self.K = codes, scale, int(N), int(K)
+
+
+def q8_pack_weight(W: torch.Tensor) -> Q8Weight:
+    """torch's per-tensor symmetric qint8 weight of a dynamic quantised Linear (scale and int_repr() exactly), packed on the device"""
+    _req(W, "W", ndim=2)
+    N, K = W.shape
+    if N < 1 or K < 1:
+        raise RuntimeError("dlrm_amd: q8_pack_weight needs a non-empty [N, K] weight")
+    codes = torch.empty((N, q8_k64(K)), dtype=torch.int8, device=W.device)
+    scale = torch.empty(2, dtype=torch.float32, device=W.device)
+    with _timed("q8_pack_weight"):
+        rc = _lib.load().dlrm_q8_pack_weight(N, K, C.c_void_p(W.data_ptr()), _ld(W), C.c_void_p(codes.data_ptr()),
+                                             C.c_void_p(scale.data_ptr()), _stream(W))
+    _lib.check(rc, "dlrm_q8_pack_weight")
+    return Q8Weight(codes, scale, N, K)
+
+
+def q8_quantize_act(X: torch.Tensor, K: Optional[int] = None, phases: int = Q8_RANGE | Q8_QUANTIZE, bufs=None):
+    """(codes int8 [M, q8_k64(K)], qparams device float[4] = {s_x, zero point, 1 / s_x, 0}) of the dynamic per-tensor quantisation of
+    X[:, :K] (K defaults to X's width; columns from K on are padding and never read).  The parameters stay on the device.
+    `bufs` = (codes, qparams, workspace) of an earlier call reuses them (the measurement tool's phase split)."""
+    _req(X, "X", ndim=2)
+    M = X.size(0)
+    K = X.size(1) if K is None else int(K)
+    if M < 1 or K < 1 or K > X.size(1):
+        raise RuntimeError(f"dlrm_amd: q8_quantize_act needs a non-empty input of at least K = {K} columns, got {tuple(X.shape)}")
+    lib = _lib.load()
+    nws = int(lib.dlrm_q8_workspace_bytes(M, K))
+    if bufs is None:
+        bufs = (torch.empty((M, q8_k64(K)), dtype=torch.int8, device=X.device), torch.empty(4, dtype=torch.float32, device=X.device),
+                torch.empty(nws // 4, dtype=torch.float32, device=X.device))
+    codes, qparams, ws = bufs
+    with _timed("q8_quantize_act"):
+        rc = lib.dlrm_q8_quantize_act(M, K, C.c_void_p(X.data_ptr()), _ld(X), C.c_void_p(codes.data_ptr()), C.c_void_p(qparams.data_ptr()),
+                                      C.c_void_p(ws.data_ptr()), nws, int(phases), _stream(X))
+    _lib.check(rc, "dlrm_q8_quantize_act")
+    return codes, qparams, ws
+
+
+def gemm_q8(codes: torch.Tensor, qparams: torch.Tensor, W: Q8Weight, bias: Optional[torch.Tensor], act: int, out: torch.Tensor) -> torch.Tensor:
+    """out = act(float(codes . W.codes^T) * (s_x * s_w) + bias) on the int8 MFMA; `out` is a [M, N] view with a free row stride"""
+    _req(codes, "codes", dtype=torch.int8, ndim=2); _req(out, "out", ndim=2); _req(qparams, "qparams", ndim=1)
+    M = codes.size(0)
+    if (not codes.is_contiguous() or codes.size(1) != W.codes.size(1) or out.size(0) != M or out.size(1) != W.N or qparams.numel() < 3
+            or M < 1):
+        raise RuntimeError(f"dlrm_amd: gemm_q8 shape mismatch codes{tuple(codes.shape)} W{tuple(W.codes.shape)} out{tuple(out.shape)}")
+    if bias is not None:
+        _req(bias, "bias", ndim=1)
+        if bias.numel() != W.N:
+            raise RuntimeError("dlrm_amd: gemm_q8 bias length mismatch")
+    with _timed("gemm_q8"):
+        rc = _lib.load().dlrm_gemm_q8(M, W.N, W.K, C.c_void_p(codes.data_ptr()), C.c_void_p(W.codes.data_ptr()),
+                                      C.c_void_p(qparams.data_ptr()), C.c_void_p(W.scale.data_ptr()),
+                                      C.c_void_p(bias.data_ptr()) if bias is not None else None, int(act), C.c_void_p(out.data_ptr()),
+                                      _ld(out), _stream(out))
+    _lib.check(rc, "dlrm_gemm_q8")
+    return out
+
+
+def linear_q8(X: torch.Tensor, W: Q8Weight, bias: Optional[torch.Tensor], act: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch's dynamic int8 Linear (+ activation) of X: quantise the input per tensor, int8 GEMM, dequantise + bias.  X may carry zero
+    padding columns beyond W.K (the interaction's 480-wide output for K = 479): they are not read."""
+    if X.dim() != 2 or X.size(1) < W.K or X.size(1) > ((W.K + 3) & ~3):
+        raise RuntimeError("dlrm_amd: linear_q8 input width %s does not match the layer (%d)" % (tuple(X.shape), W.K))
+    codes, qparams, _ = q8_quantize_act(X, W.K)
+    if out is None:
+        out = torch.empty((X.size(0), W.N), dtype=torch.float32, device=X.device)
+    return gemm_q8(codes, qparams, W, bias, act, out)
+
+
 def linear_bwd_data(dY: torch.Tensor, W: torch.Tensor, Xact: Optional[torch.Tensor], xact_kind: int,
                     dX: torch.Tensor, arith=_lib.ARITH_F32, relu_bits: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dX = (dY @ W) * act'(Xact)   (Xact None -> no mask; relu_bits = the sign bits linear_fwd stored for Xact)"""

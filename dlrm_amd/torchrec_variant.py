@@ -35,11 +35,16 @@ def _no_quantized_tables(self, bits):
     sys.exit("ERROR: quantized embedding tables are built for DLRM_Net only, not for the torchrec variants (%s)" % type(self).__name__)
 
 
+def _no_quantized_towers(self, bits):
+    sys.exit("ERROR: quantized MLP towers are built for DLRM_Net only, not for the torchrec variants (%s)" % type(self).__name__)
+
+
 class DLRM(DLRM_Net):
     """torchrec.models.dlrm.DLRM(embedding_bag_collection, dense_in_features, dense_arch_layer_sizes, over_arch_layer_sizes):
     the embedding bag collection is given by its table sizes and the embedding dimension."""
 
     quantize_embedding = _no_quantized_tables
+    quantize_mlp = _no_quantized_towers
     _qr_supported = False
     _md_supported = False
 
@@ -94,6 +99,7 @@ class ShardedDLRM(DLRM_Net):
     batch; DDP averages only the dense parameters)."""
 
     quantize_embedding = _no_quantized_tables
+    quantize_mlp = _no_quantized_towers
     _qr_supported = False
     _md_supported = False
 
@@ -236,6 +242,7 @@ class DLRM_DCN(DLRM_Net):
     through a DCN-v2 low-rank cross network; the over-arch takes its [B, F*D] output and ends with a bare Linear (logits)."""
 
     quantize_embedding = _no_quantized_tables
+    quantize_mlp = _no_quantized_towers
     _qr_supported = False
     _md_supported = False
 

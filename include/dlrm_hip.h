@@ -673,6 +673,34 @@ int dlrm_add(int64_t n, const float* a, const float* b, float* out, void* stream
 int dlrm_clamp(int64_t n, const float* x, float lo, float hi, float* y, void* stream);
 int dlrm_clamp_bwd(int64_t n, const float* x, float lo, float hi, const float* dy, float* dx, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Dynamically quantised int8 Linear layers for inference (csrc/gemm_q8.hip; symbols added, the ABI version stays 17).
+ * Replaces: torch.quantization.quantize_dynamic(dlrm, {nn.Linear}, torch.qint8) of --quantize-mlp-with-bit 8
+ *           (dlrm_s_pytorch.py:1473-1480), which swaps every tower layer for torch's CPU-only dynamic quantised Linear.
+ * K64 = K rounded up to a multiple of 64; int8 operands are row-major [rows, K64], zero codes in the padding, 16-byte aligned.
+ * dlrm_q8_pack_weight: per tensor, symmetric: s_w[0] = max(max|W| / 127.5, 2^-23), s_w[1] = 1 / s_w[0],
+ *   wq[n, k] = clamp(rint(W[n, k] * s_w[1]), -128, 127) — scale and codes of torch's packed weight exactly.
+ *   W : device float* [N, K] (row stride ldw);  wq : device int8* [N, K64];  s_w : device float[2]
+ * dlrm_q8_quantize_act: per call, per tensor over the whole [M, K] input (row stride ldx >= K; columns >= K are never read), codes 0..127
+ *   (the module's reduce_range): mn = min(min x, 0), mx = max(max x, 0), s = (double(mx) - mn) / 127 (0.1 when float(s) is 0 or its
+ *   reciprocal infinite), zero point zp as fbgemm's ChooseQuantizationParams, s_x = float(s), inv = 1 / s_x,
+ *   code = clamp(rint(x * inv) + zp, 0, 127); xq holds the SHIFTED codes (code - zp, in [-127, 127]); qparams = {s_x, zp, inv, 0}.
+ *   Nothing returns to the host.  phases: DLRM_Q8_RANGE (partial min / max into the workspace), DLRM_Q8_QUANTIZE (parameters from the
+ *   workspace's partials + codes), or both (the normal call); the split exists for measurements.
+ *   workspace : device, dlrm_q8_workspace_bytes(M, K) bytes, 4-byte aligned;  xq : device int8* [M, K64];  qparams : device float[4]
+ * dlrm_gemm_q8: out[m, n] = act(float(sum_k xq[m, k] wq[n, k]) * (s_x * s_w) + bias[n]): exact int32 accumulation on
+ *   v_mfma_i32_32x32x32_i8 (N <= 8: 4-way int8 dot products), then one fp32 product of the scales, one multiply, one add, none
+ *   contracted — the same bits whatever the tiling.  bias may be NULL (no add); act is DLRM_ACT_*; out has row stride ld_out >= N and
+ *   needs no alignment.  Any M, N, K >= 1. */
+#define DLRM_Q8_RANGE 1
+#define DLRM_Q8_QUANTIZE 2
+int dlrm_q8_pack_weight(int N, int K, const float* W, int64_t ldw, void* wq, float* s_w, void* stream);
+int64_t dlrm_q8_workspace_bytes(int64_t M, int K);
+int dlrm_q8_quantize_act(int64_t M, int K, const float* X, int64_t ldx, void* xq, float* qparams, void* workspace,
+                         int64_t workspace_bytes, int phases, void* stream);
+int dlrm_gemm_q8(int64_t M, int N, int K, const void* xq, const void* wq, const float* qparams, const float* s_w, const float* bias,
+                 int act, float* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
