@@ -43,6 +43,9 @@ SIGNATURES = {
     "dlrm_emb_fwd": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
     "dlrm_emb_quantize_rows": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp]),
     "dlrm_emb_fwd_quant": (_i32, [_i32, _i64, _i32, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_fwd_quant_pred": (_i32, [_i32, _i64, _i32, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dlrm_interact_gather_quant_ok": (_i32, [_i32, _i32, _i32]),
+    "dlrm_interact_fwd_gather_quant": (_i32, [_i64, _i32, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dlrm_emb_fwd_qr": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _pi64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
     "dlrm_emb_qr_bwd_split": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "dlrm_emb_qr_split_indices": (_i32, [_i32, _pi64, C.POINTER(_i32), _pp, _pi64, _i32, _pp, _pp, _vp]),

@@ -155,6 +155,7 @@ __device__ __forceinline__ void q_accum(float (&acc)[8], float w, const QRow<4>&
 
 template <int BITS, int LPB, typename IT, int U>
 __global__ __launch_bounds__(256) void emb_fwd_quant_kernel(EmbArgs a, long long B, int D, float* __restrict__ out, long long out_ld) {
+    if (a.pred.skip()) return;      // (dlrm_emb_fwd_quant_pred: the fused lookup + interaction kernel runs instead)
     const int t = blockIdx.y;
     const uint8_t* __restrict__ W = (const uint8_t*)a.w[t];
     const IT* __restrict__ idx = (const IT*)a.idx[t];
@@ -268,6 +269,7 @@ __device__ __forceinline__ unsigned load_le(const uint8_t* __restrict__ p, int n
 
 template <int BITS, typename IT>
 __global__ __launch_bounds__(256) void emb_fwd_quant_bytes_kernel(EmbArgs a, long long B, int D, float* __restrict__ out, long long out_ld) {
+    if (a.pred.skip()) return;
     const int t = blockIdx.y;
     const uint8_t* __restrict__ W = (const uint8_t*)a.w[t];
     const IT* __restrict__ idx = (const IT*)a.idx[t];
@@ -352,9 +354,30 @@ extern "C" int dlrm_emb_quantize_rows(int64_t rows, int D, int bits, const float
     return 0;
 }
 
+static int emb_fwd_quant_impl(int T, int64_t B, int D, int bits, const void* const* weight_host, const int64_t* rows_host,
+                              const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                              const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, DlrmPred pred, void* stream);
+
 extern "C" int dlrm_emb_fwd_quant(int T, int64_t B, int D, int bits, const void* const* weight_host, const int64_t* rows_host,
                                   const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
                                   const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, void* stream) {
+    return emb_fwd_quant_impl(T, B, D, bits, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, idx_bits, out, out_ld, err,
+                              DlrmPred{nullptr, 0}, stream);
+}
+
+// the same kernels behind a launch predicate (as dlrm_emb_fwd_pred beside dlrm_emb_fwd): the two-kernel form of a quantised forward whose
+// fused form (dlrm_interact_fwd_gather_quant) was enqueued with the opposite predicate
+extern "C" int dlrm_emb_fwd_quant_pred(int T, int64_t B, int D, int bits, const void* const* weight_host, const int64_t* rows_host,
+                                       const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                                       const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err,
+                                       const int32_t* pred_flag, int pred_nonzero, void* stream) {
+    return emb_fwd_quant_impl(T, B, D, bits, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, idx_bits, out, out_ld, err,
+                              DlrmPred{(const int*)pred_flag, pred_nonzero}, stream);
+}
+
+static int emb_fwd_quant_impl(int T, int64_t B, int D, int bits, const void* const* weight_host, const int64_t* rows_host,
+                              const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                              const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, DlrmPred pred, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0) return DLRM_E_ARG;
     if (!weight_host || !rows_host || !indices_host || !offsets_host || !nnz_host) return DLRM_E_ARG;
     if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
@@ -379,7 +402,7 @@ extern "C" int dlrm_emb_fwd_quant(int T, int64_t B, int D, int bits, const void*
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
         EmbArgs a;
         a.err = (long long*)err;
-        a.pred.flag = nullptr; a.pred.nonzero = 0;
+        a.pred = pred;
         for (int k = 0; k < DLRM_MAX_TABLES_PER_LAUNCH; ++k) {
             const int t = t0 + (k < n ? k : 0);
             a.w[k] = (float*)weight_host[t];         // (packed bytes; the kernels read them as uint8_t)

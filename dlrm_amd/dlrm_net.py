@@ -37,6 +37,12 @@ from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
 DEVICE_PREDICATE = os.environ.get("DLRM_DEVICE_PREDICATE", "1") != "0"
 from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, BagBatch
 
+# Default of DLRM_Net.fuse_quant_interact.  Rule: True only if the fused quantised forward kernel is faster than dlrm_emb_fwd_quant +
+# dlrm_interact_fwd at Criteo-Terabyte shapes at BOTH 4 and 8 bits, measured in one process (tools/bench_quant_interact.py;
+# profiles/quant_emb/fused_interact_rates.md holds the table that decided it).
+# Measured: 0.239 ms fused / 0.513 ms two kernels at 8 bits, 0.247 / 0.498 ms at 4 bits.
+FUSE_QUANT_INTERACT_DEFAULT = True
+
 
 _EMB_INIT_DEVICE = None
 
@@ -416,6 +422,11 @@ class DLRM_Net(nn.Module):
         # a ragged batch with nnz == B — an empty bag next to a two-lookup bag — takes the two kernels like every other multi-hot
         # input).  The kernels still verify the bag starts themselves and report a violation through the index-error block.
         self.fuse_emb_interact = os.environ.get("DLRM_FUSE_EMB_INTERACT", "1") == "1"
+        # The same for a model whose tables are QUANTISED (quantize_embedding): one forward kernel fetches the packed rows, dequantises them
+        # into its LDS image and multiplies (dlrm_interact_fwd_gather_quant) — the bits of dlrm_emb_fwd_quant + dlrm_interact_fwd without the
+        # [B, T*D] fp32 buffer between them.  Taken under the conditions of fuse_emb_interact (which must be set too), when no gradient is
+        # wanted from the forward.  Default: FUSE_QUANT_INTERACT_DEFAULT at the top of this file, decided by measurement.
+        self.fuse_quant_interact = FUSE_QUANT_INTERACT_DEFAULT
         # True (or env DLRM_UPDATE_IN_BACKWARD=1; opt-in): once the model knows its plain-SGD optimizer (from that optimizer's first step), the
         # fused backward takes the SGD step of every embedding row that ONE lookup of the batch names — the row is staged in the interaction
         # kernel's LDS and its gradient is in registers, so the table row is written at once and neither the gradient row nor a second read of
@@ -887,10 +898,13 @@ class DLRM_Net(nn.Module):
         # the last ReLU of the bottom tower is differentiated inside the interaction backward (which has x staged): see _relu_x
         rx = self._relu_x() if dense_x.is_cuda else 0
         if self.quantize_emb:
-            # the two-kernel form only: the fused lookup + interaction kernels fetch fp32 rows.  The bottom tower writes its
-            # slot of the feature buffer, dlrm_emb_fwd_quant the rest; interaction and top tower as below.
+            # the fused form where it applies (_quant_fused_forward), else the two-kernel form: the bottom tower writes its slot of the feature
+            # buffer, dlrm_emb_fwd_quant the rest; interaction and top tower as below.
             if self.update_in_backward:
                 sys.exit("ERROR: update_in_backward trains the embedding tables; quantized tables are constants (inference only)")
+            z = self._quant_fused_forward(dense_x, lS_o, lS_i, B, T, D)
+            if z is not None:
+                return self._clamp(self.apply_mlp(z, self.top_l))
             feat = torch.empty((B, n_out + T * D), dtype=torch.float32, device=dense_x.device)
             x = self.apply_mlp(dense_x, self.bot_l, out_slot=OutSlot(feat[:, :n_out]), consumer_applies_last_act=bool(rx))
             E = self._emb_quant_into(lS_o, lS_i, self.v_W_l, feat[:, n_out:])
@@ -951,6 +965,36 @@ class DLRM_Net(nn.Module):
         else:
             z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)   # [B, round4(width)], zero padded
         return self._clamp(self.apply_mlp(z, self.top_l))
+
+    def _quant_fused_forward(self, dense_x, lS_o, lS_i, B, T, D):
+        """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run:
+        `cat`, multi-hot bags, pooling weights, D != 128, a forward that wants gradients (the fused kernel is forward only), or
+        fuse_quant_interact / fuse_emb_interact off.  The offsets' one-lookup-per-bag state decides as in the fp32 branch of
+        sequential_forward: True / None -> the fused kernel alone; a device flag -> the fused kernel behind (flag, 0) and
+        dlrm_emb_fwd_quant + dlrm_interact_fwd behind (flag, 1), no host wait; False -> None.  No autograd node: the tables are constants."""
+        bits = self.quantize_bits
+        if not (self.fuse_emb_interact and self.fuse_quant_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
+                and ops.gather_quant_ok(1 + T, D, bits) and not any(w is not None for w in (self.v_W_l or []))):
+            return None
+        if torch.is_grad_enabled() and (dense_x.requires_grad or (getattr(self.bot_l, "quant_bits", 32) == 32
+                                                                  and any(p_.requires_grad for p_ in self.bot_l.parameters()))):
+            return None          # (a forward whose bottom tower is being trained: InteractFunction carries the gradient of x)
+        bags = self._bags(lS_o, lS_i, None)
+        if not (all(n == B for n in bags.nnz) and ops.quant_tables_aligned(self.emb_l_q, bits)):
+            return None
+        state = ops.offsets_iota_state(lS_o)
+        if state is False:
+            return None
+        x = _functional._rowmajor(self.apply_mlp(dense_x, self.bot_l))
+        mode = self._interaction_mode()
+        R = torch.empty((B, _functional._round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
+        if not isinstance(state, torch.Tensor):
+            return ops.interact_fwd_gather_quant(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R)
+        ops.interact_fwd_gather_quant(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R, pred=(state, 0))
+        ly = _functional.alloc2d(B, T * D, x)
+        ops.emb_fwd_quant(self.emb_l_q, self.emb_q_rows, D, bits, bags, ly, pred=(state, 1))
+        ops.interact_fwd((x, ly), D, mode, R, pred=(state, 1))
+        return R
 
     def distributed_forward(self, dense_x, lS_o, lS_i):
         """Table-wise sharded embeddings + batch-split MLPs (dlrm_s_pytorch.py:528-585): every rank pools

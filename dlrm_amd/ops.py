@@ -379,26 +379,37 @@ def emb_quantize(weight: torch.Tensor, bits: int) -> torch.Tensor:
     return out
 
 
-def emb_fwd_quant(qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, bags: BagBatch, out: torch.Tensor) -> torch.Tensor:
-    """emb_fwd over packed tables (emb_quantize): out[b, t*D:(t+1)*D] = sum_i psw_i * (scale_r * q_r + bias_r).  qweights[t] is the
-    uint8 [rows[t], quant_row_bytes(D, bits)] tensor of table t; `out` is a [B, >= T*D] view (row stride free)."""
-    lib = _lib.load()
+def _packed_tables_desc(qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, T: int, what: str):
     rb = quant_row_bytes(D, bits)
-    if len(qweights) != bags.T or len(rows) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_fwd_quant needs one packed table and one row count per table")
+    if len(qweights) != T or len(rows) != T:
+        raise RuntimeError("dlrm_amd: %s needs one packed table and one row count per table" % what)
     for q, n in zip(qweights, rows):
         _req(q, "packed embedding table", dtype=torch.uint8, ndim=2)
         if not q.is_contiguous() or q.size(0) != int(n) or q.size(1) != rb:
             raise RuntimeError("dlrm_amd: a packed %d-bit table of %d rows and dimension %d is a contiguous uint8 [%d, %d] tensor, got %s"
                                % (bits, n, D, n, rb, tuple(q.shape)))
+    return _lib.ptr_array([q.data_ptr() for q in qweights]), _lib.i64_array(rows)
+
+
+def emb_fwd_quant(qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, bags: BagBatch, out: torch.Tensor,
+                  pred=None) -> torch.Tensor:
+    """emb_fwd over packed tables (emb_quantize): out[b, t*D:(t+1)*D] = sum_i psw_i * (scale_r * q_r + bias_r).  qweights[t] is the
+    uint8 [rows[t], quant_row_bytes(D, bits)] tensor of table t; `out` is a [B, >= T*D] view (row stride free).  pred: see _pred_args."""
+    lib = _lib.load()
+    wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "emb_fwd_quant")
     _req(out, "out", ndim=2)
     if out.size(0) != bags.B or out.size(1) < bags.T * D:
         raise RuntimeError("dlrm_amd: emb_fwd_quant shape mismatch")
     err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
-    with _timed("emb_fwd_quant"):
-        rc = lib.dlrm_emb_fwd_quant(bags.T, bags.B, D, bits, _lib.ptr_array([q.data_ptr() for q in qweights]), _lib.i64_array(rows),
-                                    bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out),
-                                    err, _stream(out))
+    st = _stream(out)
+    # (a predicated launch belongs to the forward's fused lookup + interaction, as in emb_fwd: one timing category for the three launches)
+    with _timed("emb_fwd_quant" if pred is None else "emb_interact_fwd_quant"):
+        if pred is None:
+            rc = lib.dlrm_emb_fwd_quant(bags.T, bags.B, D, bits, wp, rp, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
+                                        C.c_void_p(out.data_ptr()), _ld(out), err, st)
+        else:
+            rc = lib.dlrm_emb_fwd_quant_pred(bags.T, bags.B, D, bits, wp, rp, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
+                                             C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_emb_fwd_quant")
     return out
 
@@ -986,6 +997,41 @@ def interact_fwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
                                             C.c_void_p(R.data_ptr()), _ld(R), C.c_void_p(_err_block(R.device).data_ptr()),
                                             *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_interact_fwd_gather")
+    return R
+
+
+def gather_quant_ok(F: int, D: int, bits: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_quant_ok(int(F), int(D), int(bits)))
+
+
+def quant_tables_aligned(qweights: Sequence[torch.Tensor], bits: int) -> bool:
+    """what interact_fwd_gather_quant needs of the packed tables: a lane's codes are one 8-byte (8 bits) / 4-byte (4 bits) load"""
+    return all(q.data_ptr() % (8 if bits == 8 else 4) == 0 for q in qweights)
+
+
+def interact_fwd_gather_quant(x: torch.Tensor, qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, bags: BagBatch,
+                              self_interaction, R: torch.Tensor, pred=None) -> torch.Tensor:
+    """R = interaction of [x | one-hot rows of the packed tables], the rows fetched and dequantised by the kernel itself
+    (dlrm_interact_fwd_gather_quant): the bits of emb_fwd_quant into a feature buffer + interact_fwd, without that buffer.  Forward only."""
+    lib = _lib.load()
+    # validated as _gather_desc does: one lookup per bag, no per-sample weights
+    if bags.T != len(qweights) or any(n != bags.B for n in bags.nnz):
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
+    if bags._psw is not None:
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+    wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "interact_fwd_gather_quant")
+    _req(x, "x", ndim=2)
+    _req(R, "R", ndim=2)
+    F = 1 + bags.T
+    if x.size(1) != D or R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+        raise RuntimeError("dlrm_amd: interact_fwd_gather_quant shape mismatch")
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_fwd_quant"):
+        rc = lib.dlrm_interact_fwd_gather_quant(bags.B, F, D, bits, C.c_void_p(x.data_ptr()), _ld(x), wp, rp, bags._idx, bags._off,
+                                                bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
+                                                C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_fwd_gather_quant")
     return R
 
 

@@ -117,6 +117,35 @@ int dlrm_emb_fwd_quant(int T, int64_t B, int D, int bits,
                        const void* const* indices_host, const void* const* offsets_host,
                        const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
                        float* out, int64_t out_ld, int64_t* err, void* stream);
+/* dlrm_emb_fwd_quant behind a launch predicate (see dlrm_*_pred below): the same kernels, whose workgroups return at once unless
+ * (*pred_flag != 0) == (pred_nonzero != 0); pred_flag == NULL: always run.  (Symbol added, the ABI version stays 17.) */
+int dlrm_emb_fwd_quant_pred(int T, int64_t B, int D, int bits,
+                            const void* const* weight_host, const int64_t* rows_host,
+                            const void* const* indices_host, const void* const* offsets_host,
+                            const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                            float* out, int64_t out_ld, int64_t* err,
+                            const int32_t* pred_flag, int pred_nonzero, void* stream);
+
+/* Fused lookup + interaction FORWARD over quantised tables (csrc/interact_quant.hip; symbols added, the ABI version stays 17).
+ * Replaces: the quantised branch of apply_emb + interact_features ("dot") for one-lookup-per-bag batches (dlrm_s_pytorch.py:430-450, 483-504).
+ * Feature 0 is the fp32 block x ([B, D], row stride x_ld); feature f = 1 .. F-1 is row index_host[f-1][b] of the packed table
+ * qweight_host[f-1] (rows_host[f-1] rows in dlrm_emb_quantize_rows' format), fetched and dequantised by the interaction kernel itself: the
+ * [B, (F-1)*D] pooled buffer of the two-kernel form is neither written nor read.  R, ldr, self_interaction: exactly dlrm_interact_fwd
+ * (mode word 0 / 1 / 2, zero-filled padding columns up to ldr).  R is BIT-IDENTICAL to dlrm_emb_fwd_quant (psw_host = NULL) into a feature
+ * buffer + dlrm_interact_fwd: element = fmaf(1, fmaf(scale, q, bias), +0), dot products in the interaction kernels' summation order.
+ *   offsets_host[t] : verified on the device to be 0, 1, 2, ... — a violation is reported through `err` with rows = -1, as dlrm_interact_fwd_gather;
+ *   an index outside [0, rows) is reported ({1, table, index, rows}) and contributes a ZERO row, as dlrm_emb_fwd_quant (not row 0);
+ *   pred_flag / pred_nonzero : launch predicate as dlrm_*_pred (NULL: always run).
+ * dlrm_interact_gather_quant_ok (host only): 1 for D = 128, bits in {4, 8} and every F dlrm_interact_gather_ok(F, 128) accepts, else 0.
+ * Returns DLRM_E_MODE for shapes that function refuses, a table base not aligned to 8 (8 bits) / 4 (4 bits) bytes, an x or R not aligned
+ * to 16 bytes, x_ld or ldr not a multiple of 4; DLRM_E_RANGE for a table of more than 0xFFFFFFFF rows; DLRM_E_ARG for null operands,
+ * rows <= 0, ldr < D + pairs. */
+int dlrm_interact_gather_quant_ok(int F, int D, int bits);
+int dlrm_interact_fwd_gather_quant(int64_t B, int F, int D, int bits, const float* x, int64_t x_ld,
+                                   const void* const* qweight_host, const int64_t* rows_host,
+                                   const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                   int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                   const int32_t* pred_flag, int pred_nonzero, void* stream);
 
 /* Quotient-remainder (QR, compositional) embedding tables: csrc/emb_qr.hip.
  * Replaces: tricks/qr_embedding_bag.py (QREmbeddingBag.forward and its autograd), built by DLRM_Net.create_emb for every table with more than
