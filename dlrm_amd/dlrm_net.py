@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
-                         EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
+                         BF16EmbeddingBagsFunction, EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
                          MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
@@ -53,6 +53,31 @@ def set_embedding_init(device=None) -> None:
     directly in that device's memory (needed for the 96 GB Criteo-Terabyte tables)."""
     global _EMB_INIT_DEVICE
     _EMB_INIT_DEVICE = device
+
+
+_EMB_DTYPE = None           # None: fp32 tables; (torch.bfloat16, rounding, seed): set_embedding_dtype
+
+
+def set_embedding_dtype(dtype=None, rounding: str = "stochastic", seed: int = 0) -> None:
+    """None / torch.float32 (default): fp32 tables.  torch.bfloat16: every DLRM_Net built from here on creates its tables in bfloat16
+    (DLRM_Net.embedding_bfloat16 applied at construction: each table is drawn in fp32 and converted before the next one is drawn, so the
+    peak is the bf16 tables plus one fp32 table) with the given update rounding ("stochastic" | "nearest") and seed."""
+    global _EMB_DTYPE
+    if dtype is None or dtype == torch.float32:
+        _EMB_DTYPE = None
+        return
+    if dtype != torch.bfloat16:
+        sys.exit("ERROR: embedding tables are float32 or bfloat16, got " + str(dtype))
+    if rounding not in ops.BF16_ROUNDINGS:
+        sys.exit("ERROR: bfloat16 embedding tables round 'stochastic' or 'nearest', got " + repr(rounding))
+    _EMB_DTYPE = (torch.bfloat16, rounding, int(seed))
+
+
+def _mix_seed(seed: int, call_no: int, stream_id: int = 0) -> int:
+    """distinct Philox keys per (model seed, update call): the mix of datagen.UniformBatchGenerator._seed"""
+    z = (seed * 0x9E3779B97F4A7C15 + call_no * 0xBF58476D1CE4E5B9 + stream_id * 0x94D049BB133111EB) & (2 ** 64 - 1)
+    z ^= z >> 31
+    return z & (2 ** 64 - 1)
 
 
 class FusedMLP(nn.Sequential):
@@ -306,6 +331,8 @@ class DLRM_Net(nn.Module):
     # that sets the qr_* attributes itself (ShardedDLRM calls create_emb directly)
     _qr_supported = True
     _md_supported = True        # (the same for mixed-dimension tables)
+    _bf16_supported = True      # (the same for bfloat16 tables: embedding_bfloat16 / set_embedding_dtype)
+    emb_bf16 = None             # (rounding, seed) once the tables are bfloat16
     quantize_mlp_bits = 32      # 8 / 16 after quantize_mlp()
 
     # ---------------------------------------------------------------- parameter construction
@@ -331,6 +358,10 @@ class DLRM_Net(nn.Module):
         parity); lookups go through the batched HIP kernel, not through the holders' forward."""
         tables = nn.ModuleList()
         pool_w = []
+        if _EMB_DTYPE is not None:
+            # tables created in bfloat16 (set_embedding_dtype): every refusal before a table is built
+            self._refuse_bf16(weighted_pooling == "learned" or (weighted_pooling is not None and weighted_pooling != "fixed"),
+                              bool(getattr(self, "qr_flag", False)), bool(getattr(self, "md_flag", False)))
         # --md-flag with per-table widths (dlrm_s_pytorch.py:1213-1219 turns m_spa into md_solver's list): every refusal before a table is built
         md = bool(getattr(self, "md_flag", False)) and not np.isscalar(m) and np.ndim(m) == 1
         m_plain, base = m, None
@@ -392,6 +423,8 @@ class DLRM_Net(nn.Module):
                 # benchmark-scale tables (tens of GB) cannot go through a float64 numpy temporary on the
                 # host: same distribution, drawn on the device (see set_embedding_init)
                 w = torch.empty((n, m_plain), dtype=torch.float32, device=_EMB_INIT_DEVICE).uniform_(-bound, bound)
+            if _EMB_DTYPE is not None:
+                w = w.to(torch.bfloat16)                 # round-to-nearest; the fp32 draw is released before the next table is drawn
             holder = nn.EmbeddingBag(n, m_plain, mode="sum", sparse=True, _weight=w)
             pool_w.append(None if weighted_pooling is None else torch.ones(n, dtype=torch.float32))
             tables.append(holder)
@@ -480,6 +513,9 @@ class DLRM_Net(nn.Module):
             # (run() checks the scalar before md_solver replaces it, dlrm_s_pytorch.py:1197-1219; the smallest table keeps it: base = max(m))
             sys.exit("ERROR: arch-sparse-feature-size " + str(int(max(m_spa))) + " does not match last dim of bottom mlp " + str(int(ln_bot[-1])))
         self.emb_l, pool_w = self.create_emb(m_spa, ln_emb, weighted_pooling)
+        if _EMB_DTYPE is not None:
+            self.emb_bf16 = (_EMB_DTYPE[1], _EMB_DTYPE[2])
+            self._bf16_update_calls = 0
         if self.weighted_pooling == "learned":
             # dlrm_s_pytorch.py:370-375: the per-row pooling weights become parameters (state_dict keys v_W_l.{k})
             self.v_W_l = nn.ParameterList([nn.Parameter(w) for w in pool_w])
@@ -611,6 +647,11 @@ class DLRM_Net(nn.Module):
             projs = [e.proj_weight() if isinstance(e, PrEmbeddingBagHolder) else None for e in emb_l]
             spec = (self._md_base(emb_l), [p is not None for p in projs], torch.is_grad_enabled())
             return MDEmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, spec, *ws, *[p for p in projs if p is not None])
+        if self.emb_bf16 is not None:
+            if isinstance(v_W_l, nn.ParameterList) or any(isinstance(w, nn.Parameter) for w in (v_W_l or []) if w is not None):
+                sys.exit("ERROR: bfloat16 embedding tables with learned pooling weights are not supported (the pooling-weight gradient "
+                         "kernel reads fp32 rows); use --weighted-pooling=fixed")
+            return BF16EmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, *ws, *self._pool_weights(v_W_l, ws[0].device))
         return EmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, *ws, *self._pool_weights(v_W_l, ws[0].device))
 
     def apply_emb(self, lS_o, lS_i, emb_l, v_W_l):
@@ -654,6 +695,8 @@ class DLRM_Net(nn.Module):
         plus one packed table).  From here on the model is an inference model: its lookups go through dlrm_emb_fwd_quant."""
         if bits not in (4, 8):
             return
+        if self.emb_bf16 is not None:
+            sys.exit("ERROR: 4 and 8-bit quantization with bfloat16 embedding tables is not supported (quantize the fp32 model)")
         if self._has_qr(self.emb_l):
             sys.exit("ERROR: 4 and 8-bit quantization with quotient remainder is not supported")
         if self._has_md(self.emb_l):
@@ -684,6 +727,61 @@ class DLRM_Net(nn.Module):
         self.emb_l = None
         self.quantize_emb = True
         self.quantize_bits = bits
+
+    def _refuse_bf16(self, learned_pooling: bool, has_qr: bool, has_md: bool) -> None:
+        """every configuration bfloat16 tables are not built for, refused before anything is modified"""
+        if not self._bf16_supported:
+            sys.exit("ERROR: bfloat16 embedding tables are built for DLRM_Net only, not for the torchrec variants (%s)" % type(self).__name__)
+        if has_qr:
+            sys.exit("ERROR: bfloat16 embedding tables with quotient remainder are not supported")
+        if has_md:
+            sys.exit("ERROR: bfloat16 embedding tables with mixed dimensions are not supported")
+        if learned_pooling:
+            sys.exit("ERROR: bfloat16 embedding tables with learned pooling weights are not supported (the pooling-weight gradient "
+                     "kernel reads fp32 rows); use --weighted-pooling=fixed")
+        if not self.fused_emb_update:
+            sys.exit("ERROR: bfloat16 embedding tables need the fused embedding update (fused_emb_update = False materialises sparse "
+                     "fp32 COO gradients for a torch optimizer, which would round on every add)")
+        if ext_dist.is_distributed():
+            sys.exit("ERROR: bfloat16 embedding tables are single-process only (the table-sharded distributed forward is not built for them)")
+
+    def embedding_bfloat16(self, rounding: str = "stochastic", seed: int = 0) -> None:
+        """Store every embedding table in bfloat16 (half the table bytes, half the row traffic of the HBM-bound lookup and update kernels).
+        Tables are converted in place, one by one, round-to-nearest (`p.data = p.data.to(torch.bfloat16)`: the Parameter objects stay, an
+        optimizer built earlier still owns them; peak memory = the fp32 tables plus one bf16 table); state_dict keys are unchanged, its
+        table entries are bfloat16, and loading an fp32 checkpoint casts.
+        Forward: dlrm_emb_fwd_bf16 + the interaction kernel — the bits of the fp32 model on the upcast tables (the fused lookup +
+        interaction kernels fetch fp32 rows and are not entered; update_in_backward falls back to the step-time update).
+        Update (plain SGD or row-wise Adagrad, when the optimizer steps): the gradient of a row is summed in fp32, the row is stepped in
+        fp32 and rounded ONCE per update call — rounding = "stochastic" (default; Philox keyed by (seed, number of update calls so far), so a
+        run is reproducible) or "nearest".  Gradient accumulation with SGD applies each parked backward pass in turn: one rounding per
+        pass, not one per optimizer step."""
+        if rounding not in ops.BF16_ROUNDINGS:
+            sys.exit("ERROR: bfloat16 embedding tables round 'stochastic' or 'nearest', got " + repr(rounding))
+        if self.emb_bf16 is not None:
+            sys.exit("ERROR: the embedding tables are bfloat16 already")
+        if getattr(self, "quantize_emb", False):
+            sys.exit("ERROR: the embedding tables are quantized (%d bits); bfloat16 tables are built from the fp32 model" % self.quantize_bits)
+        self._refuse_bf16(isinstance(self.v_W_l, nn.ParameterList), self._has_qr(self.emb_l), self._has_md(self.emb_l))
+        if self._pending_emb:
+            sys.exit("ERROR: an embedding update is still parked (backward without optimizer.step()); step or drop it before embedding_bfloat16")
+        self._join_side_stream()
+        for e in self.emb_l:
+            e.weight.data = e.weight.data.to(torch.bfloat16)             # one table at a time: its fp32 rows are released here
+        self.emb_bf16 = (rounding, int(seed))
+        self._bf16_update_calls = 0
+
+    def _bf16_next_seed(self) -> int:
+        n = self._bf16_update_calls
+        self._bf16_update_calls = n + 1
+        return _mix_seed(self.emb_bf16[1], n)
+
+    def _sgd_update(self, weights, bags, dout, lr) -> None:
+        """the fused backward + SGD step of one parked backward pass: the fp32 kernels, or the bf16 ones for bfloat16 tables"""
+        if self.emb_bf16 is not None:
+            ops.emb_bwd_sgd_bf16(weights, bags, dout, lr, self.emb_bf16[0], self._bf16_next_seed())
+        else:
+            ops.emb_bwd_sgd(weights, bags, dout, lr, self.emb_update_mode)
 
     def quantize_mlp(self, bits):
         """The reference's `torch.quantization.quantize_dynamic(dlrm, {torch.nn.Linear}, qint8 | float16)` of --quantize-mlp-with-bit 8 | 16
@@ -783,6 +881,9 @@ class DLRM_Net(nn.Module):
             self._pending_emb.append((weights, bags, dout, presorted))
             return
         if not self.fused_emb_update:
+            if self.emb_bf16 is not None:
+                sys.exit("ERROR: bfloat16 embedding tables need the fused embedding update (fused_emb_update = False materialises sparse "
+                         "fp32 COO gradients for a torch optimizer, which would round on every add)")
             self._materialize_coo_grads(weights, bags, dout)
             return
         opt = self._bound_optimizer() if (self.overlap_streams and self._bound_optimizer is not None) else None
@@ -798,7 +899,7 @@ class DLRM_Net(nn.Module):
                     ops.timer_mark()
                     side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    ops.emb_bwd_sgd(weights, bags, dout, plan[1], self.emb_update_mode)
+                    self._sgd_update(weights, bags, dout, plan[1])
                 self._side_keep += [dout] + bags.keep
                 return
         self._pending_emb.append((weights, bags, dout, None))
@@ -848,7 +949,7 @@ class DLRM_Net(nn.Module):
                 ops.emb_bwd_sgd_presorted(weights, bags, dout, pre)
                 continue
             if lr is not None:
-                ops.emb_bwd_sgd(weights, bags, dout, lr, self.emb_update_mode)
+                self._sgd_update(weights, bags, dout, lr)
                 continue
             # parked backward passes over THESE tables (`weights` is a fresh tuple per forward call: compare the tables themselves)
             key = tuple(id(w) for w in weights)
@@ -856,9 +957,12 @@ class DLRM_Net(nn.Module):
             if plan is None:
                 self._pending_emb.append((weights, bags, dout, None))   # another optimizer owns these tables
             elif plan[0] == "coo":
+                if self.emb_bf16 is not None:
+                    sys.exit("ERROR: bfloat16 embedding tables are updated by the fused kernels only: plain SGD (no momentum, no weight "
+                             "decay) or row-wise Adagrad; this optimizer needs the sparse COO gradient")
                 self._materialize_coo_grads(weights, bags, dout)  # the optimizer's own step consumes .grad right after this hook
             elif plan[0] == "sgd":
-                ops.emb_bwd_sgd(weights, bags, dout, plan[1], self.emb_update_mode)
+                self._sgd_update(weights, bags, dout, plan[1])
             else:
                 if self._has_qr(self.emb_l):
                     sys.exit("ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
@@ -867,7 +971,10 @@ class DLRM_Net(nn.Module):
                     sys.exit("ERROR: the fused row-wise Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
                              "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
                 _, clr, eps, states = plan
-                ops.emb_bwd_rowwise_adagrad(weights, states, bags, dout, clr, eps)
+                if self.emb_bf16 is not None:
+                    ops.emb_bwd_rowwise_adagrad_bf16(weights, states, bags, dout, clr, eps, self.emb_bf16[0], self._bf16_next_seed())
+                else:
+                    ops.emb_bwd_rowwise_adagrad(weights, states, bags, dout, clr, eps)
 
     # ---------------------------------------------------------------- forward paths
     def forward(self, dense_x, lS_o, lS_i):
@@ -916,7 +1023,8 @@ class DLRM_Net(nn.Module):
         # (a model with a QR or a mixed-dimension table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it the
         # step-time update, update_in_backward included)
         if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and ops.gather_ok(1 + T, D)
-                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l) and not any(w is not None for w in (self.v_W_l or []))):
+                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l) and self.emb_bf16 is None
+                and not any(w is not None for w in (self.v_W_l or []))):
             bags = self._bags(lS_o, lS_i, None)
             # nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the
             # reference computes it): ops.offsets_are_iota (dlrm_amd/iota.py) proves offsets == arange(B) on the device, once per offsets tensor
@@ -1002,6 +1110,8 @@ class DLRM_Net(nn.Module):
         MLP runs while the exchange is in flight."""
         if self.quantize_emb:
             sys.exit("ERROR: quantized embedding tables are single-process inference only (distributed quantized inference is not built)")
+        if self.emb_bf16 is not None:
+            sys.exit("ERROR: bfloat16 embedding tables are single-process only (the table-sharded distributed forward is not built for them)")
         if self._has_qr(self.emb_l):
             sys.exit("ERROR: QR embedding tables are single-process only (the table-sharded distributed forward is not built for them)")
         if self._has_md(self.emb_l):

@@ -550,6 +550,37 @@ class EmbeddingBagsFunction(Function):
         return (None, None, None) + (None,) * len(ctx.weights) + dvw
 
 
+class BF16EmbeddingBagsFunction(Function):
+    """EmbeddingBagsFunction over torch.bfloat16 tables (DLRM_Net.embedding_bfloat16): one dlrm_emb_fwd_bf16 launch pools every table into
+    the fp32 feature buffer — the bits of EmbeddingBagsFunction on the tables upcast to fp32.  Backward hands (weights, bags, d_out) to the
+    same `sink`; the model routes them to the bf16 update kernels when the optimizer steps.  Pooling weights: fixed vectors only (the
+    gradient kernel of learned ones reads fp32 rows; the model refuses them before it gets here)."""
+
+    @staticmethod
+    def forward(ctx, sink, bags, out_slot, *tensors):
+        T = bags.T
+        weights, vws = tensors[:T], tensors[T:]
+        D = weights[0].size(1)
+        if vws:
+            if any(v.requires_grad for v in vws):
+                raise RuntimeError("dlrm_amd: learned pooling weights are not built for bfloat16 embedding tables")
+            ops.pool_weights_gather(vws, bags)
+        out = out_slot.get() if out_slot is not None else alloc2d(bags.B, T * D, weights[0])        # (fp32, on the tables' device)
+        ops.emb_fwd_bf16(weights, bags, out)
+        ctx.sink = sink
+        ctx.bags = bags
+        ctx.weights = weights  # parameters (leaves) — kept by reference, not via save_for_backward
+        ctx.n_vws = len(vws)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.sink is None:
+            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+        ctx.sink(ctx.weights, ctx.bags, _rowmajor(dout))
+        return (None, None, None) + (None,) * (len(ctx.weights) + ctx.n_vws)
+
+
 class QREmbeddingBagsFunction(Function):
     """EmbeddingBagsFunction for a table list with quotient-remainder tables (tricks/qr_embedding_bag.py; dlrm_s_pytorch.py:258-266): one
     dlrm_emb_fwd_qr launch pools every table, QR or plain.  spec = (rows, collisions, operation, keep_sums); `vweights` is the VIRTUAL table

@@ -109,6 +109,8 @@ class GraphedTrainStep:
             sys.exit("ERROR: GraphedTrainStep is not built for QR embedding tables (their backward allocates the split index arrays per step)")
         if getattr(model, "_has_md", None) is not None and model._has_md(getattr(model, "emb_l", None)):
             sys.exit("ERROR: GraphedTrainStep is not built for mixed-dimension embedding tables (their backward builds the per-width bag lists per step)")
+        if getattr(model, "emb_bf16", None) is not None:
+            sys.exit("ERROR: GraphedTrainStep is not built for bfloat16 embedding tables (the per-step rounding seed would be baked into the capture)")
         self.model, self.optimizer = model, optimizer
         for g in optimizer.param_groups:
             # a decaying step size (RWSAdagrad: clr = lr / (1 + (step - 1) * lr_decay)) is computed on the host at capture time

@@ -84,20 +84,32 @@ def load_reference(reference_dir: str, device_tables: bool = False):
     return ref
 
 
-def main(argv=None) -> None:
-    argv = list(sys.argv[1:] if argv is None else argv)
-    ref_args = []
-    if "--" in argv:
-        i = argv.index("--")
-        argv, ref_args = argv[:i], argv[i + 1:]
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m dlrm_amd.launch")
     ap.add_argument("--reference", default=os.environ.get("DLRM_REFERENCE", "."),
                     help="checkout of facebookresearch/dlrm (directory holding dlrm_s_pytorch.py)")
     ap.add_argument("--device-tables", action="store_true",
                     help="allocate + initialise embedding tables directly in HBM (needed for Criteo-Terabyte sizes: the "
                          "reference's numpy float64 temporary does not fit host RAM); same distribution, torch RNG")
-    a = ap.parse_args(argv)
+    ap.add_argument("--bf16-tables", choices=("stochastic", "nearest"), default=None,
+                    help="store the embedding tables in bfloat16 (dlrm_amd.set_embedding_dtype): half the table bytes; the fused sparse "
+                         "update rounds each touched row once per step, stochastically (reproducible: --bf16-seed) or to nearest")
+    ap.add_argument("--bf16-seed", type=int, default=0, help="seed of the stochastic rounding of --bf16-tables")
+    return ap
+
+
+def main(argv=None) -> None:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    ref_args = []
+    if "--" in argv:
+        i = argv.index("--")
+        argv, ref_args = argv[:i], argv[i + 1:]
+    a = build_parser().parse_args(argv)
     ref = load_reference(os.path.abspath(a.reference), a.device_tables)
+    if a.bf16_tables is not None:
+        import torch
+        import dlrm_amd
+        dlrm_amd.set_embedding_dtype(torch.bfloat16, a.bf16_tables, a.bf16_seed)
     sys.argv = [os.path.join(a.reference, "dlrm_s_pytorch.py")] + ref_args
     ref.run()
 

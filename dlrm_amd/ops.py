@@ -874,6 +874,100 @@ def emb_bwd_rowwise_adagrad(weights: Sequence[torch.Tensor], states: Sequence[to
     _lib.check(rc, "dlrm_emb_bwd_rowwise_adagrad")
 
 
+# ---- bfloat16 embedding tables: csrc/emb_bf16.hip.  Tables are torch.bfloat16 [rows, D]; the feature buffer, the gradient, the Adagrad
+# accumulators and every sum stay fp32.  An update rounds each touched row ONCE: "nearest" (even) or "stochastic" (Philox4x32-10 keyed by
+# `seed`: the same seed gives the same bits; the host restatement is tests/test_bf16_emb_host.py).
+BF16_ROUNDINGS = {"nearest": 0, "stochastic": 1}
+
+
+def _bf16_rounding(rounding) -> int:
+    if rounding not in BF16_ROUNDINGS:
+        raise RuntimeError("dlrm_amd: bf16 table rounding is 'nearest' or 'stochastic', got %r" % (rounding,))
+    return BF16_ROUNDINGS[rounding]
+
+
+def _bf16_weights_desc(weights: Sequence[torch.Tensor]):
+    D = None
+    for w in weights:
+        _req(w, "bf16 embedding weight", dtype=torch.bfloat16, ndim=2)
+        if not w.is_contiguous():
+            raise RuntimeError("dlrm_amd: embedding tables must be contiguous [rows, D]")
+        if D is None:
+            D = w.size(1)
+        elif D != w.size(1):
+            raise RuntimeError("dlrm_amd: all embedding tables must share one embedding dimension")
+    return int(D), _lib.ptr_array([w.data_ptr() for w in weights]), _lib.i64_array([w.size(0) for w in weights])
+
+
+def emb_fwd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor) -> torch.Tensor:
+    """emb_fwd over torch.bfloat16 tables: out[b, t*D:(t+1)*D] = sum-pooled bag (t, b) in fp32, bit-identical to emb_fwd on the tables
+    upcast to fp32.  `out` is an fp32 [B, >= T*D] view (row stride free)."""
+    lib = _lib.load()
+    D, wp, rows = _bf16_weights_desc(weights)
+    _req(out, "out", ndim=2)
+    if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_fwd_bf16 shape mismatch")
+    err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
+    with _timed("emb_fwd_bf16"):
+        rc = lib.dlrm_emb_fwd_bf16(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
+                                   bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, _stream(out))
+    _lib.check(rc, "dlrm_emb_fwd_bf16")
+    return out
+
+
+def _bf16_update_ws(lib, bags: BagBatch, D: int, rows, device):
+    need = lib.dlrm_emb_bwd_bf16_workspace_bytes(bags.T, D, bags._nnz, rows)
+    if need < 0:
+        raise RuntimeError("dlrm_amd: dlrm_emb_bwd_bf16_workspace_bytes failed")
+    return _scratch("emb", need, device)
+
+
+def emb_bwd_sgd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor, lr: LrLike, rounding: str = "stochastic",
+                     seed: int = 0, table0: int = 0) -> None:
+    """Fused EmbeddingBag backward + sparse SGD over torch.bfloat16 tables, in place: per touched row r, g_r = the fp32 sum of its lookups'
+    gradients (sorted walk, deterministic), W[r] = round(fmaf(-lr, g_r, float(W[r]))) — one rounding per row per call.  table0: index of
+    weights[0] in the caller's full table list (the random stream of a table does not depend on how the list is cut into calls)."""
+    lib = _lib.load()
+    D, wp, rows = _bf16_weights_desc(weights)
+    _req(dout, "dout", ndim=2)
+    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_bwd_sgd_bf16 shape mismatch")
+    mode = _bf16_rounding(rounding)
+    ws = _bf16_update_ws(lib, bags, D, rows, dout.device)
+    lr_v, lr_p = _lr_args(lr)
+    with _timed("emb_bwd_sgd_bf16"):
+        rc = lib.dlrm_emb_bwd_sgd_bf16(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
+                                       C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, mode, int(seed) & (2 ** 64 - 1), int(table0),
+                                       C.c_void_p(ws.data_ptr()), ws.numel(),
+                                       None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
+    _lib.check(rc, "dlrm_emb_bwd_sgd_bf16")
+
+
+def emb_bwd_rowwise_adagrad_bf16(weights: Sequence[torch.Tensor], states: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor,
+                                 lr: LrLike, eps: float, rounding: str = "stochastic", seed: int = 0, table0: int = 0) -> None:
+    """emb_bwd_rowwise_adagrad over torch.bfloat16 tables, in place.  `states` stay fp32 and receive the bits emb_bwd_rowwise_adagrad gives
+    them on the upcast tables; W[r] = round(fmaf(-lr, g_r / (sqrt(states[t][r]) + eps), float(W[r]))), one rounding per row per call."""
+    lib = _lib.load()
+    D, wp, rows = _bf16_weights_desc(weights)
+    _req(dout, "dout", ndim=2)
+    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T or len(states) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_bwd_rowwise_adagrad_bf16 shape mismatch")
+    for s_, w in zip(states, weights):
+        _req(s_, "adagrad state", ndim=1)
+        if s_.numel() != w.size(0) or not s_.is_contiguous():
+            raise RuntimeError("dlrm_amd: row-wise adagrad state must be a contiguous [rows] tensor")
+    mode = _bf16_rounding(rounding)
+    sp = _lib.ptr_array([s_.data_ptr() for s_ in states])
+    ws = _bf16_update_ws(lib, bags, D, rows, dout.device)
+    lr_v, lr_p = _lr_args(lr)
+    with _timed("emb_bwd_adagrad_bf16"):
+        rc = lib.dlrm_emb_bwd_rowwise_adagrad_bf16(bags.T, bags.B, D, wp, sp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
+                                                   bags.idx_bits, C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, float(eps), mode,
+                                                   int(seed) & (2 ** 64 - 1), int(table0), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                   None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
+    _lib.check(rc, "dlrm_emb_bwd_rowwise_adagrad_bf16")
+
+
 def emb_bwd_coo(bags: BagBatch, dout: torch.Tensor, D: int) -> List[torch.Tensor]:
     """The reference's EmbeddingBag backward WITHOUT the fused update: per table the [nnz_t, D] value block of the sparse
     COO gradient (values[i] = psw[i] * dout[bag(i), t*D:(t+1)*D]; its indices are the lookup indices verbatim)."""

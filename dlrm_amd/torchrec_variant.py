@@ -47,6 +47,7 @@ class DLRM(DLRM_Net):
     quantize_mlp = _no_quantized_towers
     _qr_supported = False
     _md_supported = False
+    _bf16_supported = False
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
                  dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int]):
@@ -102,6 +103,7 @@ class ShardedDLRM(DLRM_Net):
     quantize_mlp = _no_quantized_towers
     _qr_supported = False
     _md_supported = False
+    _bf16_supported = False
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], multi_hot_sizes: Sequence[int], embedding_dim: int,
                  dense_in_features: int, dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int],
@@ -245,6 +247,7 @@ class DLRM_DCN(DLRM_Net):
     quantize_mlp = _no_quantized_towers
     _qr_supported = False
     _md_supported = False
+    _bf16_supported = False
 
     def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
                  dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int], dcn_num_layers: int,

@@ -277,6 +277,57 @@ int dlrm_emb_bwd_rowwise_adagrad(int T, int64_t B, int D,
                      const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
                      void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
 
+/* bfloat16 embedding tables: csrc/emb_bf16.hip (symbols added, the ABI version stays 17).
+ * Replaces: nothing in the reference — the 16-bit table storage of the torchrec / fbgemm path that BASELINE.json configs[4] restates.
+ * A table is weight_host[t] : device uint16* [rows_host[t], D] of bfloat16 bit patterns (torch.bfloat16), 2-byte aligned at least.
+ * dlrm_emb_fwd_bf16: dlrm_emb_fwd's operands and conventions (all tables in one launch, idx_bits, off_t[B] := nnz[t], psw_host, out / out_ld
+ *   into the fp32 feature buffer, empty bags give zeros, out-of-range ids skipped and reported through `err`).  The result is BIT-IDENTICAL
+ *   to dlrm_emb_fwd on the same tables upcast to fp32: a row element is widened by a 16-bit shift (exact) and accumulated in index order
+ *   per column, acc = fmaf(psw, v, acc) from +0.0 (psw = 1.0f when absent).  D % 8 == 0 (D <= 512) with 16-byte aligned tables and out
+ *   (out_ld % 4 == 0) takes the 16-bytes-per-lane kernel, everything else a 2-bytes-per-lane one that is correct, not fast.
+ * dlrm_emb_bwd_sgd_bf16 / dlrm_emb_bwd_rowwise_adagrad_bf16: the fused backward + update over bf16 rows; operands of
+ *   dlrm_emb_bwd_rowwise_adagrad (state_host, fp32 [rows], only for the Adagrad call; lr / lr_dev as in the fp32 calls) plus
+ *     rounding : 0 = round-to-nearest-even, 1 = stochastic (else DLRM_E_MODE);   seed : the Philox key of this call;
+ *     table0   : index of weight_host[0] in the caller's full table list (a caller that cuts its list into several calls passes the
+ *                offset, so that the random stream of a table does not depend on the cut); table0 + T <= 0x0FFFFFFF.
+ *   Per table, per UNIQUE row r touched (lookups sorted by (table, row) with the library's sorter, duplicates summed in fp32 in input
+ *   order, exactly as dlrm_emb_bwd_rowwise_adagrad sums them; no atomics on the table):
+ *     g_r = sum_i psw_i * dout[bag(i), :]
+ *     SGD     : v = fmaf(-lr, g_r, (float)W[r])
+ *     Adagrad : state[r] += mean_d(g_r[d]^2);  v = fmaf(-lr, g_r / (sqrtf(state[r]) + eps), (float)W[r])
+ *               — the arithmetic of dlrm_emb_bwd_rowwise_adagrad with the row widened on load: state[] gets that call's bits
+ *                 (every product and sum of mean_d(g^2) rounded separately, as that call's compiled D % 4 == 0 kernels do; the
+ *                 one-column-per-lane form chains fmaf(g, g, sum))
+ *     W[r]    = round(v), ONCE: each touched row is read once and written once; deterministic from run to run, independent of the
+ *               launch shape.
+ *   Nearest: IEEE round-to-nearest-even of the fp32 value.  Stochastic, finite v: stored = (bits(v) + u) >> 16, u = 16 bits of
+ *   Philox4x32-10 (a carry into the exponent gives the correct next value); Inf / NaN are truncated and a NaN stays a NaN (mantissa bit 6
+ *   set when truncation would leave none).  Element (table t = table0 + position in weight_host, row r, column c): block of counter
+ *   (r & 0xffffffff, r >> 32, c >> 3, 0xB0000000 | t), key = seed (low word, high word); word (c & 7) >> 1, low half for even c, high
+ *   half for odd c.  Out-of-range lookups are skipped and reported as in the fp32 calls.
+ *   workspace: device scratch of at least dlrm_emb_bwd_bf16_workspace_bytes(...) bytes, 16-byte aligned (both update calls).
+ *   D <= 1024 with D % 4 == 0, 8-byte aligned tables and a 16-byte aligned dout (dout_ld % 4 == 0); else D <= 256. */
+int dlrm_emb_fwd_bf16(int T, int64_t B, int D,
+                      const void* const* weight_host, const int64_t* rows_host,
+                      const void* const* indices_host, const void* const* offsets_host,
+                      const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                      float* out, int64_t out_ld, int64_t* err, void* stream);
+int64_t dlrm_emb_bwd_bf16_workspace_bytes(int T, int D, const int64_t* nnz_host, const int64_t* rows_host);
+int dlrm_emb_bwd_sgd_bf16(int T, int64_t B, int D,
+                          void* const* weight_host, const int64_t* rows_host,
+                          const void* const* indices_host, const void* const* offsets_host,
+                          const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                          const float* dout, int64_t dout_ld, float lr, const float* lr_dev,
+                          int rounding, uint64_t seed, int table0,
+                          void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
+int dlrm_emb_bwd_rowwise_adagrad_bf16(int T, int64_t B, int D,
+                          void* const* weight_host, void* const* state_host, const int64_t* rows_host,
+                          const void* const* indices_host, const void* const* offsets_host,
+                          const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                          const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
+                          int rounding, uint64_t seed, int table0,
+                          void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * K6  dot interaction forward.
  * Replaces: torch.cat + torch.bmm + Z[:, li, lj] + torch.cat in DLRM_Net.interact_features
