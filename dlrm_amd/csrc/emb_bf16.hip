@@ -40,6 +40,7 @@ __device__ __forceinline__ void fma8(float (&acc)[8], float w, const uint4& q) {
 // -------------------------------------------------------------------------------------------
 template <int LPB, typename IT, int U>
 __global__ __launch_bounds__(256) void emb_fwd_bf16_kernel(EmbArgs a, long long B, int D, float* __restrict__ out, long long out_ld) {
+    if (a.pred.skip()) return;          // dlrm_emb_fwd_bf16_pred (flag == nullptr: always run)
     const int t = blockIdx.y;
     const bf16_bits* __restrict__ W = (const bf16_bits*)a.w[t];
     const IT* __restrict__ idx = (const IT*)a.idx[t];
@@ -144,6 +145,7 @@ __global__ __launch_bounds__(256) void emb_fwd_bf16_kernel(EmbArgs a, long long 
 // forward, 2 bytes per lane: any D, any alignment.  One wavefront per bag, a lane walks its columns; correct, not fast.
 template <typename IT>
 __global__ __launch_bounds__(256) void emb_fwd_bf16_scalar_kernel(EmbArgs a, long long B, int D, float* __restrict__ out, long long out_ld) {
+    if (a.pred.skip()) return;
     const int t = blockIdx.y;
     const bf16_bits* __restrict__ W = (const bf16_bits*)a.w[t];
     const IT* __restrict__ idx = (const IT*)a.idx[t];
@@ -618,9 +620,9 @@ static int bwd_bf16_impl(const char* what, int T, int64_t B, int D, void* const*
 
 }  // namespace
 
-extern "C" int dlrm_emb_fwd_bf16(int T, int64_t B, int D, const void* const* weight_host, const int64_t* rows_host,
-                                 const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
-                                 const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, void* stream) {
+static int emb_fwd_bf16_impl(int T, int64_t B, int D, const void* const* weight_host, const int64_t* rows_host,
+                            const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                            const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, DlrmPred pred, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0) return DLRM_E_ARG;
     if (!weight_host || !rows_host || !indices_host || !offsets_host || !nnz_host) return DLRM_E_ARG;
     if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
@@ -640,7 +642,7 @@ extern "C" int dlrm_emb_fwd_bf16(int T, int64_t B, int D, const void* const* wei
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
         EmbArgs a;
-        a.err = (long long*)err; a.pred.flag = nullptr; a.pred.nonzero = 0;
+        a.err = (long long*)err; a.pred = pred;
         for (int k = 0; k < DLRM_MAX_TABLES_PER_LAUNCH; ++k) {
             const int t = t0 + (k < n ? k : 0);
             a.w[k] = (float*)weight_host[t]; a.idx[k] = indices_host[t]; a.off[k] = offsets_host[t];
@@ -671,6 +673,23 @@ extern "C" int dlrm_emb_fwd_bf16(int T, int64_t B, int D, const void* const* wei
         DLRM_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int dlrm_emb_fwd_bf16(int T, int64_t B, int D, const void* const* weight_host, const int64_t* rows_host,
+                                 const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                                 const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, void* stream) {
+    return emb_fwd_bf16_impl(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, idx_bits, out, out_ld, err,
+                             DlrmPred{nullptr, 0}, stream);
+}
+
+// dlrm_emb_fwd_bf16 behind a launch predicate (common.h DlrmPred): the same kernels, whose workgroups return at once unless
+// (*pred_flag != 0) == (pred_nonzero != 0)
+extern "C" int dlrm_emb_fwd_bf16_pred(int T, int64_t B, int D, const void* const* weight_host, const int64_t* rows_host,
+                                      const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                                      const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err,
+                                      const int32_t* pred_flag, int pred_nonzero, void* stream) {
+    return emb_fwd_bf16_impl(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, idx_bits, out, out_ld, err,
+                             DlrmPred{(const int*)pred_flag, pred_nonzero}, stream);
 }
 
 extern "C" int64_t dlrm_emb_bwd_bf16_workspace_bytes(int T, int D, const int64_t* nnz_host, const int64_t* rows_host) {

@@ -333,6 +333,10 @@ class DLRM_Net(nn.Module):
     _md_supported = True        # (the same for mixed-dimension tables)
     _bf16_supported = True      # (the same for bfloat16 tables: embedding_bfloat16 / set_embedding_dtype)
     emb_bf16 = None             # (rounding, seed) once the tables are bfloat16
+    # opt-in (launcher: --bf16-fuse-interact): a bfloat16 model enters the fused lookup + interaction branch of sequential_forward under the
+    # fp32 branch's conditions and runs csrc/interact_bf16.hip (forward and backward) instead of dlrm_emb_fwd_bf16 + the interaction kernels
+    # through the pooled [B, T*D] buffer — the same bits.  Off: a bfloat16 model runs exactly the two-kernel form.
+    fuse_bf16_interact = False
     quantize_mlp_bits = 32      # 8 / 16 after quantize_mlp()
 
     # ---------------------------------------------------------------- parameter construction
@@ -750,8 +754,9 @@ class DLRM_Net(nn.Module):
         Tables are converted in place, one by one, round-to-nearest (`p.data = p.data.to(torch.bfloat16)`: the Parameter objects stay, an
         optimizer built earlier still owns them; peak memory = the fp32 tables plus one bf16 table); state_dict keys are unchanged, its
         table entries are bfloat16, and loading an fp32 checkpoint casts.
-        Forward: dlrm_emb_fwd_bf16 + the interaction kernel — the bits of the fp32 model on the upcast tables (the fused lookup +
-        interaction kernels fetch fp32 rows and are not entered; update_in_backward falls back to the step-time update).
+        Forward: dlrm_emb_fwd_bf16 + the interaction kernel — the bits of the fp32 model on the upcast tables (the fp32 fused lookup +
+        interaction kernels are not entered; with fuse_bf16_interact = True the bf16 ones of csrc/interact_bf16.hip are, forward and
+        backward, for the same bits; update_in_backward falls back to the step-time update).
         Update (plain SGD or row-wise Adagrad, when the optimizer steps): the gradient of a row is summed in fp32, the row is stepped in
         fp32 and rounded ONCE per update call — rounding = "stochastic" (default; Philox keyed by (seed, number of update calls so far), so a
         run is reproducible) or "nearest".  Gradient accumulation with SGD applies each parked backward pass in turn: one rounding per
@@ -1022,8 +1027,12 @@ class DLRM_Net(nn.Module):
             return self._clamp(self.apply_mlp(z, self.top_l))
         # (a model with a QR or a mixed-dimension table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it the
         # step-time update, update_in_backward included)
-        if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and ops.gather_ok(1 + T, D)
-                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l) and self.emb_bf16 is None
+        # (a bfloat16 model enters only with fuse_bf16_interact set, and then runs the kernels of csrc/interact_bf16.hip: ops.interact_*_gather
+        # dispatch on the tables' dtype)
+        bf16_fused = self.emb_bf16 is not None and self.fuse_bf16_interact
+        if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
+                and (ops.gather_ok(1 + T, D) if self.emb_bf16 is None else (bf16_fused and ops.gather_bf16_ok(1 + T, D)))
+                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l)
                 and not any(w is not None for w in (self.v_W_l or []))):
             bags = self._bags(lS_o, lS_i, None)
             # nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the
@@ -1048,7 +1057,8 @@ class DLRM_Net(nn.Module):
                         state = ops.offsets_are_iota_finish(proof)
                     if state is not False:
                         bags.iota_flag = state if isinstance(state, torch.Tensor) else None
-                        bags.presort = self._presort_for_backward if self.update_in_backward else None
+                        # (bfloat16 tables: no update inside the backward — update_in_backward falls back to the step-time update)
+                        bags.presort = self._presort_for_backward if (self.update_in_backward and self.emb_bf16 is None) else None
                         z = GatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x,
                                                          *self._emb_weights(self.emb_l))
                         return self._clamp(self.apply_mlp(z, self.top_l))

@@ -731,7 +731,8 @@ class GatherInteractFunction(Function):
         else:
             ops.interact_fwd_gather(x, weights, bags, D, mode, R, pred=(flag, 0))
             ly = alloc2d(x.size(0), len(weights) * D, x)
-            ops.emb_fwd(weights, bags, ly, pred=(flag, 1))
+            # (bfloat16 tables: the fused call above dispatched on the dtype; so does the lookup of the two-kernel form)
+            (ops.emb_fwd_bf16 if weights[0].dtype == torch.bfloat16 else ops.emb_fwd)(weights, bags, ly, pred=(flag, 1))
             ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
         ctx.sink, ctx.bags, ctx.weights = sink, bags, weights
         ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)

@@ -95,6 +95,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="store the embedding tables in bfloat16 (dlrm_amd.set_embedding_dtype): half the table bytes; the fused sparse "
                          "update rounds each touched row once per step, stochastically (reproducible: --bf16-seed) or to nearest")
     ap.add_argument("--bf16-seed", type=int, default=0, help="seed of the stochastic rounding of --bf16-tables")
+    ap.add_argument("--bf16-fuse-interact", action="store_true",
+                    help="with --bf16-tables: fetch the bfloat16 rows inside the interaction kernels, forward and backward "
+                         "(DLRM_Net.fuse_bf16_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer)")
     return ap
 
 
@@ -110,6 +113,11 @@ def main(argv=None) -> None:
         import torch
         import dlrm_amd
         dlrm_amd.set_embedding_dtype(torch.bfloat16, a.bf16_tables, a.bf16_seed)
+    if a.bf16_fuse_interact:
+        if a.bf16_tables is None:
+            sys.exit("ERROR: --bf16-fuse-interact needs --bf16-tables")
+        import dlrm_amd
+        dlrm_amd.DLRM_Net.fuse_bf16_interact = True        # every model run() builds from here on
     sys.argv = [os.path.join(a.reference, "dlrm_s_pytorch.py")] + ref_args
     ref.run()
 

@@ -899,18 +899,24 @@ def _bf16_weights_desc(weights: Sequence[torch.Tensor]):
     return int(D), _lib.ptr_array([w.data_ptr() for w in weights]), _lib.i64_array([w.size(0) for w in weights])
 
 
-def emb_fwd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor) -> torch.Tensor:
+def emb_fwd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor, pred=None) -> torch.Tensor:
     """emb_fwd over torch.bfloat16 tables: out[b, t*D:(t+1)*D] = sum-pooled bag (t, b) in fp32, bit-identical to emb_fwd on the tables
-    upcast to fp32.  `out` is an fp32 [B, >= T*D] view (row stride free)."""
+    upcast to fp32.  `out` is an fp32 [B, >= T*D] view (row stride free).  pred: see _pred_args."""
     lib = _lib.load()
     D, wp, rows = _bf16_weights_desc(weights)
     _req(out, "out", ndim=2)
     if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
         raise RuntimeError("dlrm_amd: emb_fwd_bf16 shape mismatch")
     err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
-    with _timed("emb_fwd_bf16"):
-        rc = lib.dlrm_emb_fwd_bf16(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                   bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, _stream(out))
+    st = _stream(out)
+    # (a predicated launch belongs to the step's fused lookup + interaction: same timing category, as emb_fwd)
+    with _timed("emb_fwd_bf16" if pred is None else "emb_interact_fwd_bf16"):
+        if pred is None:
+            rc = lib.dlrm_emb_fwd_bf16(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
+                                       bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, st)
+        else:
+            rc = lib.dlrm_emb_fwd_bf16_pred(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
+                                            bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_emb_fwd_bf16")
     return out
 
@@ -1073,10 +1079,54 @@ def _gather_desc(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatc
     return F, _lib.ptr_array(ptrs), _lib.i64_array(lds), gidx, goff, rows
 
 
+def gather_bf16_ok(F: int, D: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_bf16_ok(int(F), int(D)))
+
+
+def bf16_tables_aligned(weights: Sequence[torch.Tensor]) -> bool:
+    """what the fused bf16 kernels need of the tables: a lane's 8 columns are one 16-byte load"""
+    return all(w.data_ptr() % 16 == 0 for w in weights)
+
+
+def _gather_tables_bf16(weights: Sequence[torch.Tensor], what: str) -> bool:
+    """True: every table is torch.bfloat16 (the calls of csrc/interact_bf16.hip); False: none is; a mixture is refused"""
+    n16 = sum(1 for w in weights if w.dtype == torch.bfloat16)
+    if n16 not in (0, len(weights)):
+        raise RuntimeError("dlrm_amd: %s takes tables of ONE dtype, all fp32 or all bfloat16" % what)
+    return n16 > 0
+
+
+def _gather_desc_bf16(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
+    """_gather_desc for bf16 tables: the same refusals; table t is feature t + 1"""
+    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
+    if bags._psw is not None:
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+    _req(x, "x", ndim=2)
+    Dw, wp, rows = _bf16_weights_desc(weights)
+    if Dw != D or x.size(1) != D or x.size(0) != bags.B:
+        raise RuntimeError("dlrm_amd: the fused bf16 embedding + interaction path: shape mismatch")
+    return 1 + bags.T, wp, rows
+
+
 def interact_fwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction: bool,
                         R: torch.Tensor, pred=None) -> torch.Tensor:
-    """R = interaction of [x | one-hot embedding rows], the rows fetched by the kernel itself (no pooled-embedding buffer)."""
+    """R = interaction of [x | one-hot embedding rows], the rows fetched by the kernel itself (no pooled-embedding buffer).
+    Tables all fp32, or all torch.bfloat16 (dlrm_interact_fwd_gather_bf16: the bits of emb_fwd_bf16 + interact_fwd)."""
     lib = _lib.load()
+    if _gather_tables_bf16(weights, "interact_fwd_gather"):
+        F, wp, rows = _gather_desc_bf16(x, weights, bags, D)
+        _req(R, "R", ndim=2)
+        if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+            raise RuntimeError("dlrm_amd: interact_fwd_gather shape mismatch")
+        st = _stream(R)
+        flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+        with _timed("emb_interact_fwd_bf16"):
+            rc = lib.dlrm_interact_fwd_gather_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
+                                                   bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
+                                                   C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+        _lib.check(rc, "dlrm_interact_fwd_gather_bf16")
+        return R
     F, p, ld, gidx, goff, rows = _gather_desc(x, weights, bags, D)
     _req(R, "R", ndim=2)
     if R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
@@ -1139,6 +1189,23 @@ def interact_bwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
     presorted (emb_presort): the sparse SGD step of the single lookups is taken here — their tables rows are UPDATED, their dE rows not
     written; emb_bwd_sgd_presorted applies the rest (dlrm_interact_bwd_gather_sgd, ABI 17)."""
     lib = _lib.load()
+    if _gather_tables_bf16(weights, "interact_bwd_gather"):
+        # bf16 tables (dlrm_interact_bwd_gather_bf16): the bits of interact_bwd over (x, the buffer emb_fwd_bf16 wrote)
+        if presorted is not None:
+            raise RuntimeError("dlrm_amd: interact_bwd_gather: the update inside the backward (presorted) exists for fp32 tables only")
+        F, wp, rows = _gather_desc_bf16(x, weights, bags, D)
+        _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
+        if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
+            raise RuntimeError("dlrm_amd: interact_bwd_gather shape mismatch")
+        st = _stream(dR)
+        flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+        with _timed("emb_interact_bwd_bf16"):
+            rc = lib.dlrm_interact_bwd_gather_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
+                                                   bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
+                                                   C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(dE.data_ptr()), _ld(dE),
+                                                   C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
+        _lib.check(rc, "dlrm_interact_bwd_gather_bf16")
+        return
     F, p, ld, gidx, goff, rows = _gather_desc(x, weights, bags, D)
     _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
     dptrs = [dx.data_ptr()] + [dE.data_ptr() + 4 * k * D for k in range(bags.T)]

@@ -312,6 +312,14 @@ int dlrm_emb_fwd_bf16(int T, int64_t B, int D,
                       const void* const* indices_host, const void* const* offsets_host,
                       const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
                       float* out, int64_t out_ld, int64_t* err, void* stream);
+/* dlrm_emb_fwd_bf16 behind a launch predicate (see dlrm_*_pred below): the same kernels, whose workgroups return at once unless
+ * (*pred_flag != 0) == (pred_nonzero != 0); pred_flag == NULL: always run.  (Symbol added, the ABI version stays 17.) */
+int dlrm_emb_fwd_bf16_pred(int T, int64_t B, int D,
+                           const void* const* weight_host, const int64_t* rows_host,
+                           const void* const* indices_host, const void* const* offsets_host,
+                           const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                           float* out, int64_t out_ld, int64_t* err,
+                           const int32_t* pred_flag, int pred_nonzero, void* stream);
 int64_t dlrm_emb_bwd_bf16_workspace_bytes(int T, int D, const int64_t* nnz_host, const int64_t* rows_host);
 int dlrm_emb_bwd_sgd_bf16(int T, int64_t B, int D,
                           void* const* weight_host, const int64_t* rows_host,
@@ -327,6 +335,40 @@ int dlrm_emb_bwd_rowwise_adagrad_bf16(int T, int64_t B, int D,
                           const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
                           int rounding, uint64_t seed, int table0,
                           void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
+
+/* Fused lookup + interaction over bfloat16 tables, FORWARD and BACKWARD (csrc/interact_bf16.hip; symbols added, the ABI version stays 17).
+ * Replaces, for one-lookup-per-bag batches without per-sample weights: dlrm_emb_fwd_bf16 + dlrm_interact_fwd, and dlrm_interact_bwd over the
+ * pooled buffer.  Feature 0 is the fp32 block x ([B, D], row stride x_ld); feature f = 1 .. F-1 is row index_host[f-1][b] of the bf16 table
+ * weight_host[f-1] (rows_host[f-1] rows of D bfloat16, 16-byte aligned), fetched and widened by the interaction kernel itself: the
+ * [B, (F-1)*D] pooled fp32 buffer of the two-kernel form is neither written nor read.  D = 128 only.
+ *   forward : R, ldr, self_interaction exactly dlrm_interact_fwd (mode word 0 / 1 / 2, R[:, :D] = x, zero-filled padding columns up to ldr).
+ *             R is BIT-IDENTICAL to dlrm_emb_fwd_bf16 (psw_host = NULL) into a feature buffer + dlrm_interact_fwd; for in-range ids
+ *             therefore also to dlrm_interact_fwd_gather on the tables upcast to fp32.
+ *   backward: dR, ldr, self_interaction (| DLRM_INTERACT_RELU_X) exactly dlrm_interact_bwd; writes dx [B, D] (row stride dx_ld) and
+ *             dE [B, (F-1)*D] (row stride dE_ld; table t at columns t*D.., fp32 — the dout of dlrm_emb_bwd_sgd_bf16 /
+ *             dlrm_emb_bwd_rowwise_adagrad_bf16).  dx, dE are BIT-IDENTICAL to dlrm_interact_bwd over (x, the buffer dlrm_emb_fwd_bf16
+ *             wrote); for in-range ids therefore also to dlrm_interact_bwd_gather on the upcast tables.  The gradient row of an
+ *             out-of-range lookup is written like any other (the update skips it).
+ *   element = fmaf(1.0f, upcast(bits), +0.0f), as dlrm_emb_fwd_bf16 produces it for a bag of one row (-0.0 becomes +0.0);
+ *   offsets_host[t] : verified on the device to be 0, 1, 2, ... — a violation is reported through `err` with rows = -1;
+ *   an index outside [0, rows) is reported ({1, table, index, rows}) and contributes a ZERO row, as dlrm_emb_fwd_bf16 (not row 0, which
+ *   the fp32 fused kernels read);   pred_flag / pred_nonzero : launch predicate as dlrm_*_pred (NULL: always run).
+ * dlrm_interact_gather_bf16_ok (host only): D == 128 && dlrm_interact_gather_ok(F, D).
+ * Returns DLRM_E_MODE for shapes that function refuses, a table not aligned to 16 bytes, an x / R / dR / dx / dE not aligned to 16 bytes
+ * or a leading dimension that is not a multiple of 4, a dR row that does not fit its image (ldr * 4 >= 2048); DLRM_E_RANGE for a table
+ * of more than 0xFFFFFFFF rows; DLRM_E_ARG for null operands, rows <= 0, leading dimensions smaller than their rows. */
+int dlrm_interact_gather_bf16_ok(int F, int D);
+int dlrm_interact_fwd_gather_bf16(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                  const void* const* weight_host, const int64_t* rows_host,
+                                  const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                  int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                  const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_interact_bwd_gather_bf16(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                  const void* const* weight_host, const int64_t* rows_host,
+                                  const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                  int self_interaction, const float* dR, int64_t ldr,
+                                  float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
+                                  const int32_t* pred_flag, int pred_nonzero, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * K6  dot interaction forward.
