@@ -80,6 +80,14 @@ SIGNATURES = {
     "dlrm_interact_fwd_gather_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dlrm_interact_bwd_gather_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64,
                                              _vp, _vp, _i32, _vp]),
+    "dlrm_interact_gather_qr_ok": (_i32, [_i32, _i32]),
+    "dlrm_interact_fwd_gather_qr": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _i32, _i32, _vp, _i64,
+                                           _vp, _vp, _i32, _vp]),
+    "dlrm_interact_bwd_gather_qr": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _i32, _i32, _vp, _i64,
+                                           _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dlrm_emb_fwd_qr_pred": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _pi64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                    _vp, _i32, _vp]),
+    "dlrm_emb_qr_bwd_split_pred": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _vp]),
     "dlrm_emb_bwd_bf16_workspace_bytes": (_i64, [_i32, _i32, _pi64, _pi64]),
     "dlrm_emb_bwd_sgd_bf16": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64,
                                      _f32, _vp, _i32, C.c_uint64, _i32, _vp, _i64, _vp, _vp]),

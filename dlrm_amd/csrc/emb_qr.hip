@@ -21,6 +21,7 @@
 // c = 4, D = 128): every workgroup reads the same few lines, which stay in the vector L1 / L2 — it is not staged in LDS.
 // A table with collisions == 0 is a plain table: one sum, no composition, the bits dlrm_emb_fwd gives.
 #include "common.h"
+#include "qr_split.h"
 
 namespace {
 
@@ -30,15 +31,6 @@ struct QrArgs {
     int          qslot[DLRM_MAX_TABLES_PER_LAUNCH];  // position among the QR tables of the call: its sums go to saved[:, 2*qslot*D .. +2D)
     long long    rows_q[DLRM_MAX_TABLES_PER_LAUNCH]; // ceil(n / c) (plain: rows)
 };
-
-// the reference's index split.  false: the lookup names no row (skipped and reported by the caller)
-__device__ __forceinline__ bool qr_split(long long id, long long n, int c, long long rows_q, long long* q, long long* r) {
-    if (!dlrm_index_ok(id, n)) return false;
-    const long long qq = (long long)__fdiv_rn((float)id, (float)c);
-    if (!dlrm_index_ok(qq, rows_q)) return false;
-    *q = qq; *r = id % c;
-    return true;
-}
 
 __device__ __forceinline__ void f4_add(float4& a, const float4& v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
 __device__ __forceinline__ float4 f4_mul(const float4& a, const float4& b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
@@ -51,6 +43,7 @@ template <int LPB, int NCH, typename IT, int U>
 __global__ __launch_bounds__(256) void emb_fwd_qr_kernel(EmbArgs a, QrArgs qa, long long B, int D, int op_add,
                                                          float* __restrict__ out, long long out_ld,
                                                          float* __restrict__ saved, long long saved_ld) {
+    if (a.pred.skip()) return;          // dlrm_emb_fwd_qr_pred (flag == nullptr: always run)
     const int t = blockIdx.y;
     const float* __restrict__ Wq = a.w[t];
     const float* __restrict__ Wr = qa.wr[t];
@@ -183,6 +176,7 @@ template <typename IT>
 __global__ __launch_bounds__(256) void emb_fwd_qr_scalar_kernel(EmbArgs a, QrArgs qa, long long B, int D, int op_add,
                                                                 float* __restrict__ out, long long out_ld,
                                                                 float* __restrict__ saved, long long saved_ld) {
+    if (a.pred.skip()) return;
     const int t = blockIdx.y;
     const float* __restrict__ Wq = a.w[t];
     const float* __restrict__ Wr = qa.wr[t];
@@ -221,6 +215,7 @@ struct SplitArgs {
     int vslot[DLRM_MAX_TABLES_PER_LAUNCH];           // virtual slot of the table (of its q component)
     int qslot[DLRM_MAX_TABLES_PER_LAUNCH];           // position among the QR tables, -1: plain table
     int slot[DLRM_MAX_TABLES_PER_LAUNCH];            // column block of the table in dout
+    DlrmPred pred;                                   // launch predicate (dlrm_emb_qr_bwd_split_pred); flag == nullptr: always run
 };
 
 template <typename VT> struct SplitOps;
@@ -232,6 +227,7 @@ __global__ __launch_bounds__(256) void emb_qr_bwd_split_kernel(SplitArgs sa, lon
                                                                const VT* __restrict__ dout, long long dout_ld,
                                                                const VT* __restrict__ saved, long long saved_ld,
                                                                VT* __restrict__ gout, long long gout_ld) {
+    if (sa.pred.skip()) return;
     const int t = blockIdx.y;
     const int vs = sa.vslot[t], qs = sa.qslot[t], ds = sa.slot[t];
     const long long total = B * Dv;
@@ -279,12 +275,10 @@ __global__ __launch_bounds__(256) void emb_qr_split_indices_kernel(IdxSplitArgs 
 
 int pow2ceil_qr(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
-}  // namespace
-
-extern "C" int dlrm_emb_fwd_qr(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
-                               const int64_t* rows_host, const int32_t* collisions_host, int op,
-                               const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
-                               float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err, void* stream) {
+int emb_fwd_qr_impl(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
+                    const int64_t* rows_host, const int32_t* collisions_host, int op,
+                    const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
+                    float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err, DlrmPred pred, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0) return DLRM_E_ARG;
     if (!weight_host || !weight_r_host || !rows_host || !collisions_host || !indices_host || !offsets_host || !nnz_host) return DLRM_E_ARG;
     if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
@@ -316,7 +310,7 @@ extern "C" int dlrm_emb_fwd_qr(int T, int64_t B, int D, const void* const* weigh
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
         EmbArgs a = {};
         QrArgs qa = {};
-        a.err = (long long*)err;
+        a.err = (long long*)err; a.pred = pred;
         for (int k = 0; k < n; ++k) {
             const int t = t0 + k;
             const int c = collisions_host[t];
@@ -355,8 +349,8 @@ extern "C" int dlrm_emb_fwd_qr(int T, int64_t B, int D, const void* const* weigh
     return 0;
 }
 
-extern "C" int dlrm_emb_qr_bwd_split(int T, int64_t B, int D, const int32_t* collisions_host, int op, const float* dout, int64_t dout_ld,
-                                     const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld, void* stream) {
+int emb_qr_bwd_split_impl(int T, int64_t B, int D, const int32_t* collisions_host, int op, const float* dout, int64_t dout_ld,
+                          const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld, DlrmPred pred, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0 || !collisions_host || !dout || !gout) return DLRM_E_ARG;
     if (op != DLRM_QR_MULT && op != DLRM_QR_ADD) return DLRM_E_MODE;
     int n_qr = 0;
@@ -371,6 +365,7 @@ extern "C" int dlrm_emb_qr_bwd_split(int T, int64_t B, int D, const int32_t* col
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
         SplitArgs sa = {};
+        sa.pred = pred;
         for (int k = 0; k < n; ++k) {
             const int c = collisions_host[t0 + k];
             sa.slot[k] = t0 + k; sa.vslot[k] = vslot; sa.qslot[k] = c ? qslot++ : -1;
@@ -388,6 +383,39 @@ extern "C" int dlrm_emb_qr_bwd_split(int T, int64_t B, int D, const int32_t* col
         DLRM_LAUNCH_CHECK();
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int dlrm_emb_fwd_qr(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
+                               const int64_t* rows_host, const int32_t* collisions_host, int op,
+                               const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
+                               float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err, void* stream) {
+    return emb_fwd_qr_impl(T, B, D, weight_host, weight_r_host, rows_host, collisions_host, op, indices_host, offsets_host, nnz_host, idx_bits,
+                           out, out_ld, saved, saved_ld, err, DlrmPred{nullptr, 0}, stream);
+}
+
+// dlrm_emb_fwd_qr behind a launch predicate (common.h DlrmPred): the same kernels, whose workgroups return at once unless
+// (*pred_flag != 0) == (pred_nonzero != 0)
+extern "C" int dlrm_emb_fwd_qr_pred(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
+                                    const int64_t* rows_host, const int32_t* collisions_host, int op,
+                                    const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
+                                    float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err,
+                                    const int32_t* pred_flag, int pred_nonzero, void* stream) {
+    return emb_fwd_qr_impl(T, B, D, weight_host, weight_r_host, rows_host, collisions_host, op, indices_host, offsets_host, nnz_host, idx_bits,
+                           out, out_ld, saved, saved_ld, err, DlrmPred{(const int*)pred_flag, pred_nonzero}, stream);
+}
+
+extern "C" int dlrm_emb_qr_bwd_split(int T, int64_t B, int D, const int32_t* collisions_host, int op, const float* dout, int64_t dout_ld,
+                                     const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld, void* stream) {
+    return emb_qr_bwd_split_impl(T, B, D, collisions_host, op, dout, dout_ld, saved, saved_ld, gout, gout_ld, DlrmPred{nullptr, 0}, stream);
+}
+
+extern "C" int dlrm_emb_qr_bwd_split_pred(int T, int64_t B, int D, const int32_t* collisions_host, int op, const float* dout,
+                                          int64_t dout_ld, const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld,
+                                          const int32_t* pred_flag, int pred_nonzero, void* stream) {
+    return emb_qr_bwd_split_impl(T, B, D, collisions_host, op, dout, dout_ld, saved, saved_ld, gout, gout_ld,
+                                 DlrmPred{(const int*)pred_flag, pred_nonzero}, stream);
 }
 
 extern "C" int dlrm_emb_qr_split_indices(int T, const int64_t* rows_host, const int32_t* collisions_host, const void* const* indices_host,

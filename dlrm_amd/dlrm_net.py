@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
                          BF16EmbeddingBagsFunction, EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
-                         MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction)
+                         MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction, QRGatherInteractFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
 
@@ -337,6 +337,11 @@ class DLRM_Net(nn.Module):
     # fp32 branch's conditions and runs csrc/interact_bf16.hip (forward and backward) instead of dlrm_emb_fwd_bf16 + the interaction kernels
     # through the pooled [B, T*D] buffer — the same bits.  Off: a bfloat16 model runs exactly the two-kernel form.
     fuse_bf16_interact = False
+    # opt-in (launcher: --qr-fuse-interact): a model with quotient-remainder tables enters the fused lookup + interaction branch of
+    # sequential_forward under the fp32 branch's conditions and runs csrc/interact_qr.hip (forward and backward) instead of dlrm_emb_fwd_qr + the
+    # interaction kernels + dlrm_emb_qr_bwd_split through the pooled [B, T*D] buffer and the [B, 2*Tq*D] pooled sums — the same bits.  Off: a QR
+    # model runs exactly the two-kernel form.
+    fuse_qr_interact = False
     quantize_mlp_bits = 32      # 8 / 16 after quantize_mlp()
 
     # ---------------------------------------------------------------- parameter construction
@@ -1025,8 +1030,12 @@ class DLRM_Net(nn.Module):
             else:
                 z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)
             return self._clamp(self.apply_mlp(z, self.top_l))
-        # (a model with a QR or a mixed-dimension table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it the
-        # step-time update, update_in_backward included)
+        # (a model with a mixed-dimension table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it
+        # the step-time update, update_in_backward included.  So does a model with a QR table unless fuse_qr_interact is set: _qr_fused_forward)
+        if self.fuse_qr_interact and self._has_qr(self.emb_l):
+            z = self._qr_fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
+            if z is not None:
+                return self._clamp(self.apply_mlp(z, self.top_l))
         # (a bfloat16 model enters only with fuse_bf16_interact set, and then runs the kernels of csrc/interact_bf16.hip: ops.interact_*_gather
         # dispatch on the tables' dtype)
         bf16_fused = self.emb_bf16 is not None and self.fuse_bf16_interact
@@ -1083,6 +1092,39 @@ class DLRM_Net(nn.Module):
         else:
             z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)   # [B, round4(width)], zero padded
         return self._clamp(self.apply_mlp(z, self.top_l))
+
+    def _qr_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
+        """The interaction output of a model with QR tables through csrc/interact_qr.hip (QRGatherInteractFunction), or None when the two-kernel
+        form has to run: the conditions and the offsets state machine of the fp32 fused branch of sequential_forward — True / None -> the fused
+        kernels alone; a device flag -> both forms behind the launch predicate, no host wait; False (proven ragged) -> None.  The update stays
+        the step-time one (bags.presort = None), update_in_backward included."""
+        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and self.emb_bf16 is None
+                and ops.gather_qr_ok(1 + T, D) and not self._has_md(self.emb_l)
+                and not any(w is not None for w in (self.v_W_l or []))):
+            return None
+        bags = self._bags(lS_o, lS_i, None)
+        qr = [isinstance(e, QREmbeddingBagHolder) for e in self.emb_l]
+        if not (all(n == B for n in bags.nnz)
+                and ops.qr_tables_aligned([e.weight_q if q else e.weight for e, q in zip(self.emb_l, qr)],
+                                          [e.weight_r if q else None for e, q in zip(self.emb_l, qr)])):
+            return None
+        proof = None
+        if DEVICE_PREDICATE:
+            state = ops.offsets_iota_state(lS_o)
+        else:
+            proof = ops.offsets_are_iota_start(lS_o)
+            state = proof if (proof is None or isinstance(proof, bool)) else "pending"
+        if state is False:
+            return None
+        x = self.apply_mlp(dense_x, self.bot_l, consumer_applies_last_act=bool(rx))
+        if proof is not None and state == "pending":
+            state = ops.offsets_are_iota_finish(proof)
+        if state is False:
+            return None          # a ragged batch with nnz == B after all: the two-kernel form (the bottom tower runs again, into its slot)
+        bags.iota_flag = state if isinstance(state, torch.Tensor) else None
+        bags.presort = None
+        return QRGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, self._qr_spec(self.emb_l), x,
+                                              *self._emb_weights(self.emb_l))
 
     def _quant_fused_forward(self, dense_x, lS_o, lS_i, B, T, D):
         """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run:

@@ -768,6 +768,73 @@ class GatherInteractFunction(Function):
         return (None, None, None, None, dx) + (None,) * T
 
 
+class QRGatherInteractFunction(Function):
+    """GatherInteractFunction for a table list with quotient-remainder tables (csrc/interact_qr.hip): R = [x | lower-triangular dots of
+    (x, the composed rows Wq[q] o Wr[r], plain rows)], the rows fetched and composed by the interaction kernel itself — the bits of
+    QREmbeddingBagsFunction + InteractFunction without the [B, T*D] pooled buffer, its gradient or the [B, 2*Tq*D] pooled sums.
+    spec = (rows, collisions, operation, keep_sums) and `vweights` = the VIRTUAL table list, as QREmbeddingBagsFunction takes them.  Backward
+    gathers the rows again, writes dx and the gradient buffer of the virtual list and hands (virtual weights, virtual bags, buffer) to `sink`:
+    exactly what QREmbeddingBagsFunction.backward hands over."""
+
+    @staticmethod
+    def forward(ctx, sink, D, self_interaction, bags, spec, x, *vweights):
+        rows, collisions, op, keep_sums = spec
+        weights, weights_r = [], []
+        it = iter(vweights)
+        for c in collisions:
+            weights.append(next(it))
+            weights_r.append(next(it) if c else None)
+        x = _rowmajor(x)
+        B, T = x.size(0), len(weights)
+        mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
+        R = torch.empty((B, _round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
+        # `bags.iota_flag`: as GatherInteractFunction.forward — the fused kernel behind (flag, 0), the two-kernel form behind (flag, 1)
+        flag = getattr(bags, "iota_flag", None)
+        ly = saved = None
+        if flag is None:
+            ops.interact_fwd_gather_qr(x, weights, weights_r, rows, collisions, op, bags, D, mode, R)
+        else:
+            ops.interact_fwd_gather_qr(x, weights, weights_r, rows, collisions, op, bags, D, mode, R, pred=(flag, 0))
+            ly = alloc2d(B, T * D, x)
+            if keep_sums and op == "mult":
+                saved = torch.empty((B, 2 * D * sum(1 for c in collisions if c)), dtype=torch.float32, device=x.device)
+            ops.emb_fwd_qr(weights, weights_r, rows, collisions, op, bags, ly, saved, pred=(flag, 1))
+            ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
+        ctx.sink, ctx.bags, ctx.spec = sink, bags, spec
+        ctx.tables = (weights, weights_r)
+        ctx.vweights = vweights      # parameters (leaves) — kept by reference, not via save_for_backward
+        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
+        ctx.flag, ctx.saved = flag, saved
+        if ly is None:
+            ctx.save_for_backward(x)
+        else:
+            ctx.save_for_backward(x, ly)
+        return R                                   # [B, round4(width)], zero padding columns (what MLPFunction takes as is)
+
+    @staticmethod
+    def backward(ctx, dR):
+        if ctx.sink is None:
+            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+        x = ctx.saved_tensors[0]
+        dR = _rowmajor(dR)
+        rows, collisions, op, _ = ctx.spec
+        weights, weights_r = ctx.tables
+        B, D, T = x.size(0), ctx.D, len(weights)
+        Tv = T + sum(1 for c in collisions if c)
+        dx = torch.empty((B, D), dtype=torch.float32, device=dR.device)
+        gout = torch.empty((B, Tv * D), dtype=torch.float32, device=dR.device)
+        pred = None if ctx.flag is None else (ctx.flag, 0)
+        ops.interact_bwd_gather_qr(x, weights, weights_r, rows, collisions, op, ctx.bags, D, ctx.self_interaction, dR, dx, gout, pred=pred)
+        if ctx.flag is not None:
+            if op == "mult" and ctx.saved is None:
+                raise RuntimeError("dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept")
+            dE = torch.empty((B, T * D), dtype=torch.float32, device=dR.device)
+            ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
+            ops.emb_qr_bwd_split(collisions, op, D, dE, ctx.saved, gout, pred=(ctx.flag, 1))
+        ctx.sink(ctx.vweights, ops.qr_virtual_bags(rows, collisions, ctx.bags), gout)
+        return (None, None, None, None, None, dx) + (None,) * len(ctx.vweights)
+
+
 class LowRankCrossNetFunction(Function):
     """DCN-v2 interaction (torchrec.modules.crossnet.LowRankCrossNet, the MLPerf-v2 default: torchrec_dlrm/dlrm_main.py:608-619):
         x_{l+1} = x_0 * (W_l (V_l x_l) + b_l) + x_l,   l = 0 .. L-1,   on the flattened feature buffer x_0 [B, F*D].

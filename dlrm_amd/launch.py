@@ -98,6 +98,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--bf16-fuse-interact", action="store_true",
                     help="with --bf16-tables: fetch the bfloat16 rows inside the interaction kernels, forward and backward "
                          "(DLRM_Net.fuse_bf16_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer)")
+    ap.add_argument("--qr-fuse-interact", action="store_true",
+                    help="with the reference's --qr-flag: fetch and compose the quotient / remainder rows inside the interaction kernels, "
+                         "forward and backward (DLRM_Net.fuse_qr_interact; same bits as the default two-kernel form, no pooled [B, T*D] "
+                         "buffer and no pooled sums kept for the backward)")
     return ap
 
 
@@ -118,6 +122,9 @@ def main(argv=None) -> None:
             sys.exit("ERROR: --bf16-fuse-interact needs --bf16-tables")
         import dlrm_amd
         dlrm_amd.DLRM_Net.fuse_bf16_interact = True        # every model run() builds from here on
+    if a.qr_fuse_interact:
+        import dlrm_amd
+        dlrm_amd.DLRM_Net.fuse_qr_interact = True          # every model run() builds from here on (a model without QR tables ignores it)
     sys.argv = [os.path.join(a.reference, "dlrm_s_pytorch.py")] + ref_args
     ref.run()
 

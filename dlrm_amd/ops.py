@@ -455,9 +455,10 @@ def _qr_desc(weights, weights_r, rows, collisions):
 
 
 def emb_fwd_qr(weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]], rows: Sequence[int], collisions: Sequence[int],
-               op: str, bags: BagBatch, out: torch.Tensor, saved: Optional[torch.Tensor] = None) -> torch.Tensor:
+               op: str, bags: BagBatch, out: torch.Tensor, saved: Optional[torch.Tensor] = None, pred=None) -> torch.Tensor:
     """emb_fwd over a table list with QR tables: out[b, t*D:(t+1)*D] = (sum Wq[q_i]) op (sum Wr[r_i]) for a QR table, the pooled sum for a plain
-    one.  saved: a [B, >= 2*Tq*D] buffer that receives the two sums of every QR table (what emb_qr_bwd_split reads)."""
+    one.  saved: a [B, >= 2*Tq*D] buffer that receives the two sums of every QR table (what emb_qr_bwd_split reads).
+    pred = (flag, nonzero): launch predicate (dlrm_emb_fwd_qr_pred)."""
     lib = _lib.load()
     D, wp, wrp, rows_a, coll_a = _qr_desc(weights, weights_r, rows, collisions)
     _req(out, "out", ndim=2)
@@ -472,17 +473,23 @@ def emb_fwd_qr(weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[tor
             raise RuntimeError("dlrm_amd: emb_fwd_qr `saved` is a [B, >= 2 * (QR tables) * D] buffer")
         sv_p, sv_ld = C.c_void_p(saved.data_ptr()), _ld(saved)
     err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
-    with _timed("emb_fwd"):
-        rc = lib.dlrm_emb_fwd_qr(bags.T, bags.B, D, wp, wrp, rows_a, coll_a, _qr_op(op), bags._idx, bags._off, bags._nnz, bags.idx_bits,
-                                 C.c_void_p(out.data_ptr()), _ld(out), sv_p, sv_ld, err, _stream(out))
+    st = _stream(out)
+    with _timed("emb_fwd" if pred is None else "emb_interact_fwd_qr"):
+        if pred is None:
+            rc = lib.dlrm_emb_fwd_qr(bags.T, bags.B, D, wp, wrp, rows_a, coll_a, _qr_op(op), bags._idx, bags._off, bags._nnz, bags.idx_bits,
+                                     C.c_void_p(out.data_ptr()), _ld(out), sv_p, sv_ld, err, st)
+        else:
+            rc = lib.dlrm_emb_fwd_qr_pred(bags.T, bags.B, D, wp, wrp, rows_a, coll_a, _qr_op(op), bags._idx, bags._off, bags._nnz,
+                                          bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), sv_p, sv_ld, err, *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_emb_fwd_qr")
     return out
 
 
 def emb_qr_bwd_split(collisions: Sequence[int], op: str, D: int, dout: torch.Tensor, saved: Optional[torch.Tensor],
-                     gout: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     gout: Optional[torch.Tensor] = None, pred=None) -> torch.Tensor:
     """[B, Tv*D] gradient buffer of the virtual table list (a QR table = its q table, then its r table) from dout [B, >= T*D]:
-    dout * sr, dout * sq ("mult"; `saved` of emb_fwd_qr) | dout, dout ("add") | a copy for plain tables."""
+    dout * sr, dout * sq ("mult"; `saved` of emb_fwd_qr) | dout, dout ("add") | a copy for plain tables.
+    pred = (flag, nonzero): launch predicate (dlrm_emb_qr_bwd_split_pred)."""
     lib = _lib.load()
     T = len(collisions)
     Tv = T + sum(1 for c in collisions if c)
@@ -501,9 +508,14 @@ def emb_qr_bwd_split(collisions: Sequence[int], op: str, D: int, dout: torch.Ten
         if saved.size(0) != B or saved.size(1) < 2 * D * (Tv - T):
             raise RuntimeError("dlrm_amd: emb_qr_bwd_split `saved` is a [B, >= 2 * (QR tables) * D] buffer")
         sv_p, sv_ld = C.c_void_p(saved.data_ptr()), _ld(saved)
-    with _timed("emb_qr_bwd_split"):
-        rc = lib.dlrm_emb_qr_bwd_split(T, B, D, _i32_array(collisions), _qr_op(op), C.c_void_p(dout.data_ptr()), _ld(dout), sv_p, sv_ld,
-                                       C.c_void_p(gout.data_ptr()), _ld(gout), _stream(dout))
+    st = _stream(dout)
+    with _timed("emb_qr_bwd_split" if pred is None else "emb_interact_bwd_qr"):
+        if pred is None:
+            rc = lib.dlrm_emb_qr_bwd_split(T, B, D, _i32_array(collisions), _qr_op(op), C.c_void_p(dout.data_ptr()), _ld(dout), sv_p, sv_ld,
+                                           C.c_void_p(gout.data_ptr()), _ld(gout), st)
+        else:
+            rc = lib.dlrm_emb_qr_bwd_split_pred(T, B, D, _i32_array(collisions), _qr_op(op), C.c_void_p(dout.data_ptr()), _ld(dout), sv_p,
+                                                sv_ld, C.c_void_p(gout.data_ptr()), _ld(gout), *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_emb_qr_bwd_split")
     return gout
 
@@ -1142,6 +1154,71 @@ def interact_fwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
                                             *_pred_args(pred, st), st)
     _lib.check(rc, "dlrm_interact_fwd_gather")
     return R
+
+
+# ---- fused lookup + interaction over QR tables (csrc/interact_qr.hip); the table list is described as for emb_fwd_qr
+def gather_qr_ok(F: int, D: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_qr_ok(int(F), int(D)))
+
+
+def qr_tables_aligned(weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]]) -> bool:
+    """what the fused QR kernels need of weight_q / weight_r / plain tables: a lane's 4 columns are one 16-byte load"""
+    return all(w.data_ptr() % 16 == 0 for w in weights) and all(wr is None or wr.data_ptr() % 16 == 0 for wr in weights_r)
+
+
+def _gather_desc_qr(x: torch.Tensor, weights, weights_r, rows, collisions, bags: BagBatch, D: int):
+    """_gather_desc for a table list with QR tables: the same refusals; table t is feature t + 1"""
+    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
+    if bags._psw is not None:
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+    _req(x, "x", ndim=2)
+    Dw, wp, wrp, rows_a, coll_a = _qr_desc(weights, weights_r, rows, collisions)
+    if Dw != D or x.size(1) != D or x.size(0) != bags.B:
+        raise RuntimeError("dlrm_amd: the fused QR embedding + interaction path: shape mismatch")
+    return 1 + bags.T, wp, wrp, rows_a, coll_a
+
+
+def interact_fwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]], rows: Sequence[int],
+                           collisions: Sequence[int], op: str, bags: BagBatch, D: int, self_interaction, R: torch.Tensor,
+                           pred=None) -> torch.Tensor:
+    """R = interaction of [x | the composed rows of the tables], the rows fetched and composed by the kernel itself
+    (dlrm_interact_fwd_gather_qr): the bits of emb_fwd_qr into a feature buffer + interact_fwd, without that buffer."""
+    lib = _lib.load()
+    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
+    _req(R, "R", ndim=2)
+    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+        raise RuntimeError("dlrm_amd: interact_fwd_gather_qr shape mismatch")
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_fwd_qr"):
+        rc = lib.dlrm_interact_fwd_gather_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
+                                             bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
+                                             C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_fwd_gather_qr")
+    return R
+
+
+def interact_bwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]], rows: Sequence[int],
+                           collisions: Sequence[int], op: str, bags: BagBatch, D: int, self_interaction, dR: torch.Tensor,
+                           dx: torch.Tensor, gout: torch.Tensor, pred=None) -> None:
+    """dx [B, D] = gradient of x; gout [B, >= Tv*D] = the gradient buffer of the VIRTUAL table list, as emb_qr_bwd_split lays it out
+    (dlrm_interact_bwd_gather_qr): the bits of interact_bwd over (x, the buffer emb_fwd_qr wrote) + emb_qr_bwd_split, without the pooled
+    buffer, its gradient or the saved sums.  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
+    lib = _lib.load()
+    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
+    Tv = bags.T + sum(1 for c in collisions if c)
+    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(gout, "gout", ndim=2)
+    if dR.size(0) != bags.B or dx.size(0) != bags.B or gout.size(0) != bags.B or dx.size(1) < D or gout.size(1) < Tv * D:
+        raise RuntimeError("dlrm_amd: interact_bwd_gather_qr shape mismatch")
+    st = _stream(dR)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_bwd_qr"):
+        rc = lib.dlrm_interact_bwd_gather_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
+                                             bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
+                                             C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(gout.data_ptr()), _ld(gout),
+                                             C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_bwd_gather_qr")
 
 
 def gather_quant_ok(F: int, D: int, bits: int) -> bool:

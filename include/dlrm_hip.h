@@ -370,6 +370,56 @@ int dlrm_interact_bwd_gather_bf16(int64_t B, int F, int D, const float* x, int64
                                   float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
                                   const int32_t* pred_flag, int pred_nonzero, void* stream);
 
+/* Fused lookup + interaction over quotient-remainder (QR) tables, FORWARD and BACKWARD (csrc/interact_qr.hip; symbols added, the ABI version
+ * stays 17).  Replaces, for one-lookup-per-bag batches: dlrm_emb_fwd_qr + dlrm_interact_fwd, and dlrm_interact_bwd over the pooled buffer +
+ * dlrm_emb_qr_bwd_split.  Feature 0 is the fp32 block x ([B, D], row stride x_ld); feature f = 1 .. F-1 is table f-1, whose operands follow
+ * dlrm_emb_fwd_qr: collisions_host[t] == 0 a plain fp32 table (weight_r_host[t] ignored), > 0 a QR table (weight_host[t] = weight_q
+ * [ceil(n / c), D], weight_r_host[t] = weight_r [c, D], rows_host[t] = n); op = DLRM_QR_MULT | DLRM_QR_ADD for the whole call.  The rows are
+ * fetched and composed by the interaction kernel itself: neither the [B, (F-1)*D] pooled buffer nor its gradient nor the [B, 2*Tq*D] saved sums
+ * of the two-kernel form are written or read.  D = 128 only; any c >= 1.
+ *   forward : R, ldr, self_interaction exactly dlrm_interact_fwd (mode word 0 / 1 / 2, R[:, :D] = x, zero-filled padding columns up to ldr).
+ *             R is BIT-IDENTICAL to dlrm_emb_fwd_qr (saved = NULL) into a feature buffer + dlrm_interact_fwd.
+ *   backward: dR, ldr, self_interaction (| DLRM_INTERACT_RELU_X) exactly dlrm_interact_bwd; writes dx [B, D] (row stride dx_ld) and
+ *             gout [B, >= Tv*D] (row stride gout_ld), the gradient buffer of the VIRTUAL table list as dlrm_emb_qr_bwd_split lays it out
+ *             (a QR table is a q table then an r table, Tv = T + Tq): dout * sr then dout * sq (MULT), dout twice (ADD), a copy for a plain
+ *             table.  dx and gout are BIT-IDENTICAL to dlrm_interact_bwd over (x, the buffer dlrm_emb_fwd_qr wrote) followed by
+ *             dlrm_emb_qr_bwd_split with the sums that forward would have saved.  For MULT a second kernel of the same call gathers the two
+ *             rows again and multiplies in place; one predicate covers both launches.
+ *   element = fmaf(1, Wq[q], +0) * fmaf(1, Wr[r], +0) (MULT) | ... + ... (ADD), each rounded once; a plain table fmaf(1, W[id], +0): -0.0 in
+ *             a table row becomes +0.0 before the composition.  q, r: the index split of dlrm_emb_fwd_qr (FLOAT32 quotient).
+ *   offsets_host[t] : verified on the device to be 0, 1, 2, ... — a violation is reported through `err` with rows = -1;
+ *   a lookup dlrm_emb_fwd_qr skips (id outside [0, n), quotient >= ceil(n / c)) is reported ({1, table, id, n}) and contributes the ZERO row; its
+ *   gout rows are dout * (+0) (MULT) or dout (ADD), as the two-kernel form writes them.  pred_flag / pred_nonzero: launch predicate (NULL: run).
+ * dlrm_interact_gather_qr_ok (host only): D == 128 && dlrm_interact_gather_ok(F, D); independent of the collisions.
+ * Returns DLRM_E_MODE for shapes that function refuses, a weight_q / weight_r / plain table / x / R / dR / dx / gout not aligned to 16 bytes, a
+ * leading dimension that is not a multiple of 4, a dR row that does not fit its image (ldr * 4 >= 2048); DLRM_E_RANGE for more than 0xFFFFFFFF
+ * rows in weight_q or in a plain table; DLRM_E_ARG for null operands (weight_r of a QR table included), rows <= 0, collisions < 0, an unknown
+ * op, leading dimensions smaller than their rows.
+ * dlrm_emb_fwd_qr_pred / dlrm_emb_qr_bwd_split_pred: dlrm_emb_fwd_qr / dlrm_emb_qr_bwd_split behind a launch predicate (the same kernels, whose
+ * workgroups return at once unless (*pred_flag != 0) == (pred_nonzero != 0)). */
+int dlrm_interact_gather_qr_ok(int F, int D);
+int dlrm_interact_fwd_gather_qr(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                const void* const* weight_host, const void* const* weight_r_host, const int64_t* rows_host,
+                                const int32_t* collisions_host, int op,
+                                const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_interact_bwd_gather_qr(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                const void* const* weight_host, const void* const* weight_r_host, const int64_t* rows_host,
+                                const int32_t* collisions_host, int op,
+                                const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                int self_interaction, const float* dR, int64_t ldr,
+                                float* dx, int64_t dx_ld, float* gout, int64_t gout_ld, int64_t* err,
+                                const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_emb_fwd_qr_pred(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
+                         const int64_t* rows_host, const int32_t* collisions_host, int op,
+                         const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
+                         float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err,
+                         const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_emb_qr_bwd_split_pred(int T, int64_t B, int D, const int32_t* collisions_host, int op, const float* dout, int64_t dout_ld,
+                               const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld,
+                               const int32_t* pred_flag, int pred_nonzero, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * K6  dot interaction forward.
  * Replaces: torch.cat + torch.bmm + Z[:, li, lj] + torch.cat in DLRM_Net.interact_features
