@@ -274,6 +274,36 @@ __global__ __launch_bounds__(256) void add_kernel(long long n4, const float4* __
         out[i] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
     }
 }
+// scalar forms of the three kernels above, same arithmetic per element (same fmaf, same RNE conversion, same `accumulate`): any n, operands
+// aligned to their element size only — an odd batch times a feature width that is no multiple of 4, a view at an odd storage offset
+__device__ __forceinline__ unsigned short lo_cvt_bf16(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+__global__ __launch_bounds__(256) void cross_fwd_scalar_kernel(long long n, const float* __restrict__ x0, const float* __restrict__ u,
+                                                               const float* __restrict__ xl, float* __restrict__ out,
+                                                               unsigned short* __restrict__ out16) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float r = __builtin_fmaf(x0[i], u[i], xl[i]);
+        out[i] = r;
+        if (out16) out16[i] = lo_cvt_bf16(r);
+    }
+}
+template <bool U16>
+__global__ __launch_bounds__(256) void cross_bwd_scalar_kernel(long long n, const float* __restrict__ g, const float* __restrict__ x0,
+                                                               const void* __restrict__ uv, float* __restrict__ du,
+                                                               unsigned short* __restrict__ du16, float* __restrict__ dx0, int accumulate) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float gg = g[i];
+        float b;
+        if constexpr (U16) b = __uint_as_float((unsigned)((const unsigned short*)uv)[i] << 16);
+        else               b = ((const float*)uv)[i];
+        const float r = gg * x0[i];
+        if (du) du[i] = r;
+        if (du16) du16[i] = lo_cvt_bf16(r);
+        dx0[i] = __builtin_fmaf(gg, b, accumulate ? dx0[i] : 0.f);
+    }
+}
+__global__ __launch_bounds__(256) void add_scalar_kernel(long long n, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) out[i] = a[i] + b[i];
+}
 
 // torch.clamp(x, lo, hi) of the predictions (--loss-threshold, dlrm_s_pytorch.py:580-583,607-610) and its backward
 // (gradient passes where lo <= x <= hi, torch's clamp_backward mask)
@@ -516,11 +546,21 @@ static inline bool vec4_ok(int64_t n, const void* a, const void* b, const void* 
     return n % 4 == 0 && dlrm_aligned16(a) && dlrm_aligned16(b) && (!c || dlrm_aligned16(c)) && (!d || dlrm_aligned16(d)) && (!e || dlrm_aligned16(e));
 }
 
+// fp32 operands of the scalar forms: aligned to their element size (nullable operands pass)
+static inline bool elem_ok(const void* a, const void* b, const void* c, const void* d, const void* e) {
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e)) & 3u) == 0;
+}
+
+// float4 kernels where n % 4 == 0 and every operand is 16-byte (bf16: 8-byte) aligned, bit-identical scalar forms otherwise
 extern "C" int dlrm_cross_fwd(int64_t n, const float* x0, const float* u, const float* xl, float* out, uint16_t* out16, void* stream) {
     if (n <= 0 || !x0 || !u || !xl || !out) return DLRM_E_ARG;
-    if (!vec4_ok(n, x0, u, xl, out, nullptr) || (out16 && (((uintptr_t)out16) & 7u))) return DLRM_E_ALIGN;
-    hipLaunchKernelGGL(cross_fwd_kernel, dim3(ew_blocks_full(n / 4)), dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)x0,
-                       (const float4*)u, (const float4*)xl, (float4*)out, (uint2*)out16);
+    if (!elem_ok(x0, u, xl, out, nullptr) || (out16 && (((uintptr_t)out16) & 1u))) return DLRM_E_ALIGN;
+    if (vec4_ok(n, x0, u, xl, out, nullptr) && !(out16 && (((uintptr_t)out16) & 7u)))
+        hipLaunchKernelGGL(cross_fwd_kernel, dim3(ew_blocks_full(n / 4)), dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)x0,
+                           (const float4*)u, (const float4*)xl, (float4*)out, (uint2*)out16);
+    else
+        hipLaunchKernelGGL(cross_fwd_scalar_kernel, dim3(ew_blocks_full(n)), dim3(256), 0, (hipStream_t)stream, (long long)n, x0, u, xl, out,
+                           (unsigned short*)out16);
     DLRM_LAUNCH_CHECK();
     return 0;
 }
@@ -528,22 +568,33 @@ extern "C" int dlrm_cross_fwd(int64_t n, const float* x0, const float* u, const 
 extern "C" int dlrm_cross_bwd(int64_t n, const float* g, const float* x0, const float* u, const uint16_t* u16, float* du, uint16_t* du16, float* dx0,
                               int accumulate, void* stream) {
     if (n <= 0 || !g || !x0 || (!u == !u16) || (!du && !du16) || !dx0) return DLRM_E_ARG;
-    if (!vec4_ok(n, g, x0, u, du, dx0) || (du16 && (((uintptr_t)du16) & 7u)) || (u16 && (((uintptr_t)u16) & 7u))) return DLRM_E_ALIGN;
-    if (u16)
-        hipLaunchKernelGGL(cross_bwd_kernel<true>, dim3(ew_blocks_full(n / 4)), dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)g,
+    if (!elem_ok(g, x0, u, du, dx0) || (du16 && (((uintptr_t)du16) & 1u)) || (u16 && (((uintptr_t)u16) & 1u))) return DLRM_E_ALIGN;
+    const bool vec = vec4_ok(n, g, x0, u, du, dx0) && !(du16 && (((uintptr_t)du16) & 7u)) && !(u16 && (((uintptr_t)u16) & 7u));
+    const dim3 grid(vec ? ew_blocks_full(n / 4) : ew_blocks_full(n));
+    if (vec && u16)
+        hipLaunchKernelGGL(cross_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)g,
                            (const float4*)x0, (const void*)u16, (float4*)du, (uint2*)du16, (float4*)dx0, accumulate ? 1 : 0);
-    else
-        hipLaunchKernelGGL(cross_bwd_kernel<false>, dim3(ew_blocks_full(n / 4)), dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)g,
+    else if (vec)
+        hipLaunchKernelGGL(cross_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)g,
                            (const float4*)x0, (const void*)u, (float4*)du, (uint2*)du16, (float4*)dx0, accumulate ? 1 : 0);
+    else if (u16)
+        hipLaunchKernelGGL(cross_bwd_scalar_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (long long)n, g, x0, (const void*)u16, du,
+                           (unsigned short*)du16, dx0, accumulate ? 1 : 0);
+    else
+        hipLaunchKernelGGL(cross_bwd_scalar_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (long long)n, g, x0, (const void*)u, du,
+                           (unsigned short*)du16, dx0, accumulate ? 1 : 0);
     DLRM_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int dlrm_add(int64_t n, const float* a, const float* b, float* out, void* stream) {
     if (n <= 0 || !a || !b || !out) return DLRM_E_ARG;
-    if (!vec4_ok(n, a, b, out, nullptr, nullptr)) return DLRM_E_ALIGN;
-    hipLaunchKernelGGL(add_kernel, dim3(ew_blocks_full(n / 4)), dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)a,
-                       (const float4*)b, (float4*)out);
+    if (!elem_ok(a, b, out, nullptr, nullptr)) return DLRM_E_ALIGN;
+    if (vec4_ok(n, a, b, out, nullptr, nullptr))
+        hipLaunchKernelGGL(add_kernel, dim3(ew_blocks_full(n / 4)), dim3(256), 0, (hipStream_t)stream, (long long)(n / 4), (const float4*)a,
+                           (const float4*)b, (float4*)out);
+    else
+        hipLaunchKernelGGL(add_scalar_kernel, dim3(ew_blocks_full(n)), dim3(256), 0, (hipStream_t)stream, (long long)n, a, b, out);
     DLRM_LAUNCH_CHECK();
     return 0;
 }

@@ -825,8 +825,11 @@ int dlrm_bce_elementwise_bwd(int64_t n, const float* p, const float* target, con
 /* DCN-v2 interaction (MLPerf-v2's default, torchrec_dlrm/dlrm_main.py:608-619; torchrec LowRankCrossNet, not in the tree):
  *   x_{l+1} = x_0 * (W_l (V_l x_l) + b_l) + x_l  on the flattened [B, F*D] feature buffer.  The two products of a layer are
  *   dlrm_linear_fwd calls (act none; V without bias); these are the elementwise halves, contiguous fp32 arrays of n elements
- *   (n % 4 == 0, 16-byte aligned):  dlrm_cross_fwd  out = x0 * u + xl;   dlrm_cross_bwd  du = g * x0,  dx0 (+)= g * u
- *   (accumulate != 0 adds into dx0);  dlrm_add  out = a + b  (the gradient reaching x_l through the V product joins g). */
+ *   (any n >= 1; fp32 operands 4-byte, bf16 operands 2-byte aligned — DLRM_E_ALIGN otherwise.  float4 kernels where n % 4 == 0 and every
+ *   operand is 16-byte (bf16: 8-byte) aligned, scalar kernels of the same arithmetic, bit-identical per element, for the rest: an odd batch
+ *   times a width that is no multiple of 4, a view at an odd storage offset):
+ *   dlrm_cross_fwd  out = fma(x0, u, xl);   dlrm_cross_bwd  du = g * x0,  dx0 = fma(g, u, accumulate ? dx0 : 0)
+ *   (accumulate == 0: dx0 is written, never read);  dlrm_add  out = a + b  (the gradient reaching x_l through the V product joins g). */
 int dlrm_cross_fwd(int64_t n, const float* x0, const float* u, const float* xl, float* out, uint16_t* out16 /* nullable: bf16(out) */, void* stream);
 int dlrm_cross_bwd(int64_t n, const float* g, const float* x0, const float* u /* fp32 u ... */, const uint16_t* u16 /* ... or its bf16 copy: exactly one */,
                    float* du /* nullable */, uint16_t* du16 /* nullable: bf16(g * x0) */, float* dx0, int accumulate, void* stream);

@@ -915,10 +915,12 @@ def test_graphed_step_survives_host_syncs_at_full_batch():
     assert runs[0] == runs[1], [(a, b) for a, b in zip(*runs) if a != b][:4]
 
 
-@pytest.mark.parametrize("B,n,r,L,arith", [(300, 64, 16, 3, "f32"), (4096, 3456, 512, 3, "f32"), (4096, 3456, 512, 2, "bf16x6"), (70, 20, 4, 1, "f32")])
+@pytest.mark.parametrize("B,n,r,L,arith", [(300, 64, 16, 3, "f32"), (4096, 3456, 512, 3, "f32"), (4096, 3456, 512, 2, "bf16x6"), (70, 20, 4, 1, "f32"),
+                                                  (67, 15, 3, 2, "f32"), (1, 5, 2, 1, "f32")])
 def test_dcn_v2_cross_network_matches_oracle(B, n, r, L, arith):
     """LowRankCrossNetFunction (DCN-v2, the MLPerf-v2 interaction: GEMM kernels + dlrm_cross_fwd / _bwd, hand-written backward)
-    against the float64 oracle: output, gradient of x_0 and of every V / W / bias — at the benchmark's 27 x 128 -> rank 512 shape too."""
+    against the float64 oracle: output, gradient of x_0 and of every V / W / bias — at the benchmark's 27 x 128 -> rank 512 shape too, and
+    where B * n is no multiple of 4 (67 x 15, 1 x 5: the scalar forms of the elementwise halves)."""
     from dlrm_amd import ops
     from dlrm_amd.functional import LowRankCrossNetFunction
     device = torch.device("cuda:0")
