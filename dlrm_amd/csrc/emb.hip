@@ -539,7 +539,18 @@ static int emb_fwd_impl(int T, int64_t B, int D, const void* const* weight_host,
         fill_args(a, ids, n, (void* const*)weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err);
         a.pred = pred;
         dim3 grid((unsigned)((B + bags_per_block - 1) / bags_per_block), (unsigned)n, 1), block(256, 1, 1);
-        if (pred.flag) {           // predicated: the D = 128 shape only (what the fused path's fallback needs), capped grid + grid stride
+        if (pred.flag) {           // predicated: the shapes of the fused paths' fallbacks only (D = 128; D = 16 / 32 / 64), capped grid + grid stride
+            if (sh.vec == 4 && sh.nch == 1 && (sh.lpb == 4 || sh.lpb == 8 || sh.lpb == 16)) {
+                // the narrow widths: the LOOP form of the instantiation the plain call launches (same U, so `grid` holds), the same in-order
+                // sums per lane and therefore the same bits
+                dim3 gl(grid.x < 512u ? grid.x : 512u, (unsigned)n, 1);
+#define EMB_FWD_PL(LPBV) do { if (idx_bits == 64) hipLaunchKernelGGL((emb_fwd_kernel<4, LPBV, 1, long long, kU, true>), gl, block, 0, st, a, (long long)B, D, out, (long long)out_ld); \
+                              else hipLaunchKernelGGL((emb_fwd_kernel<4, LPBV, 1, int, kU, true>), gl, block, 0, st, a, (long long)B, D, out, (long long)out_ld); } while (0)
+                if (sh.lpb == 4) EMB_FWD_PL(4); else if (sh.lpb == 8) EMB_FWD_PL(8); else EMB_FWD_PL(16);
+#undef EMB_FWD_PL
+                DLRM_LAUNCH_CHECK();
+                continue;
+            }
             if (!(sh.vec == 4 && sh.lpb == 32 && sh.nch == 1)) return DLRM_E_MODE;
             dim3 gl(grid.x < 512u ? grid.x : 512u, (unsigned)n, 1);
             if (idx_bits == 64) hipLaunchKernelGGL((emb_fwd_kernel<4, 32, 1, long long, 2, true>), gl, block, 0, st, a, (long long)B, D, out, (long long)out_ld);

@@ -101,9 +101,13 @@ __device__ __forceinline__ void stage_sample(float* my, const long long* tp, con
 // -------------------------------------------------------------------------------------------
 // forward
 // -------------------------------------------------------------------------------------------
+// PRED (dlrm_interact_fwd_pred without gather, the fallback of the narrow fused path): one early return per workgroup; the default is the
+// kernel of every other call, which never looks at `pred`
+template <bool PRED = false>
 __global__ __launch_bounds__(256) void interact_fwd_kernel(FeatArgs fa, long long B, int F, int D, int self,
                                                            float* __restrict__ R, long long ldr, int vec,
-                                                           int d4shift) {
+                                                           int d4shift, DlrmPred pred) {
+    if constexpr (PRED) { if (pred.skip()) return; }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int Dp = (D + 15) & ~15;
@@ -163,10 +167,11 @@ __global__ __launch_bounds__(256) void interact_fwd_kernel(FeatArgs fa, long lon
 // -------------------------------------------------------------------------------------------
 // backward
 // -------------------------------------------------------------------------------------------
-template <int NB>
+template <int NB, bool PRED = false>          // PRED: as interact_fwd_kernel
 __global__ __launch_bounds__(256) void interact_bwd_kernel(FeatArgs fa, FeatArgs da, long long B, int F, int D,
                                                            int self, const float* __restrict__ dR,
-                                                           long long ldr, int vec, int d4shift) {
+                                                           long long ldr, int vec, int d4shift, DlrmPred pred) {
+    if constexpr (PRED) { if (pred.skip()) return; }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int Dp = (D + 15) & ~15;
@@ -960,8 +965,9 @@ extern "C" int dlrm_interact_fwd_gather(int64_t B, int F, int D, const void* con
 }
 
 // One call, two implementations, chosen ON THE DEVICE (ABI 16): the same arguments as dlrm_interact_fwd / _fwd_gather / _bwd / _bwd_gather plus a
-// predicate — the launch's workgroups return at once unless (*pred_flag != 0) == (pred_nonzero != 0).  Only the D = 128 LDS-DMA kernels take
-// one (the shapes of the fused path); other shapes: DLRM_E_MODE.
+// predicate — the launch's workgroups return at once unless (*pred_flag != 0) == (pred_nonzero != 0).  The D = 128 LDS-DMA kernels take
+// one (the shapes of the fused path), and so do the generic kernels WITHOUT gather (the fallback of the narrow fused path, interact_narrow.hip);
+// gathered features at other shapes: DLRM_E_MODE.
 extern "C" int dlrm_interact_fwd_pred(int64_t B, int F, int D, const void* const* feat_host, const int64_t* feat_ld_host,
                                       const void* const* index_host, const void* const* offsets_host, const int64_t* rows_host,
                                       int idx_bits, int self_interaction, float* R, int64_t ldr, int64_t* err,
@@ -1035,17 +1041,25 @@ static int interact_fwd_impl(int64_t B, int F, int D, const void* const* feat_ho
         DLRM_LAUNCH_CHECK();
         return 0;
     }
-    if (pred.flag) return DLRM_E_MODE;                         // (predicated launches exist for the LDS-DMA kernels only)
     const int Dp = (D + 15) & ~15;
     const size_t lds = 2 * DLRM_MAX_FEATURES * sizeof(long long) + 4 * (size_t)(((F + 15) >> 4) * 16) * (Dp + 4) * sizeof(float);
     if (lds > 160 * 1024) {
         fprintf(stderr, "libdlrm_hip: dlrm_interact_fwd: F=%d, D=%d needs %zu B of LDS (> 160 KiB)\n", F, D, lds);
         return DLRM_E_RANGE;
     }
-    (void)hipFuncSetAttribute((const void*)interact_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(interact_fwd_kernel, dim3(pick_grid(B)), dim3(256), lds, (hipStream_t)stream, fa,
+    if (pred.flag) {           // the generic kernel behind a device predicate: a capped grid, since a launch that must not run still dispatches
+        const int gp = pick_grid(B) < 512 ? pick_grid(B) : 512;
+        (void)hipFuncSetAttribute((const void*)interact_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(interact_fwd_kernel<true>, dim3(gp), dim3(256), lds, (hipStream_t)stream, fa,
+                           (long long)B, F, D, self_interaction & 3, R, (long long)ldr, vec,
+                           vec ? log2_exact(D / 4) : -1, pred);
+        DLRM_LAUNCH_CHECK();
+        return 0;
+    }
+    (void)hipFuncSetAttribute((const void*)interact_fwd_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(interact_fwd_kernel<>, dim3(pick_grid(B)), dim3(256), lds, (hipStream_t)stream, fa,
                        (long long)B, F, D, self_interaction & 3, R, (long long)ldr, vec,
-                       vec ? log2_exact(D / 4) : -1);
+                       vec ? log2_exact(D / 4) : -1, pred);
     DLRM_LAUNCH_CHECK();
     return 0;
 }
@@ -1167,7 +1181,6 @@ static int interact_bwd_impl(int64_t B, int F, int D, const void* const* feat_ho
             return 0;
         }
     }
-    if (pred.flag) return DLRM_E_MODE;                         // (predicated launches exist for the LDS-DMA kernels only)
     const int Dp = (D + 15) & ~15, NB = (F + 15) >> 4, rows = NB * 16;
     const size_t lds = 4 * DLRM_MAX_FEATURES * sizeof(long long) +
                        4 * ((size_t)F * (Dp + 16) + (size_t)F * (rows + 1)) * sizeof(float);
@@ -1180,9 +1193,15 @@ static int interact_bwd_impl(int64_t B, int F, int D, const void* const* feat_ho
     hipStream_t st = (hipStream_t)stream;
 #define BWD_LAUNCH(NBV)                                                                                  \
     do {                                                                                                 \
+        if (pred.flag) {       /* behind a device predicate: a capped grid (the kernel walks the batch with a grid stride) */ \
+            (void)hipFuncSetAttribute((const void*)interact_bwd_kernel<NBV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            hipLaunchKernelGGL((interact_bwd_kernel<NBV, true>), dim3(grid.x < 512u ? grid.x : 512u), block, lds, st, fa, da, (long long)B, F, D, \
+                               self_interaction & 7, dR, (long long)ldr, vec, d4s, pred);            \
+            break;                                                                                       \
+        }                                                                                                \
         (void)hipFuncSetAttribute((const void*)interact_bwd_kernel<NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(interact_bwd_kernel<NBV>, grid, block, lds, st, fa, da, (long long)B, F, D,   \
-                           self_interaction & 7, dR, (long long)ldr, vec, d4s);                      \
+                           self_interaction & 7, dR, (long long)ldr, vec, d4s, pred);                \
     } while (0)
     switch (NB) {
         case 1: BWD_LAUNCH(1); break;

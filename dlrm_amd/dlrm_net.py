@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
                          BF16EmbeddingBagsFunction, EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
-                         MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction, QRGatherInteractFunction)
+                         MDEmbeddingBagsFunction, NarrowGatherInteractFunction, OutSlot, QREmbeddingBagsFunction, QRGatherInteractFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
 
@@ -342,6 +342,10 @@ class DLRM_Net(nn.Module):
     # interaction kernels + dlrm_emb_qr_bwd_split through the pooled [B, T*D] buffer and the [B, 2*Tq*D] pooled sums — the same bits.  Off: a QR
     # model runs exactly the two-kernel form.
     fuse_qr_interact = False
+    # opt-in (launcher: --narrow-fuse-interact): a model with plain fp32 tables of D = 16 / 32 / 64 enters the fused lookup + interaction branch
+    # of sequential_forward under the fp32 branch's conditions and runs csrc/interact_narrow.hip (forward and backward) instead of dlrm_emb_fwd
+    # + the generic interaction kernels through the pooled [B, T*D] buffer — the same bits.  Off: such a model runs exactly the two-kernel form.
+    fuse_narrow_interact = False
     quantize_mlp_bits = 32      # 8 / 16 after quantize_mlp()
 
     # ---------------------------------------------------------------- parameter construction
@@ -1036,6 +1040,10 @@ class DLRM_Net(nn.Module):
             z = self._qr_fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
             if z is not None:
                 return self._clamp(self.apply_mlp(z, self.top_l))
+        if self.fuse_narrow_interact:
+            z = self._narrow_fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
+            if z is not None:
+                return self._clamp(self.apply_mlp(z, self.top_l))
         # (a bfloat16 model enters only with fuse_bf16_interact set, and then runs the kernels of csrc/interact_bf16.hip: ops.interact_*_gather
         # dispatch on the tables' dtype)
         bf16_fused = self.emb_bf16 is not None and self.fuse_bf16_interact
@@ -1125,6 +1133,38 @@ class DLRM_Net(nn.Module):
         bags.presort = None
         return QRGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, self._qr_spec(self.emb_l), x,
                                               *self._emb_weights(self.emb_l))
+
+    def _narrow_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
+        """The interaction output of a model with plain fp32 tables of D = 16 / 32 / 64 through csrc/interact_narrow.hip
+        (NarrowGatherInteractFunction), or None when the two-kernel form has to run: the conditions and the offsets state machine of the fp32
+        fused branch of sequential_forward — True -> the fused kernels alone; a device flag -> both forms behind the launch predicate, no host
+        wait; False (proven ragged) -> None.  ONE difference: None (a HIP graph is being captured) -> None too, because GraphedTrainStep proves
+        the offsets of every incoming batch only for the shapes of ops.gather_ok.  The update stays the step-time one (bags.presort = None),
+        update_in_backward included: the update inside the backward exists at D = 128 only."""
+        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and self.emb_bf16 is None
+                and ops.gather_narrow_ok(1 + T, D) and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l)
+                and not any(w is not None for w in (self.v_W_l or []))):
+            return None
+        bags = self._bags(lS_o, lS_i, None)
+        if not (all(n == B for n in bags.nnz) and all(e.weight.data_ptr() % 16 == 0 for e in self.emb_l)):
+            return None
+        proof = None
+        if DEVICE_PREDICATE:
+            state = ops.offsets_iota_state(lS_o)
+        else:
+            proof = ops.offsets_are_iota_start(lS_o)
+            state = proof if (proof is None or isinstance(proof, bool)) else "pending"
+        if state is False or state is None:
+            return None
+        x = self.apply_mlp(dense_x, self.bot_l, consumer_applies_last_act=bool(rx))
+        if proof is not None and state == "pending":
+            state = ops.offsets_are_iota_finish(proof)
+        if state is False or state is None:
+            return None          # a ragged batch with nnz == B after all: the two-kernel form (the bottom tower runs again, into its slot)
+        bags.iota_flag = state if isinstance(state, torch.Tensor) else None
+        bags.presort = None
+        return NarrowGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x,
+                                                  *self._emb_weights(self.emb_l))
 
     def _quant_fused_forward(self, dense_x, lS_o, lS_i, B, T, D):
         """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run:

@@ -768,6 +768,53 @@ class GatherInteractFunction(Function):
         return (None, None, None, None, dx) + (None,) * T
 
 
+class NarrowGatherInteractFunction(Function):
+    """GatherInteractFunction for plain fp32 tables of D = 16 / 32 / 64 (csrc/interact_narrow.hip): the bits of EmbeddingBagsFunction +
+    InteractFunction without the [B, T*D] pooled buffer.  With `bags.iota_flag` absent the fused kernels run alone; with a device flag they run
+    behind (flag, 0) and dlrm_emb_fwd + the generic interaction kernels behind (flag, 1), the pooled buffer saved for the backward.  dE goes
+    to `sink` either way: one update call per step.  There is no update inside the backward at these widths (`bags.presort` is not read)."""
+
+    @staticmethod
+    def forward(ctx, sink, D, self_interaction, bags, x, *weights):
+        x = _rowmajor(x)
+        F = 1 + len(weights)
+        mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
+        R = torch.empty((x.size(0), _round4(ops.interact_out_width(F, D, mode))), dtype=torch.float32, device=x.device)
+        flag = getattr(bags, "iota_flag", None)
+        ly = None
+        if flag is None:
+            ops.interact_fwd_gather_narrow(x, weights, bags, D, mode, R)
+        else:
+            ops.interact_fwd_gather_narrow(x, weights, bags, D, mode, R, pred=(flag, 0))
+            ly = alloc2d(x.size(0), len(weights) * D, x)
+            ops.emb_fwd(weights, bags, ly, pred=(flag, 1))
+            ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
+        ctx.sink, ctx.bags, ctx.weights = sink, bags, weights
+        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
+        ctx.flag = flag
+        if ly is None:
+            ctx.save_for_backward(x)
+        else:
+            ctx.save_for_backward(x, ly)
+        return R                                   # [B, round4(width)], zero padding columns (what MLPFunction takes as is)
+
+    @staticmethod
+    def backward(ctx, dR):
+        if ctx.sink is None:
+            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+        x = ctx.saved_tensors[0]
+        dR = _rowmajor(dR)
+        B, D, T = x.size(0), ctx.D, len(ctx.weights)
+        flat = torch.empty(B * (1 + T) * D, dtype=torch.float32, device=dR.device)
+        dx, dE = flat[:B * D].view(B, D), flat[B * D:].view(B, T * D)
+        pred = None if ctx.flag is None else (ctx.flag, 0)
+        ops.interact_bwd_gather_narrow(x, ctx.weights, ctx.bags, D, ctx.self_interaction, dR, dx, dE, pred=pred)
+        if ctx.flag is not None:
+            ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
+        ctx.sink(ctx.weights, ctx.bags, dE)
+        return (None, None, None, None, dx) + (None,) * T
+
+
 class QRGatherInteractFunction(Function):
     """GatherInteractFunction for a table list with quotient-remainder tables (csrc/interact_qr.hip): R = [x | lower-triangular dots of
     (x, the composed rows Wq[q] o Wr[r], plain rows)], the rows fetched and composed by the interaction kernel itself — the bits of

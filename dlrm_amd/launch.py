@@ -102,6 +102,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with the reference's --qr-flag: fetch and compose the quotient / remainder rows inside the interaction kernels, "
                          "forward and backward (DLRM_Net.fuse_qr_interact; same bits as the default two-kernel form, no pooled [B, T*D] "
                          "buffer and no pooled sums kept for the backward)")
+    ap.add_argument("--narrow-fuse-interact", action="store_true",
+                    help="plain fp32 tables of --arch-sparse-feature-size 16 / 32 / 64: fetch the rows inside the interaction kernels, forward "
+                         "and backward (DLRM_Net.fuse_narrow_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer)")
     return ap
 
 
@@ -125,6 +128,9 @@ def main(argv=None) -> None:
     if a.qr_fuse_interact:
         import dlrm_amd
         dlrm_amd.DLRM_Net.fuse_qr_interact = True          # every model run() builds from here on (a model without QR tables ignores it)
+    if a.narrow_fuse_interact:
+        import dlrm_amd
+        dlrm_amd.DLRM_Net.fuse_narrow_interact = True      # every model run() builds from here on (other widths and table kinds ignore it)
     sys.argv = [os.path.join(a.reference, "dlrm_s_pytorch.py")] + ref_args
     ref.run()
 

@@ -1307,6 +1307,63 @@ def interact_bwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
     _lib.check(rc, "dlrm_interact_bwd_gather")
 
 
+# ---- fused lookup + interaction over plain fp32 tables of D = 16 / 32 / 64 (csrc/interact_narrow.hip).  Separate functions: interact_*_gather
+# keep refusing every D != 128
+def gather_narrow_ok(F: int, D: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_narrow_ok(int(F), int(D)))
+
+
+def _gather_desc_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
+    """_gather_desc's refusals for the narrow kernels; table t is feature t + 1"""
+    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
+    if bags._psw is not None:
+        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+    _req(x, "x", ndim=2)
+    Dw, wp, rows = _weights_desc(weights)
+    if Dw != D or x.size(1) != D or x.size(0) != bags.B:
+        raise RuntimeError("dlrm_amd: the fused narrow embedding + interaction path: shape mismatch")
+    return 1 + bags.T, wp, rows
+
+
+def interact_fwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
+                               R: torch.Tensor, pred=None) -> torch.Tensor:
+    """R = interaction of [x | one-hot rows of the fp32 tables], D = 16 / 32 / 64, the rows fetched by the kernel itself
+    (dlrm_interact_fwd_gather_narrow): the bits of emb_fwd into a feature buffer + interact_fwd, without that buffer."""
+    lib = _lib.load()
+    F, wp, rows = _gather_desc_narrow(x, weights, bags, D)
+    _req(R, "R", ndim=2)
+    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow shape mismatch")
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_fwd_narrow"):
+        rc = lib.dlrm_interact_fwd_gather_narrow(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
+                                                 bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
+                                                 C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_fwd_gather_narrow")
+    return R
+
+
+def interact_bwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
+                               dR: torch.Tensor, dx: torch.Tensor, dE: torch.Tensor, pred=None) -> None:
+    """dx [B, D] = gradient of x; dE [B, T*D] = gradients of the T gathered rows (dlrm_interact_bwd_gather_narrow): the bits of
+    interact_bwd over (x, the buffer emb_fwd wrote).  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
+    lib = _lib.load()
+    F, wp, rows = _gather_desc_narrow(x, weights, bags, D)
+    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
+    if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
+        raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow shape mismatch")
+    st = _stream(dR)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_bwd_narrow"):
+        rc = lib.dlrm_interact_bwd_gather_narrow(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
+                                                 bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
+                                                 C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(dE.data_ptr()), _ld(dE),
+                                                 C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_bwd_gather_narrow")
+
+
 def interact_bwd(blocks: Sequence[torch.Tensor], D: int, self_interaction: bool, dR: torch.Tensor,
                  dblocks: Sequence[torch.Tensor], order=None, pred=None) -> None:
     """`self_interaction` is the forward's mode, optionally OR-ed with INTERACT_RELU_X: feature 0 (the first D columns of blocks[0],

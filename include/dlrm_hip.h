@@ -370,6 +370,40 @@ int dlrm_interact_bwd_gather_bf16(int64_t B, int F, int D, const float* x, int64
                                   float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
                                   const int32_t* pred_flag, int pred_nonzero, void* stream);
 
+/* Fused lookup + interaction over plain fp32 tables of D = 16 / 32 / 64, FORWARD and BACKWARD (csrc/interact_narrow.hip; symbols added, the
+ * ABI version stays 17).  Replaces, for one-lookup-per-bag batches without per-sample weights: dlrm_emb_fwd + dlrm_interact_fwd, and
+ * dlrm_interact_bwd over the pooled buffer, at the widths where those run the generic interaction kernels.  Feature 0 is the fp32 block x
+ * ([B, D], row stride x_ld); feature f = 1 .. F-1 is row index_host[f-1][b] of the fp32 table weight_host[f-1] (rows_host[f-1] rows of D floats,
+ * 16-byte aligned), fetched by the interaction kernel itself: the [B, (F-1)*D] pooled buffer is neither written nor read.
+ *   forward : R, ldr, self_interaction exactly dlrm_interact_fwd (mode word 0 / 1 / 2, R[:, :D] = x, zero-filled padding columns up to ldr).
+ *             R is BIT-IDENTICAL to dlrm_emb_fwd (psw_host = NULL) into a feature buffer + dlrm_interact_fwd over (x, that buffer).
+ *   backward: dR, ldr, self_interaction (| DLRM_INTERACT_RELU_X) exactly dlrm_interact_bwd; writes dx [B, D] (row stride dx_ld) and
+ *             dE [B, (F-1)*D] (row stride dE_ld; table t at columns t*D.. — the dout of dlrm_emb_bwd_sgd / dlrm_emb_bwd_rowwise_adagrad).
+ *             dx, dE are BIT-IDENTICAL to dlrm_interact_bwd over (x, the buffer dlrm_emb_fwd wrote).  The gradient row of an out-of-range
+ *             lookup is written like any other (the update skips it).
+ *   element = fmaf(1.0f, W[id], +0.0f), as dlrm_emb_fwd produces it for a bag of one row (-0.0 becomes +0.0);
+ *   offsets_host[t] : verified on the device to be 0, 1, 2, ... — a violation is reported through `err` with rows = -1;
+ *   an index outside [0, rows) is reported ({1, table, index, rows}) and contributes a ZERO row, as dlrm_emb_fwd (not row 0, which the
+ *   D = 128 fp32 fused kernels read);   pred_flag / pred_nonzero : launch predicate as dlrm_*_pred (NULL: always run).
+ * dlrm_interact_gather_narrow_ok (host only): 1 iff D is 16, 32 or 64 and 1 <= F <= 32.
+ * Returns DLRM_E_MODE for shapes that function refuses, a table not aligned to 16 bytes, an x / R / dR / dx / dE not aligned to 16 bytes
+ * or a leading dimension that is not a multiple of 4; DLRM_E_RANGE for a table of more than 0xFFFFFFFF rows; DLRM_E_ARG for null operands,
+ * rows <= 0, leading dimensions smaller than their rows.
+ * The two-kernel form behind the opposite predicate exists at these widths too: dlrm_emb_fwd_pred takes D = 16 / 32 / 64 (16-byte aligned
+ * operands), and dlrm_interact_fwd_pred / dlrm_interact_bwd_pred WITHOUT gather take any shape of dlrm_interact_fwd / _bwd. */
+int dlrm_interact_gather_narrow_ok(int F, int D);
+int dlrm_interact_fwd_gather_narrow(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                    const void* const* weight_host, const int64_t* rows_host,
+                                    const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                    int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                    const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_interact_bwd_gather_narrow(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                    const void* const* weight_host, const int64_t* rows_host,
+                                    const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                    int self_interaction, const float* dR, int64_t ldr,
+                                    float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
+                                    const int32_t* pred_flag, int pred_nonzero, void* stream);
+
 /* Fused lookup + interaction over quotient-remainder (QR) tables, FORWARD and BACKWARD (csrc/interact_qr.hip; symbols added, the ABI version
  * stays 17).  Replaces, for one-lookup-per-bag batches: dlrm_emb_fwd_qr + dlrm_interact_fwd, and dlrm_interact_bwd over the pooled buffer +
  * dlrm_emb_qr_bwd_split.  Feature 0 is the fp32 block x ([B, D], row stride x_ld); feature f = 1 .. F-1 is table f-1, whose operands follow
@@ -484,7 +518,9 @@ int dlrm_interact_bwd_gather(int64_t B, int F, int D, const void* const* feat_ho
  *                             of a tensor object it will see again;
  *   dlrm_*_pred               the call without the suffix, whose workgroups return at once unless (*pred_flag != 0) == (pred_nonzero != 0)
  *                             (pred_flag == NULL: always run).  dlrm_interact_fwd_pred / _bwd_pred are the gather form when index_host != NULL
- *                             and the plain form otherwise; only the D = 128 LDS-DMA kernels take a predicate (else DLRM_E_MODE).
+ *                             and the plain form otherwise; the gather form exists at D = 128 only (else DLRM_E_MODE), the plain form takes a
+ *                             predicate at every shape (D = 128: the LDS-DMA kernels; else the generic kernels, one early return per
+ *                             workgroup).  dlrm_emb_fwd_pred takes 16-byte aligned operands at D = 128 and at D % 4 == 0, D <= 64.
  * A step therefore runs  fused(pred_nonzero = 0)  +  dlrm_emb_fwd_pred + dlrm_interact_fwd_pred(plain)(pred_nonzero = 1)  — three launches that
  * return at once for a one-lookup-per-bag batch, the fused one for a ragged batch — and its results are those of the implementation that ran. */
 int dlrm_offsets_iota_flags(int T, int64_t B, const void* const* offsets_host, int idx_bits, int32_t* flag_dev, int32_t* flag_host, void* stream);

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""The fused narrow (D = 16 / 32 / 64) fp32 lookup + interaction kernels (forward and backward) beside the two-kernel form they replace, same
+process, same GPU, same inputs.
+
+    python tools/bench_narrow_interact.py [--repeats 20] [--warmup 3] [--max-rows 10000000] [--out profiles/narrow_interact/fused_rates.md]
+
+Shapes: 26 tables, one lookup per bag, int64 ids; D = 64 with the Criteo-Terabyte row counts and D = 16 with the Criteo-Kaggle row counts
+(bench.py WORKLOADS), each at B = 2048 and B = 65536; row counts capped at --max-rows per table.
+  forward : dlrm_interact_fwd_gather_narrow (fused);  dlrm_emb_fwd + dlrm_interact_fwd over the buffer the lookup wrote (both launches inside
+            one timed interval, and the lookup alone).
+  backward: dlrm_interact_bwd_gather_narrow (fused);  dlrm_interact_bwd over (x, the pooled buffer) — the backward of the two-kernel form.
+
+Protocol (docs/MEASUREMENT.md): warm-up rounds, then `repeats` rounds; every round times each variant once between two HIP events (the
+variants alternate inside a round, so drift hits all alike); the MEDIAN over the rounds is reported with min / max.  Before timing, the
+fused results are compared with the two-kernel results bit for bit.  Algorithmic bytes: ids + offsets, table row bytes, x, R / dR, dx and
+dE; the two-kernel form adds the [B, T*D] fp32 buffer (forward: written and read back; backward: read).  No GPU: the tool fails."""
+from __future__ import annotations
+
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch
+
+FWD_FUSED = "forward: fused (dlrm_interact_fwd_gather_narrow)"
+FWD_TWO = "forward: two kernels (dlrm_emb_fwd + dlrm_interact_fwd)"
+FWD_LOOKUP = "forward: lookup alone (dlrm_emb_fwd)"
+BWD_FUSED = "backward: fused (dlrm_interact_bwd_gather_narrow)"
+BWD_TWO = "backward: two-kernel form (dlrm_interact_bwd)"
+
+
+def time_ms(fn) -> float:
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def same_bits(a, b) -> bool:
+    return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def make_tables(rows, D, dev, g):
+    return [torch.empty((n, D), dtype=torch.float32, device=dev).uniform_(-float(n) ** -0.5, float(n) ** -0.5, generator=g) for n in rows]
+
+
+def run_shape(name, tables, D, B, args, dev, lines, g):
+    from dlrm_amd import ops
+    rows = [w.size(0) for w in tables]
+    T = len(rows)
+    F = T + 1
+    offs = [ops.mark_one_lookup_per_bag(torch.arange(B, device=dev)) for _ in rows]
+    idxs = [torch.randint(0, n, (B,), device=dev, generator=g) for n in rows]
+    bags = ops.BagBatch(offs, idxs)
+    x = torch.randn((B, D), device=dev, generator=g)
+    Wd = ops.interact_out_width(F, D, 0)
+    ldr = (Wd + 3) & ~3
+    feat = torch.empty((B, F * D), dtype=torch.float32, device=dev)
+    feat[:, :D] = x
+    E = feat[:, D:]
+    dR = torch.zeros((B, ldr), dtype=torch.float32, device=dev)
+    dR[:, :Wd] = torch.randn((B, Wd), device=dev, generator=g)
+    R = {k: torch.empty((B, ldr), dtype=torch.float32, device=dev) for k in ("fused", "two")}
+    G = {k: (torch.empty((B, D), dtype=torch.float32, device=dev), torch.empty((B, T * D), dtype=torch.float32, device=dev))
+         for k in ("fused", "two")}
+    mode = ops.INTERACT_RELU_X          # what the model's backward passes (the bottom tower ends in a ReLU)
+
+    def two_fwd():
+        ops.emb_fwd(tables, bags, E)
+        ops.interact_fwd((feat,), D, 0, R["two"])
+    kernels = {
+        FWD_FUSED: lambda: ops.interact_fwd_gather_narrow(x, tables, bags, D, 0, R["fused"]),
+        FWD_TWO: two_fwd,
+        FWD_LOOKUP: lambda: ops.emb_fwd(tables, bags, E),
+        BWD_FUSED: lambda: ops.interact_bwd_gather_narrow(x, tables, bags, D, mode, dR, *G["fused"]),
+        BWD_TWO: lambda: ops.interact_bwd((x, E), D, mode, dR, G["two"]),
+    }
+    # the results the timed kernels compute are the same bits
+    for fn in kernels.values():
+        fn()
+    ops.check_index_errors(sync=True)
+    if not same_bits(R["fused"], R["two"]) or not same_bits(G["fused"][0], G["two"][0]) or not same_bits(G["fused"][1], G["two"][1]):
+        sys.exit("ERROR: %s: the fused narrow kernels and the two-kernel form differ" % name)
+    for _ in range(args.warmup):
+        for fn in kernels.values():
+            fn()
+    ops.check_index_errors(sync=True)
+    times = {k: [] for k in kernels}
+    for _ in range(args.repeats):
+        for k, fn in kernels.items():
+            times[k].append(time_ms(fn))
+    ops.check_index_errors(sync=True)
+    sel = 2 * B * T * 8
+    xb, rb, buf = B * D * 4, B * ldr * 4, B * T * D * 4
+    grads = xb + buf                          # dx + dE
+    total = {
+        FWD_FUSED: sel + buf + xb + rb,       # (the table rows read are as many bytes as the buffer)
+        FWD_TWO: sel + buf + 2 * buf + xb + rb,
+        FWD_LOOKUP: sel + buf + buf,
+        BWD_FUSED: sel + buf + xb + rb + grads,
+        BWD_TWO: buf + xb + rb + grads,
+    }
+    lines.append("")
+    lines.append("### %s: %d tables (%.1f M rows, at most %d per table), D = %d, B = %d, one lookup per bag, int64 ids" %
+                 (name, T, sum(rows) / 1e6, max(rows), D, B))
+    lines.append("")
+    lines.append("| kernel | median ms | min | max | algorithmic MB | GB/s |")
+    lines.append("|---|---|---|---|---|---|")
+    med = {}
+    for k, ts in times.items():
+        med[k] = statistics.median(ts)
+        lines.append("| %s | %.4f | %.4f | %.4f | %.1f | %.0f |" % (k, med[k], min(ts), max(ts), total[k] / 1e6, total[k] / med[k] / 1e6))
+    lines.append("")
+    for what, f, t in (("forward", med[FWD_FUSED], med[FWD_TWO]), ("backward", med[BWD_FUSED], med[BWD_TWO])):
+        lines.append("%s: fused %.4f ms, two-kernel form %.4f ms (fused is %.2fx %s)" %
+                     (what, f, t, t / f if f <= t else f / t, "faster" if f < t else "SLOWER"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--max-rows", type=int, default=10_000_000, help="cap of every table's row count")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("ERROR: tools/bench_narrow_interact.py measures on the GPU; none found")
+    import bench
+    dev = torch.device("cuda:0")
+    lines = ["GPU: %s; torch %s; %d repeats after %d warm-up rounds, HIP events, median; all kernels in one process, alternating inside every round" %
+             (torch.cuda.get_device_name(0), torch.__version__, args.repeats, args.warmup)]
+    g = torch.Generator(device=dev).manual_seed(7)
+    for workload, D in (("criteo_terabyte", 64), ("criteo_kaggle", 16)):
+        tables = make_tables([min(n, args.max_rows) for n in bench.WORKLOADS[workload]["rows"]], D, dev, g)
+        for B in (2048, 65536):
+            run_shape("%s rows" % workload, tables, D, B, args, dev, lines, g)
+        del tables
+        torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
