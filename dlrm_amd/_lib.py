@@ -74,6 +74,8 @@ SIGNATURES = {
     "dlrm_emb_adagrad_workspace_bytes": (_i64, [_i32, _i32, _pi64, _pi64]),
     "dlrm_emb_bwd_rowwise_adagrad": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32,
                                             _vp, _i64, _f32, _vp, _f32, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_bwd_adagrad": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32,
+                                    _vp, _i64, _f32, _vp, _f32, _vp, _i64, _vp, _vp]),
     "dlrm_emb_fwd_bf16": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp]),
     "dlrm_emb_fwd_bf16_pred": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dlrm_interact_gather_bf16_ok": (_i32, [_i32, _i32]),

@@ -1,4 +1,4 @@
-// adagrad.hip — K4: fused EmbeddingBag backward + row-wise sparse Adagrad, and the dense Adagrad step.
+// adagrad.hip — K4: fused EmbeddingBag backward + row-wise sparse Adagrad, its exact (per-element) twin, and the dense Adagrad step.
 //
 // Reference replaced: autograd EmbeddingBagBackward (sparse COO gradient) followed by RWSAdagrad.step's sparse
 // branch (optim/rwsadagrad.py:117-143): coalesce the gradient (duplicates of a row summed), then per touched row r
@@ -15,6 +15,11 @@
 //           run's end by binary search in the sorted keys, adds the edge partials in order and applies the update.
 // Every sum has a fixed order: results are run-to-run deterministic (hot rows are re-associated per 64 lookups
 // relative to the reference's strictly sequential coalesce).
+//
+// EXACT = true (dlrm_emb_bwd_adagrad) is torch.optim.Adagrad's sparse branch (the reference's --optimizer=adagrad,
+// dlrm_s_pytorch.py:1343-1369) over the same walk: the accumulator is torch's state["sum"], [rows, D], and per touched row, per column
+//     sum[r,d] += g_r[d]^2;   W[r,d] -= clr * g_r[d] / (sqrt(sum[r,d]) + eps)
+// Sort, groups, edge buffers and fix-up ownership are the row-wise kernels' (one template, a flag): g_r has the same bits in both.
 #include <stdlib.h>
 #include "sorted_common.h"
 
@@ -24,7 +29,7 @@ constexpr int kG = 64;          // sorted entries per lane group
 // kC = gradient rows in flight per lane group: template parameter (env DLRM_ADAGRAD_KC, default 4)
 
 struct AdagradArgs {
-    float* state[DLRM_MAX_TABLES_PER_LAUNCH];      // row-wise accumulator ("momentum") of each table, [rows]
+    float* state[DLRM_MAX_TABLES_PER_LAUNCH];      // row-wise accumulator ("momentum") of each table, [rows]; EXACT: state["sum"], [rows, D]
 };
 
 __device__ __forceinline__ float4 v_add(const float4& a, const float4& b) {
@@ -42,12 +47,47 @@ __device__ __forceinline__ void v_step(float4& w, float nclr_over_denom, const f
     w.z = __builtin_fmaf(nclr_over_denom, g.z, w.z); w.w = __builtin_fmaf(nclr_over_denom, g.w, w.w);
 }
 
+// EXACT: s = sum + g*g in two roundings (torch: state_sum.add_(grad.pow(2)), no fma), then the row-wise / dense kernels' form of the step.
+// (hipcc's __fmul_rn / __fadd_rn are plain * and +, which -ffp-contract=fast fuses into one fma: the pragma is what keeps them apart)
+__device__ __forceinline__ void v_exact_step(float& w, float& s, const float& g, float clr, float eps) {
+    {
+#pragma clang fp contract(off)
+        const float gg = g * g;
+        s = s + gg;
+    }
+    w = __builtin_fmaf(-clr, g / (sqrtf(s) + eps), w);
+}
+__device__ __forceinline__ void v_exact_step(float4& w, float4& s, const float4& g, float clr, float eps) {
+    v_exact_step(w.x, s.x, g.x, clr, eps); v_exact_step(w.y, s.y, g.y, clr, eps);
+    v_exact_step(w.z, s.z, g.z, clr, eps); v_exact_step(w.w, s.w, g.w, clr, eps);
+}
+
 // mom[row] += mean(g^2); W[row,:] = fma(-clr, g / (sqrt(mom[row]) + eps), W[row,:]).  Called by all LPB lanes of a
 // lane group together (same control flow), `acc` = the lane's columns of the row's coalesced gradient.
-template <int VEC, int LPB, int NCH>
+// EXACT: mom_r is the row of the [rows, D] accumulator; a lane owns the same columns of W, sum and g (no cross-lane step) and requests
+// all of its W and sum vectors before any arithmetic.
+template <int VEC, int LPB, int NCH, bool EXACT>
 __device__ __forceinline__ void adagrad_apply(float* __restrict__ wrow, float* __restrict__ mom_r, int D, int lig,
                                               const typename Vec<VEC>::T (&acc)[NCH], float clr, float eps) {
     using VT = typename Vec<VEC>::T;
+    if constexpr (EXACT) {
+        VT w[NCH], s[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int col = (c * LPB + lig) * VEC;
+            if (col < D) { v_gload(w[c], wrow + col); v_gload(s[c], mom_r + col); }
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int col = (c * LPB + lig) * VEC;
+            if (col < D) {
+                v_exact_step(w[c], s[c], acc[c], clr, eps);
+                v_gstore(wrow + col, w[c]);
+                v_gstore(mom_r + col, s[c]);
+            }
+        }
+        return;
+    }
     float sq = 0.f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -93,7 +133,7 @@ template <> __device__ __forceinline__ unsigned long long group_bcast<unsigned l
 }
 template <> __device__ __forceinline__ float group_bcast<float>(float v, int src_lane) { return __shfl(v, src_lane, 64); }
 
-template <int VEC, int LPB, int NCH, typename KT, int kC>
+template <int VEC, int LPB, int NCH, typename KT, int kC, bool EXACT>
 __global__ __launch_bounds__(256) void adagrad_groups_kernel(SortedArgs sa, AdagradArgs aa, long long L, int D, int row_bits,
                                                              const KT* __restrict__ keys, const unsigned* __restrict__ vals,
                                                              const unsigned* __restrict__ bag_of,
@@ -169,7 +209,7 @@ __global__ __launch_bounds__(256) void adagrad_groups_kernel(SortedArgs sa, Adag
         } else {
             const int t = (int)(run_key >> row_bits);
             const long long row = (long long)(run_key & row_mask);
-            adagrad_apply<VEC, LPB, NCH>((float*)s_w[t] + row * D, (float*)s_state[t] + row, D, lig, acc, clr, eps);
+            adagrad_apply<VEC, LPB, NCH, EXACT>((float*)s_w[t] + row * D, (float*)s_state[t] + row * (EXACT ? D : 1), D, lig, acc, clr, eps);
         }
     };
 
@@ -224,7 +264,7 @@ __global__ __launch_bounds__(256) void adagrad_groups_kernel(SortedArgs sa, Adag
 }
 
 // one lane group per group index: acts only where a run starts in this group and continues into the next one
-template <int VEC, int LPB, int NCH, typename KT>
+template <int VEC, int LPB, int NCH, typename KT, bool EXACT>
 __global__ __launch_bounds__(256) void adagrad_fixup_kernel(SortedArgs sa, AdagradArgs aa, long long L, int D, int row_bits,
                                                             const KT* __restrict__ keys, DlrmStep clr_, float eps,
                                                             const float* __restrict__ edge_first,
@@ -268,7 +308,7 @@ __global__ __launch_bounds__(256) void adagrad_fixup_kernel(SortedArgs sa, Adagr
     const KT row_mask = (((KT)1) << row_bits) - 1;
     const int t = (int)(key >> row_bits);
     const long long row = (long long)(key & row_mask);
-    adagrad_apply<VEC, LPB, NCH>(sa.w[t] + row * D, aa.state[t] + row, D, lig, acc, clr, eps);
+    adagrad_apply<VEC, LPB, NCH, EXACT>(sa.w[t] + row * D, aa.state[t] + row * (EXACT ? D : 1), D, lig, acc, clr, eps);
 }
 
 struct Shape { int vec, lpb, nch, dp; };
@@ -307,7 +347,7 @@ static int ada_layout(size_t L, bool wide, int key_bits, int D, AdaLayout* lo, i
     return 0;
 }
 
-template <typename KT>
+template <typename KT, bool EXACT>
 static int run_adagrad(int n, const int* ids, int64_t B, int D, void* const* weight_host, void* const* state_host,
                        const int64_t* rows_host, const void* const* indices_host, const void* const* offsets_host,
                        const int64_t* nnz_host, const void* const* psw_host, int idx_bits, const float* dout, int64_t dout_ld,
@@ -335,16 +375,18 @@ static int run_adagrad(int n, const int* ids, int64_t B, int D, void* const* wei
     dim3 grid((unsigned)((groups + gpb - 1) / gpb), 1, 1), block(256);
 #define ADA(V, LP, NC)                                                                                                         \
     do {                                                                                                                       \
-        if (kc == 1) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 1>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
+        if constexpr (EXACT) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 2, true>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
+                           vals, bag_of, dout, (long long)dout_ld, clr, eps, ef, el);   /* (the exact update is built for the default kC only) */ \
+        else if (kc == 1) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 1, false>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
                            vals, bag_of, dout, (long long)dout_ld, clr, eps, ef, el);                                          \
-        else if (kc == 2) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 2>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
+        else if (kc == 2) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 2, false>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
                            vals, bag_of, dout, (long long)dout_ld, clr, eps, ef, el);                                          \
-        else if (kc == 8) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, (LP >= 8 ? 8 : 4)>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
+        else if (kc == 8) hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, (LP >= 8 ? 8 : 4), false>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
                            vals, bag_of, dout, (long long)dout_ld, clr, eps, ef, el);                                          \
-        else hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 4>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
+        else hipLaunchKernelGGL((adagrad_groups_kernel<V, LP, NC, KT, 4, false>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys, \
                            vals, bag_of, dout, (long long)dout_ld, clr, eps, ef, el);                                          \
         DLRM_LAUNCH_CHECK();                                                                                                   \
-        hipLaunchKernelGGL((adagrad_fixup_kernel<V, LP, NC, KT>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys,  \
+        hipLaunchKernelGGL((adagrad_fixup_kernel<V, LP, NC, KT, EXACT>), grid, block, 0, st, sa, aa, (long long)L, D, row_bits, keys,  \
                            clr, eps, (const float*)ef, (const float*)el);                                                      \
         DLRM_LAUNCH_CHECK();                                                                                                   \
     } while (0)
@@ -392,12 +434,16 @@ extern "C" int64_t dlrm_emb_adagrad_workspace_bytes(int T, int D, const int64_t*
     return (int64_t)worst;
 }
 
-extern "C" int dlrm_emb_bwd_rowwise_adagrad(int T, int64_t B, int D, void* const* weight_host,
-                                            void* const* state_host, const int64_t* rows_host,
-                                            const void* const* indices_host, const void* const* offsets_host,
-                                            const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
-                                            const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
-                                            void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
+namespace {
+
+// both entry points: EXACT picks the accumulator layout and the apply step, `name` is the caller's symbol (messages)
+template <bool EXACT>
+static int emb_bwd_adagrad_any(const char* name, int T, int64_t B, int D, void* const* weight_host,
+                               void* const* state_host, const int64_t* rows_host,
+                               const void* const* indices_host, const void* const* offsets_host,
+                               const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                               const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
+                               void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0 || !weight_host || !state_host || !rows_host || !indices_host || !offsets_host || !nnz_host ||
         !dout || dout_ld < (int64_t)T * D)
         return DLRM_E_ARG;
@@ -407,6 +453,7 @@ extern "C" int dlrm_emb_bwd_rowwise_adagrad(int T, int64_t B, int D, void* const
     for (int t = 0; t < T; ++t) {
         if (!weight_host[t] || !state_host[t]) return DLRM_E_ARG;
         vec_ok = vec_ok && dlrm_aligned16(weight_host[t]);
+        if (EXACT) vec_ok = vec_ok && dlrm_aligned16(state_host[t]);      // (a lane loads its columns of the [rows, D] accumulator as one vector)
     }
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
@@ -424,20 +471,46 @@ extern "C" int dlrm_emb_bwd_rowwise_adagrad(int T, int64_t B, int D, void* const
         int rc = ada_layout(L, wide, key_bits, D, &lo, n, nnz_host + t0, rows_host + t0);
         if (rc) return rc;
         if (!workspace || !dlrm_aligned16(workspace) || (size_t)workspace_bytes < lo.total) {
-            fprintf(stderr, "libdlrm_hip: dlrm_emb_bwd_rowwise_adagrad: workspace too small (%lld < %zu bytes)\n",
+            fprintf(stderr, "libdlrm_hip: %s: workspace too small (%lld < %zu bytes)\n", name,
                     (long long)workspace_bytes, lo.total);
             return DLRM_E_ARG;
         }
-        rc = wide ? run_adagrad<unsigned long long>(n, ids, B, D, weight_host, state_host, rows_host, indices_host, offsets_host,
+        rc = wide ? run_adagrad<unsigned long long, EXACT>(n, ids, B, D, weight_host, state_host, rows_host, indices_host, offsets_host,
                                                     nnz_host, psw_host, idx_bits, dout, dout_ld, dlrm_step_pos(lr, lr_dev), eps, (char*)workspace, lo, L,
                                                     row_bits, key_bits, vec_ok, st, err)
-                  : run_adagrad<unsigned>(n, ids, B, D, weight_host, state_host, rows_host, indices_host, offsets_host, nnz_host,
+                  : run_adagrad<unsigned, EXACT>(n, ids, B, D, weight_host, state_host, rows_host, indices_host, offsets_host, nnz_host,
                                           psw_host, idx_bits, dout, dout_ld, dlrm_step_pos(lr, lr_dev), eps, (char*)workspace, lo, L, row_bits, key_bits,
                                           vec_ok, st, err);
         if (rc) return rc;
     }
     return 0;
 }
+
+}  // namespace
+
+#define DLRM_ADAGRAD_ARGS                                                                                                      \
+    T, B, D, weight_host, state_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, idx_bits, dout, dout_ld, lr, \
+        lr_dev, eps, workspace, workspace_bytes, err, stream
+
+extern "C" int dlrm_emb_bwd_rowwise_adagrad(int T, int64_t B, int D, void* const* weight_host,
+                                            void* const* state_host, const int64_t* rows_host,
+                                            const void* const* indices_host, const void* const* offsets_host,
+                                            const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                                            const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
+                                            void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
+    return emb_bwd_adagrad_any<false>("dlrm_emb_bwd_rowwise_adagrad", DLRM_ADAGRAD_ARGS);
+}
+
+// state_host[t]: torch's state["sum"] of table t, contiguous fp32 [rows_host[t], D]
+extern "C" int dlrm_emb_bwd_adagrad(int T, int64_t B, int D, void* const* weight_host,
+                                    void* const* state_host, const int64_t* rows_host,
+                                    const void* const* indices_host, const void* const* offsets_host,
+                                    const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                                    const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
+                                    void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
+    return emb_bwd_adagrad_any<true>("dlrm_emb_bwd_adagrad", DLRM_ADAGRAD_ARGS);
+}
+#undef DLRM_ADAGRAD_ARGS
 
 extern "C" int dlrm_adagrad_dense(int64_t n, float* w, float* sum, const float* g, float lr, const float* lr_dev, float eps, void* stream) {
     if (n <= 0 || !w || !sum || !g) return DLRM_E_ARG;

@@ -346,6 +346,11 @@ class DLRM_Net(nn.Module):
     # of sequential_forward under the fp32 branch's conditions and runs csrc/interact_narrow.hip (forward and backward) instead of dlrm_emb_fwd
     # + the generic interaction kernels through the pooled [B, T*D] buffer — the same bits.  Off: such a model runs exactly the two-kernel form.
     fuse_narrow_interact = False
+    # opt-in (launcher: --fused-adagrad): a stock torch.optim.Adagrad that owns the tables (the reference's --optimizer=adagrad) gets the fused
+    # exact Adagrad update (csrc/adagrad.hip dlrm_emb_bwd_adagrad) on ITS state[p]["sum"], the step pre-hook advances the tables'
+    # state[p]["step"], and the dense parameters stay with torch's own step.  Off: such an optimizer takes the sparse COO gradient, as before.
+    # (dlrm_amd.optim.FusedAdagrad takes the fused update either way.)
+    fused_adagrad = False
     quantize_mlp_bits = 32      # 8 / 16 after quantize_mlp()
 
     # ---------------------------------------------------------------- parameter construction
@@ -967,7 +972,18 @@ class DLRM_Net(nn.Module):
                 continue
             # parked backward passes over THESE tables (`weights` is a fresh tuple per forward call: compare the tables themselves)
             key = tuple(id(w) for w in weights)
-            plan = _embedding_update_plan(optimizer, weights, count=sum(1 for p_ in pending if tuple(id(w) for w in p_[0]) == key))
+            if _is_exact_adagrad(optimizer, self.fused_adagrad) and self._owned_by(optimizer):
+                # (asked in front of the plan, which advances state["step"])
+                if self.emb_bf16 is not None:
+                    sys.exit("ERROR: the fused exact Adagrad update is not built for bfloat16 embedding tables; use SGD or row-wise Adagrad")
+                if self._has_qr(self.emb_l):
+                    sys.exit("ERROR: the fused exact Adagrad update is not built for QR embedding tables; use SGD, or set "
+                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
+                if self._has_md(self.emb_l):
+                    sys.exit("ERROR: the fused exact Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
+                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
+            plan = _embedding_update_plan(optimizer, weights, count=sum(1 for p_ in pending if tuple(id(w) for w in p_[0]) == key),
+                                          fused_adagrad=self.fused_adagrad)
             if plan is None:
                 self._pending_emb.append((weights, bags, dout, None))   # another optimizer owns these tables
             elif plan[0] == "coo":
@@ -977,6 +993,9 @@ class DLRM_Net(nn.Module):
                 self._materialize_coo_grads(weights, bags, dout)  # the optimizer's own step consumes .grad right after this hook
             elif plan[0] == "sgd":
                 self._sgd_update(weights, bags, dout, plan[1])
+            elif plan[0] == "adagrad":
+                _, clr, eps, sums = plan
+                ops.emb_bwd_adagrad(weights, sums, bags, dout, clr, eps)
             else:
                 if self._has_qr(self.emb_l):
                     sys.exit("ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
@@ -1270,11 +1289,24 @@ def _is_rwsadagrad(optimizer) -> bool:
         all(k in d for k in ("lr", "lr_decay", "eps", "initial_accumulator_value"))
 
 
-def _embedding_update_plan(optimizer, weights, count=1):
+def _is_exact_adagrad(optimizer, fused_adagrad=False) -> bool:
+    """dlrm_amd.optim.FusedAdagrad, or — only with DLRM_Net.fused_adagrad — a stock torch.optim.Adagrad (the reference's --optimizer=adagrad)."""
+    d = getattr(optimizer, "defaults", {})
+    if not all(k in d for k in ("lr", "lr_decay", "eps", "initial_accumulator_value")):
+        return False
+    if type(optimizer).__name__ == "FusedAdagrad":
+        return True
+    return bool(fused_adagrad) and type(optimizer) is torch.optim.Adagrad and \
+        not any(g.get("maximize", False) for g in optimizer.param_groups)
+
+
+def _embedding_update_plan(optimizer, weights, count=1, fused_adagrad=False):
     """None if `optimizer` does not own the tables; ("sgd", lr) for torch.optim.SGD; ("rwsadagrad", clr, eps, states)
     for RWSAdagrad — `states` are the per-table row-wise accumulators kept in optimizer.state[p]["momentum"] exactly
     where the reference keeps them (created lazily with initial_accumulator_value, rwsadagrad.py:89-95), the step count
-    in state[p]["step"] (clr = lr / (1 + (step-1)*lr_decay), :113-115); ("coo",) for every other optimizer (and SGD with
+    in state[p]["step"] (clr = lr / (1 + (step-1)*lr_decay), :113-115); ("adagrad", clr, eps, sums) for FusedAdagrad and,
+    with `fused_adagrad` (DLRM_Net.fused_adagrad), for a stock torch.optim.Adagrad — `sums` are the optimizer's own
+    state[p]["sum"] tensors ([rows, D]), clr and the step count as for RWSAdagrad; ("coo",) for every other optimizer (and SGD with
     momentum / weight decay): the sparse COO gradient is materialised and the optimizer's own step consumes it, as in
     the reference.  `count` = parked backward passes of these tables (gradient accumulation)."""
     if optimizer is None:
@@ -1288,29 +1320,33 @@ def _embedding_update_plan(optimizer, weights, count=1):
         return None
     if any(g is None for g in groups):
         sys.exit("ERROR: optimizer holds only some of the embedding tables")
-    if _is_rwsadagrad(optimizer):
+    exact = _is_exact_adagrad(optimizer, fused_adagrad)
+    if exact or _is_rwsadagrad(optimizer):
         if count > 1:
             # the reference coalesces the ACCUMULATED gradient and applies one non-linear update / one step increment;
             # several separate fused updates would not equal that
-            sys.exit("ERROR: gradient accumulation (more than one backward per optimizer step) with the fused row-wise "
-                     "Adagrad update is not supported; set model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0)")
+            sys.exit("ERROR: gradient accumulation (more than one backward per optimizer step) with the fused %s "
+                     "Adagrad update is not supported; set model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0)" %
+                     ("exact" if exact else "row-wise"))
+        if any(g.get("weight_decay", 0) != 0 for g in groups):
+            sys.exit("ERROR: weight_decay option is not compatible with sparse gradients")
+        # the accumulator: torch's state["sum"], the shape of the table (exact) | the reference's state["momentum"], [rows] (row-wise)
+        name = "sum" if exact else "momentum"
         clrs, states = [], []
         for w, g in zip(weights, groups):
-            if g.get("weight_decay", 0) != 0:
-                sys.exit("ERROR: weight_decay option is not compatible with sparse gradients")
             st = optimizer.state[w]
-            if "momentum" not in st or st["momentum"].device != w.device:
-                st["momentum"] = torch.full([w.shape[0]], float(optimizer.defaults["initial_accumulator_value"]),
-                                            dtype=torch.float32, device=w.device)
-            st["step"] = st.get("step", 0) + 1
-            clrs.append(float(g["lr"]) / (1.0 + (st["step"] - 1.0) * float(g["lr_decay"])))
-            states.append(st["momentum"])
+            if name not in st or (not exact and st[name].device != w.device):
+                st[name] = torch.full(list(w.shape) if exact else [w.shape[0]], float(optimizer.defaults["initial_accumulator_value"]),
+                                      dtype=torch.float32, device=w.device)
+            st["step"] = st.get("step", 0) + 1          # (a python number, or torch.optim.Adagrad's host tensor)
+            clrs.append(float(g["lr"]) / (1.0 + (float(st["step"]) - 1.0) * float(g["lr_decay"])))
+            states.append(st[name])
         if len(set(clrs)) != 1 or len({float(g["eps"]) for g in groups}) != 1:
             sys.exit("ERROR: embedding tables in param groups with different learning rates are not supported")
         clr = clrs[0]
         if float(groups[0]["lr_decay"]) == 0.0:
             clr = ops.device_lr(groups[0], clr)          # clr == lr: the group's device scalar while a whole-step graph captures (graph.py)
-        return ("rwsadagrad", clr, float(groups[0]["eps"]), states)
+        return ("adagrad" if exact else "rwsadagrad", clr, float(groups[0]["eps"]), states)
     if not isinstance(optimizer, torch.optim.SGD):
         return ("coo",)
     for g in groups:

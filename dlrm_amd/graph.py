@@ -111,6 +111,9 @@ class GraphedTrainStep:
             sys.exit("ERROR: GraphedTrainStep is not built for mixed-dimension embedding tables (their backward builds the per-width bag lists per step)")
         if getattr(model, "emb_bf16", None) is not None:
             sys.exit("ERROR: GraphedTrainStep is not built for bfloat16 embedding tables (the per-step rounding seed would be baked into the capture)")
+        if type(optimizer).__name__ == "FusedAdagrad" or (getattr(model, "fused_adagrad", False) and type(optimizer) is torch.optim.Adagrad):
+            sys.exit("ERROR: GraphedTrainStep is not built for the fused exact Adagrad update (FusedAdagrad, or torch.optim.Adagrad with "
+                     "model.fused_adagrad); use the eager step")
         self.model, self.optimizer = model, optimizer
         for g in optimizer.param_groups:
             # a decaying step size (RWSAdagrad: clr = lr / (1 + (step - 1) * lr_decay)) is computed on the host at capture time

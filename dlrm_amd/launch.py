@@ -105,6 +105,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--narrow-fuse-interact", action="store_true",
                     help="plain fp32 tables of --arch-sparse-feature-size 16 / 32 / 64: fetch the rows inside the interaction kernels, forward "
                          "and backward (DLRM_Net.fuse_narrow_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer)")
+    ap.add_argument("--fused-adagrad", action="store_true",
+                    help="with the reference's --optimizer=adagrad: update the embedding tables with the fused exact Adagrad kernel on "
+                         "torch.optim.Adagrad's own state (DLRM_Net.fused_adagrad; no sparse COO gradient, the dense parameters stay with "
+                         "torch's step); not built for bfloat16, QR or mixed-dimension tables")
     return ap
 
 
@@ -131,6 +135,9 @@ def main(argv=None) -> None:
     if a.narrow_fuse_interact:
         import dlrm_amd
         dlrm_amd.DLRM_Net.fuse_narrow_interact = True      # every model run() builds from here on (other widths and table kinds ignore it)
+    if a.fused_adagrad:
+        import dlrm_amd
+        dlrm_amd.DLRM_Net.fused_adagrad = True             # every model run() builds from here on (other optimizers ignore it)
     sys.argv = [os.path.join(a.reference, "dlrm_s_pytorch.py")] + ref_args
     ref.run()
 

@@ -886,6 +886,36 @@ def emb_bwd_rowwise_adagrad(weights: Sequence[torch.Tensor], states: Sequence[to
     _lib.check(rc, "dlrm_emb_bwd_rowwise_adagrad")
 
 
+def emb_bwd_adagrad(weights: Sequence[torch.Tensor], sums: Sequence[torch.Tensor], bags: BagBatch,
+                    dout: torch.Tensor, lr: LrLike, eps: float) -> None:
+    """Fused EmbeddingBag backward + exact sparse Adagrad (torch.optim.Adagrad's sparse branch, the reference's --optimizer=adagrad), in
+    place: per touched row r:  g_r = sum of its lookups' gradients (the order and bits of emb_bwd_rowwise_adagrad);
+    sums[t][r] += g_r^2;  W_t[r] -= lr * g_r / (sqrt(sums[t][r]) + eps), per element.  `sums[t]` is torch's state["sum"] of table t:
+    fp32, contiguous, the shape of the table.  `lr` is the decayed clr."""
+    lib = _lib.load()
+    D, wp, rows = _weights_desc(weights)
+    _req(dout, "dout", ndim=2)
+    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T or len(sums) != bags.T:
+        raise RuntimeError("dlrm_amd: emb_bwd_adagrad shape mismatch")
+    for s_, w in zip(sums, weights):
+        # (the kernel writes sums[t][row, 0:D] for every looked-up row: any other layout is an out-of-bounds device write)
+        _req(s_, "adagrad sum", ndim=2)
+        if tuple(s_.shape) != tuple(w.shape) or not s_.is_contiguous() or s_.device != w.device:
+            raise RuntimeError("dlrm_amd: adagrad sum must be a contiguous [rows, D] tensor on its table's device")
+    sp = _lib.ptr_array([s_.data_ptr() for s_ in sums])
+    need = lib.dlrm_emb_adagrad_workspace_bytes(bags.T, D, bags._nnz, rows)
+    if need < 0:
+        raise RuntimeError("dlrm_amd: dlrm_emb_adagrad_workspace_bytes failed")
+    ws = _scratch("emb", need, dout.device)
+    lr_v, lr_p = _lr_args(lr)
+    with _timed("emb_bwd_adagrad"):
+        rc = lib.dlrm_emb_bwd_adagrad(bags.T, bags.B, D, wp, sp, rows, bags._idx, bags._off, bags._nnz,
+                                      bags._psw, bags.idx_bits, C.c_void_p(dout.data_ptr()), _ld(dout),
+                                      lr_v, lr_p, float(eps), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                      None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
+    _lib.check(rc, "dlrm_emb_bwd_adagrad")
+
+
 # ---- bfloat16 embedding tables: csrc/emb_bf16.hip.  Tables are torch.bfloat16 [rows, D]; the feature buffer, the gradient, the Adagrad
 # accumulators and every sum stay fp32.  An update rounds each touched row ONCE: "nearest" (even) or "stochastic" (Philox4x32-10 keyed by
 # `seed`: the same seed gives the same bits; the host restatement is tests/test_bf16_emb_host.py).

@@ -277,6 +277,23 @@ int dlrm_emb_bwd_rowwise_adagrad(int T, int64_t B, int D,
                      const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
                      void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
 
+/* K4, exact: fused EmbeddingBag backward + torch.optim.Adagrad's sparse branch (the reference's --optimizer=adagrad,
+ * dlrm_s_pytorch.py:1343-1369).  Symbol added, the ABI version stays 17.  The operands of dlrm_emb_bwd_rowwise_adagrad, except
+ *   state_host[t] : device float* [rows_host[t], D], contiguous — torch's state["sum"] of table t.
+ * The same sort and the same walk: g_r is summed in the same order and has the same bits as in the row-wise call.  Per UNIQUE row r
+ * touched this step, per column d (fp32, IEEE sqrt and divide):
+ *     s         = sum[r,d] + g_r[d]*g_r[d]        (product rounded, then the sum: torch's state_sum.add_(grad.pow(2)), no fma)
+ *     W[r,d]    = fma(-lr, g_r[d] / (sqrt(s) + eps), W[r,d]);   sum[r,d] = s
+ * Rows no lookup names keep their bits in W and in sum.  Out-of-range ids are skipped (zero gradient) and reported through `err`.
+ * workspace: dlrm_emb_adagrad_workspace_bytes(...) bytes (the row-wise call's).  The 16-bytes-per-lane kernels also need every
+ * state_host[t] 16-byte aligned; otherwise the 4-bytes-per-lane ones run. */
+int dlrm_emb_bwd_adagrad(int T, int64_t B, int D,
+                     void* const* weight_host, void* const* state_host, const int64_t* rows_host,
+                     const void* const* indices_host, const void* const* offsets_host,
+                     const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                     const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
+                     void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
+
 /* bfloat16 embedding tables: csrc/emb_bf16.hip (symbols added, the ABI version stays 17).
  * Replaces: nothing in the reference — the 16-bit table storage of the torchrec / fbgemm path that BASELINE.json configs[4] restates.
  * A table is weight_host[t] : device uint16* [rows_host[t], D] of bfloat16 bit patterns (torch.bfloat16), 2-byte aligned at least.
