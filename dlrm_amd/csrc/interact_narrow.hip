@@ -50,38 +50,13 @@
 //   interact_bwd_narrow_kernel<64, 2, IT>      232 / 234                 32     92      0      95232 B   (one workgroup per CU)
 //   The launch keeps at most two workgroups (eight waves) per CU, so neither registers (512 per lane at one wave per SIMD, 256 at two) nor
 //   LDS limits any instantiation below what the grid asks for.
-#include "common.h"
+#include "gather_common.h"
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) char gchar;          // pointers rebuilt from integers: tag them global (global_*, not flat_* accesses)
-typedef __attribute__((address_space(1))) floatx4 gfloatx4;
 typedef __attribute__((address_space(1))) float gfloat;
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) floatx2 gfloatx2;
-
-// position of the pair (i, j), j <= i, in the flattened interaction output — as interact.hip: bit 0 = with the diagonal, bit 1 = torchrec order
-__device__ __forceinline__ int pair_pos(int i, int j, int F, int mode) {
-    if (mode & 2) return j * F - j * (j + 1) / 2 + (i - j - 1);
-    return ((mode & 1) ? i * (i + 1) / 2 : i * (i - 1) / 2) + j;
-}
-
-constexpr int NI_MAXF = 32;                 // feature slots of the argument block = the launch limit F <= 32
-constexpr unsigned NI_BAD = 0xFFFFFFFFu;    // row selector of an out-of-range id (tables have at most 0xFFFFFFFF rows: never a valid row)
-
-// feature f >= 1 is table f - 1; slot 0 is unused (feature 0 = x)
-struct NGatherArgs {
-    const void* w[NI_MAXF];                 // fp32 rows of D floats
-    const void* idx[NI_MAXF];
-    const void* off[NI_MAXF];               // bag starts: verified to be 0, 1, 2, ... (one lookup per bag)
-    long long   rows[NI_MAXF];
-    long long*  err;
-    DlrmPred    pred;
-};
-
-// fma(1, v, +0): dlrm_emb_fwd's element for a bag of one row without per-sample weights
-__device__ __forceinline__ float bag1(float v) { return __builtin_fmaf(1.0f, v, 0.f); }
 
 template <int D, int NB> struct NGeom {
     static constexpr int LPR = D / 4;                           // lanes per row
@@ -105,32 +80,6 @@ struct NLane {
     bool own;
 };
 
-template <typename IT>
-struct NSel { IT id, off; };
-
-template <typename IT, int NP>
-__device__ __forceinline__ NSel<IT> sel_load(const NLane<NP>& nl, long long s) {
-    NSel<IT> r; r.id = 0; r.off = 0;
-    if (nl.own) {
-        r.id = *(const __attribute__((address_space(1))) IT*)(nl.qsrc + s * (long long)sizeof(IT));
-        r.off = *(const __attribute__((address_space(1))) IT*)(nl.osrc + s * (long long)sizeof(IT));
-    }
-    return r;
-}
-
-// the owner lane's checks: a bad id selects the zero row, as dlrm_emb_fwd skips it
-template <typename IT, int NP>
-__device__ __forceinline__ unsigned sel_resolve(const NLane<NP>& nl, const NSel<IT>& sel, long long s, int lane, long long* err) {
-    unsigned idu = NI_BAD;
-    if (nl.own) {
-        const long long id = (long long)sel.id, o = (long long)sel.off;
-        if (o != s) dlrm_report_bad_index(err, lane - 1, -(o + 1), -1);                 // not a one-lookup-per-bag batch (rows = -1 marks it)
-        if (!dlrm_index_ok(id, nl.rows)) dlrm_report_bad_index(err, lane - 1, id, nl.rows);
-        else idu = (unsigned)id;
-    }
-    return idu;
-}
-
 // row loads of one sample into registers: NP passes, one 16-byte load each, nothing waits here
 template <int D, int NB, int NP>
 __device__ __forceinline__ void rows_issue(float4 (&v)[NP], const NLane<NP>& nl, unsigned idu, int lane) {
@@ -140,7 +89,7 @@ __device__ __forceinline__ void rows_issue(float4 (&v)[NP], const NLane<NP>& nl,
     for (int p = 0; p < G::NP; ++p) {
         const unsigned mine = (unsigned)__shfl((int)idu, (1 + G::RPP * p + rg) & 63, 64);      // (rows that are features are < 32: a lane of this wave)
         v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (nl.on[p] && mine != NI_BAD) {
+        if (nl.on[p] && mine != GC_BAD) {
             const floatx4 q = *(const gfloatx4*)(nl.base[p] + (unsigned long long)mine * (D * 4));      // 64-bit byte offset
             v[p] = make_float4(q.x, q.y, q.z, q.w);
         }
@@ -158,14 +107,6 @@ __device__ __forceinline__ void image_write(char* img, const float4 (&v)[NP], co
             *(float4*)(img + nl.wofs[p]) = make_float4(bag1(q.x), bag1(q.y), bag1(q.z), bag1(q.w));
         }
     }
-}
-
-// the kernarg tables into LDS with compile-time kernarg offsets (a lane-indexed read of a by-value struct would go to scratch)
-__device__ __forceinline__ void args_to_lds(const NGatherArgs& na, long long* tw, long long* tq, long long* to, long long* tr, int F) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int f = 1; f < NI_MAXF; ++f)
-        if (tid == f && f < F) { tw[f] = (long long)na.w[f]; tq[f] = (long long)na.idx[f]; to[f] = (long long)na.off[f]; tr[f] = na.rows[f]; }
 }
 
 template <int D, int NB, int NP>
@@ -190,7 +131,7 @@ __device__ __forceinline__ void lane_init(NLane<NP>& nl, const long long* tw, co
 // forward
 // -------------------------------------------------------------------------------------------
 template <int D, int NB, typename IT>          // NB = 16-row tiles of the image: 1 (F <= 16) or 2
-__global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(NGatherArgs na, const float* __restrict__ x, long long x_ld, long long B,
+__global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(GatherArgs na, const float* __restrict__ x, long long x_ld, long long B,
                                                                   int F, int self, float* __restrict__ R, long long ldr) {
     if (na.pred.skip()) return;                              // (the two-kernel form runs instead)
     using G = NGeom<D, NB>;
@@ -201,10 +142,10 @@ __global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(NGatherArgs na
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int W = __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6));
     long long* tw = (long long*)lds;
-    long long* tq = tw + NI_MAXF;
-    long long* to = tq + NI_MAXF;
-    long long* tr = to + NI_MAXF;
-    char* img0 = (char*)(tr + NI_MAXF) + (size_t)wave * 2 * IMGB;
+    long long* tq = tw + GC_MAXF;
+    long long* to = tq + GC_MAXF;
+    long long* tr = to + GC_MAXF;
+    char* img0 = (char*)(tr + GC_MAXF) + (size_t)wave * 2 * IMGB;
 
     args_to_lds(na, tw, tq, to, tr, F);
     for (int e = lane; e < 2 * IMGB / 16; e += 64) ((float4*)img0)[e] = make_float4(0.f, 0.f, 0.f, 0.f);      // rows F.. (and the pitch padding) stay zero
@@ -239,15 +180,15 @@ __global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(NGatherArgs na
     // prologue: the first sample's image, and the second sample's (checked) selectors
     unsigned idun;
     {
-        const unsigned idu = sel_resolve<IT, NP>(nl, sel_load<IT, NP>(nl, b), b, lane, na.err);
+        const unsigned idu = sel_resolve<IT>(nl, sel_load<IT>(nl, b), b, lane, na.err);
         float4 v[NP];
         rows_issue<D, NB>(v, nl, idu, lane);
         float4 xv = zero4;                                  // (not a ?: of two lvalues: that selects between ADDRESSES and puts zero4 into scratch)
         if (lane < G::LPR) xv = *(const float4*)(x + b * x_ld + 4 * lane);
         const long long s1 = b + b_stride;
-        const NSel<IT> sel1 = sel_load<IT, NP>(nl, s1 < B ? s1 : last);
+        const Sel<IT> sel1 = sel_load<IT>(nl, s1 < B ? s1 : last);
         image_write<D, NB>(img0, v, nl, xv, lane);
-        idun = s1 < B ? sel_resolve<IT, NP>(nl, sel1, s1, lane, na.err) : NI_BAD;
+        idun = s1 < B ? sel_resolve<IT>(nl, sel1, s1, lane, na.err) : GC_BAD;
     }
     int cur = 0;
     for (; b < B; b += b_stride) {
@@ -258,7 +199,7 @@ __global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(NGatherArgs na
         rows_issue<D, NB>(vn, nl, idun, lane);
         float4 xn = zero4;
         if (lane < G::LPR) xn = *(const float4*)(x + (s1 < B ? s1 : last) * x_ld + 4 * lane);
-        const NSel<IT> seln = sel_load<IT, NP>(nl, s2 < B ? s2 : last);
+        const Sel<IT> seln = sel_load<IT>(nl, s2 < B ? s2 : last);
 
         const char* my = img0 + cur * IMGB;
         // ---- fragments: row 16 r + li, columns 16 s + 4 g .. + 3 (interact_fwd_kernel's av / bv) ----
@@ -293,7 +234,7 @@ __global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(NGatherArgs na
         // the multiplication and IN FRONT of this sample's stores — vmcnt counts stores too, and a wait placed behind them would wait
         // for their acknowledgement; this way they drain beside the next sample's loads and MFMAs
         image_write<D, NB>(img0 + (cur ^ 1) * IMGB, vn, nl, xn, lane);
-        idun = s2 < B ? sel_resolve<IT, NP>(nl, seln, s2, lane, na.err) : NI_BAD;
+        idun = s2 < B ? sel_resolve<IT>(nl, seln, s2, lane, na.err) : GC_BAD;
 
         float* Rb = R + b * ldr;
 #pragma unroll
@@ -313,27 +254,8 @@ __global__ __launch_bounds__(256) void interact_fwd_narrow_kernel(NGatherArgs na
 // -------------------------------------------------------------------------------------------
 // backward: dT = (dZ + dZ^T) . T per sample (interact_bwd_kernel<NB>), T fetched from the tables
 // -------------------------------------------------------------------------------------------
-// the lane's share of a dR row: bytes [1024 c + 16 lane, +16), where they lie inside the first rowb bytes (rowb = 4 * roundup4(D + P) <= 4 ldr)
-template <int NC> struct DrRegs { float4 v[NC]; };
-template <int NC>
-__device__ __forceinline__ DrRegs<NC> dr_load(const float* __restrict__ row, int rowb, int lane) {
-    DrRegs<NC> d;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        d.v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (1024 * c + 16 * lane < rowb) d.v[c] = *(const float4*)((const char*)row + 1024 * c + 16 * lane);
-    }
-    return d;
-}
-template <int NC>
-__device__ __forceinline__ void dr_write(char* img, const DrRegs<NC>& d, int rowb, int lane) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (1024 * c + 16 * lane < rowb) *(float4*)(img + 1024 * c + 16 * lane) = d.v[c];
-}
-
 template <int D, int NB, typename IT>
-__global__ __launch_bounds__(256) void interact_bwd_narrow_kernel(NGatherArgs na, const float* __restrict__ x, long long x_ld, long long B,
+__global__ __launch_bounds__(256) void interact_bwd_narrow_kernel(GatherArgs na, const float* __restrict__ x, long long x_ld, long long B,
                                                                   int F, int self, const float* __restrict__ dR, long long ldr,
                                                                   float* __restrict__ dx, long long dx_ld, float* __restrict__ dE, long long dE_ld) {
     if (na.pred.skip()) return;
@@ -348,10 +270,10 @@ __global__ __launch_bounds__(256) void interact_bwd_narrow_kernel(NGatherArgs na
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int W = __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6));
     long long* tw = (long long*)lds;
-    long long* tq = tw + NI_MAXF;
-    long long* to = tq + NI_MAXF;
-    long long* tr = to + NI_MAXF;
-    char* img0 = (char*)(tr + NI_MAXF) + (size_t)wave * (2 * IMGB + 2 * DRB);
+    long long* tq = tw + GC_MAXF;
+    long long* to = tq + GC_MAXF;
+    long long* tr = to + GC_MAXF;
+    char* img0 = (char*)(tr + GC_MAXF) + (size_t)wave * (2 * IMGB + 2 * DRB);
     char* drow0 = img0 + 2 * IMGB;
 
     args_to_lds(na, tw, tq, to, tr, F);
@@ -409,17 +331,17 @@ __global__ __launch_bounds__(256) void interact_bwd_narrow_kernel(NGatherArgs na
     // prologue: the first sample's images, and the second sample's (checked) selectors
     unsigned idun;
     {
-        const unsigned idu = sel_resolve<IT, NP>(nl, sel_load<IT, NP>(nl, b), b, lane, na.err);
+        const unsigned idu = sel_resolve<IT>(nl, sel_load<IT>(nl, b), b, lane, na.err);
         float4 v[NP];
         rows_issue<D, NB>(v, nl, idu, lane);
         float4 xv = zero4;
         if (lane < G::LPR) xv = *(const float4*)(x + b * x_ld + 4 * lane);
         const DrRegs<NDR> d = dr_load<NDR>(dR + b * ldr, rowb, lane);
         const long long s1 = b + b_stride;
-        const NSel<IT> sel1 = sel_load<IT, NP>(nl, s1 < B ? s1 : last);
+        const Sel<IT> sel1 = sel_load<IT>(nl, s1 < B ? s1 : last);
         image_write<D, NB>(img0, v, nl, xv, lane);
         dr_write<NDR>(drow0, d, rowb, lane);
-        idun = s1 < B ? sel_resolve<IT, NP>(nl, sel1, s1, lane, na.err) : NI_BAD;
+        idun = s1 < B ? sel_resolve<IT>(nl, sel1, s1, lane, na.err) : GC_BAD;
     }
     int cur = 0;
     for (; b < B; b += b_stride) {
@@ -431,7 +353,7 @@ __global__ __launch_bounds__(256) void interact_bwd_narrow_kernel(NGatherArgs na
         float4 xn = zero4;
         if (lane < G::LPR) xn = *(const float4*)(x + n1 * x_ld + 4 * lane);
         const DrRegs<NDR> dn = dr_load<NDR>(dR + n1 * ldr, rowb, lane);
-        const NSel<IT> seln = sel_load<IT, NP>(nl, s2 < B ? s2 : last);
+        const Sel<IT> seln = sel_load<IT>(nl, s2 < B ? s2 : last);
 
         const char* my = img0 + cur * IMGB;
         const char* dr = drow0 + cur * DRB;
@@ -494,68 +416,39 @@ __global__ __launch_bounds__(256) void interact_bwd_narrow_kernel(NGatherArgs na
         // only now are the next sample's registers touched (see the forward kernel)
         image_write<D, NB>(img0 + (cur ^ 1) * IMGB, vn, nl, xn, lane);
         dr_write<NDR>(drow0 + (cur ^ 1) * DRB, dn, rowb, lane);
-        idun = s2 < B ? sel_resolve<IT, NP>(nl, seln, s2, lane, na.err) : NI_BAD;
+        idun = s2 < B ? sel_resolve<IT>(nl, seln, s2, lane, na.err) : GC_BAD;
         cur ^= 1;
     }
 }
 
-constexpr int NI_WAVES = 4;          // one per SIMD
-
 template <int D, int NB>
 constexpr size_t narrow_lds(bool bwd) {
-    return 4 * NI_MAXF * sizeof(long long) + (size_t)NI_WAVES * (2 * (size_t)NGeom<D, NB>::IMGB + (bwd ? 2 * (size_t)NGeom<D, NB>::DRB : 0));
+    return 4 * GC_MAXF * sizeof(long long) + (size_t)GC_WAVES * (2 * (size_t)NGeom<D, NB>::IMGB + (bwd ? 2 * (size_t)NGeom<D, NB>::DRB : 0));
 }
-// workgroups of one pass: 256 CUs x min(2, workgroups whose LDS fits a CU); a wave takes one sample per pass.
-// (The D = 64, NB = 2 backward needs 93 KiB: one workgroup per CU.  Three-wave workgroups, of which two fit a CU, were measured SLOWER: 0.635 ms
-// against 0.462 ms for the two-kernel form, where the four-wave launch has 0.515 against 0.464 ms — profiles/narrow_interact/fused_rates.md.)
-long long narrow_grid(long long B, size_t lds) {
-    const long long per_cu = (160 * 1024) / (long long)lds >= 2 ? 2 : 1;
-    long long nb = (B + NI_WAVES - 1) / NI_WAVES;
-    if (nb > 256 * per_cu) nb = 256 * per_cu;
-    return nb;
-}
-
+// (The grid rule keeps the D = 64, NB = 2 backward, which needs 93 KiB, at one workgroup per CU.  Three-wave workgroups, of which two fit a CU,
+// were measured SLOWER: 0.635 ms against 0.462 ms for the two-kernel form, where the four-wave launch has 0.515 against 0.464 ms —
+// profiles/narrow_interact/fused_rates.md.)
 template <int D, int NB, typename IT>
-void launch_fwd(const NGatherArgs& na, const float* x, long long x_ld, long long B, int F, int self, float* R, long long ldr, hipStream_t st) {
+void launch_fwd(const GatherArgs& na, const float* x, long long x_ld, long long B, int F, int self, float* R, long long ldr, hipStream_t st) {
     constexpr size_t lds = narrow_lds<D, NB>(false);
     (void)hipFuncSetAttribute((const void*)interact_fwd_narrow_kernel<D, NB, IT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((interact_fwd_narrow_kernel<D, NB, IT>), dim3((unsigned)narrow_grid(B, lds)), dim3(64 * NI_WAVES), lds, st, na, x, x_ld,
+    hipLaunchKernelGGL((interact_fwd_narrow_kernel<D, NB, IT>), dim3((unsigned)gather_grid(B, lds)), dim3(64 * GC_WAVES), lds, st, na, x, x_ld,
                        B, F, self, R, ldr);
 }
 
 template <int D, int NB, typename IT>
-void launch_bwd(const NGatherArgs& na, const float* x, long long x_ld, long long B, int F, int self, const float* dR, long long ldr, float* dx,
+void launch_bwd(const GatherArgs& na, const float* x, long long x_ld, long long B, int F, int self, const float* dR, long long ldr, float* dx,
                 long long dx_ld, float* dE, long long dE_ld, hipStream_t st) {
     constexpr size_t lds = narrow_lds<D, NB>(true);
     (void)hipFuncSetAttribute((const void*)interact_bwd_narrow_kernel<D, NB, IT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((interact_bwd_narrow_kernel<D, NB, IT>), dim3((unsigned)narrow_grid(B, lds)), dim3(64 * NI_WAVES), lds, st, na, x, x_ld,
+    hipLaunchKernelGGL((interact_bwd_narrow_kernel<D, NB, IT>), dim3((unsigned)gather_grid(B, lds)), dim3(64 * GC_WAVES), lds, st, na, x, x_ld,
                        B, F, self, dR, ldr, dx, dx_ld, dE, dE_ld);
-}
-
-// the argument block shared by both entry points; 0 or a DLRM_E_* code
-int fill_args(NGatherArgs& na, int F, const void* const* weight_host, const int64_t* rows_host, const void* const* index_host,
-              const void* const* offsets_host, int64_t* err, const int32_t* pred_flag, int pred_nonzero) {
-    na.err = (long long*)err;
-    na.pred = DlrmPred{(const int*)pred_flag, pred_nonzero};
-    for (int f = 0; f < NI_MAXF; ++f) {
-        const int t = (f >= 1 && f < F) ? f - 1 : (F > 1 ? 0 : -1);      // unused slots repeat table 0 (never dereferenced)
-        na.w[f] = t >= 0 ? weight_host[t] : nullptr;
-        na.idx[f] = t >= 0 ? index_host[t] : nullptr;
-        na.off[f] = t >= 0 ? offsets_host[t] : nullptr;
-        na.rows[f] = t >= 0 ? rows_host[t] : 0;
-        if (f >= 1 && f < F) {
-            if (!na.w[f] || !na.idx[f] || !na.off[f] || na.rows[f] <= 0) return DLRM_E_ARG;
-            if (na.rows[f] > 0xFFFFFFFFLL) return DLRM_E_RANGE;            // row selectors travel as 32-bit values inside the kernels
-            if (!dlrm_aligned16(na.w[f])) return DLRM_E_MODE;              // a lane's 4 columns are one 16-byte load; rows are 4 D bytes apart
-        }
-    }
-    return 0;
 }
 
 }  // namespace
 
 extern "C" int dlrm_interact_gather_narrow_ok(int F, int D) {
-    return ((D == 16 || D == 32 || D == 64) && F >= 1 && F <= NI_MAXF) ? 1 : 0;
+    return ((D == 16 || D == 32 || D == 64) && F >= 1 && F <= GC_MAXF) ? 1 : 0;
 }
 
 #define NARROW_DISPATCH(CALL, ...)                                                                                   \
@@ -577,17 +470,13 @@ extern "C" int dlrm_interact_fwd_gather_narrow(int64_t B, int F, int D, const fl
                                                const void* const* index_host, const void* const* offsets_host, int idx_bits,
                                                int self_interaction, float* R, int64_t ldr, int64_t* err,
                                                const int32_t* pred_flag, int pred_nonzero, void* stream) {
-    if (B <= 0 || F <= 0 || D <= 0 || !x || !R) return DLRM_E_ARG;
-    if (F > 1 && (!weight_host || !rows_host || !index_host || !offsets_host)) return DLRM_E_ARG;
-    if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
-    if (!dlrm_interact_gather_narrow_ok(F, D)) return DLRM_E_MODE;
-    if (self_interaction < 0 || self_interaction > 2) return DLRM_E_MODE;     // 0 tril, 1 tril + diagonal, 2 torchrec triu order
-    const int P = (self_interaction & 1) ? F * (F + 1) / 2 : F * (F - 1) / 2;
-    if (ldr < D + P || x_ld < D) return DLRM_E_ARG;
-    NGatherArgs na;
-    const int rc = fill_args(na, F, weight_host, rows_host, index_host, offsets_host, err, pred_flag, pred_nonzero);
+    GatherArgs na;
+    // a lane's 4 columns are one 16-byte load; rows are 4 D bytes apart
+    const int rc = gather_check_fwd(B, F, D, x, x_ld, weight_host && rows_host && index_host && offsets_host, idx_bits,
+                                    dlrm_interact_gather_narrow_ok(F, D), self_interaction, R, ldr, [&] {
+        return fill_args(na, F, weight_host, rows_host, index_host, offsets_host, err, pred_flag, pred_nonzero, 15u);
+    });
     if (rc) return rc;
-    if (!dlrm_aligned16(x) || x_ld % 4 != 0 || !dlrm_aligned16(R) || ldr % 4 != 0) return DLRM_E_MODE;
     hipStream_t st = (hipStream_t)stream;
     const int self = self_interaction & 3;
     NARROW_DISPATCH(launch_fwd, na, x, (long long)x_ld, (long long)B, F, self, R, (long long)ldr, st);
@@ -601,19 +490,13 @@ extern "C" int dlrm_interact_bwd_gather_narrow(int64_t B, int F, int D, const fl
                                                int self_interaction, const float* dR, int64_t ldr,
                                                float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
                                                const int32_t* pred_flag, int pred_nonzero, void* stream) {
-    if (B <= 0 || F <= 0 || D <= 0 || !x || !dR || !dx) return DLRM_E_ARG;
-    if (F > 1 && (!weight_host || !rows_host || !index_host || !offsets_host || !dE)) return DLRM_E_ARG;
-    if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
-    if (!dlrm_interact_gather_narrow_ok(F, D)) return DLRM_E_MODE;
-    // bits 0-1 as the forward; bit 2 (DLRM_INTERACT_RELU_X): x is the output of a ReLU and dx is multiplied by [x > 0]
-    if (self_interaction < 0 || self_interaction > 7 || (self_interaction & 3) > 2) return DLRM_E_MODE;
-    const int P = (self_interaction & 1) ? F * (F + 1) / 2 : F * (F - 1) / 2;
-    if (ldr < D + P || x_ld < D || dx_ld < D || (F > 1 && dE_ld < (int64_t)(F - 1) * D)) return DLRM_E_ARG;
-    NGatherArgs na;
-    const int rc = fill_args(na, F, weight_host, rows_host, index_host, offsets_host, err, pred_flag, pred_nonzero);
+    GatherArgs na;
+    const int rc = gather_check_bwd(B, F, D, x, x_ld, weight_host && rows_host && index_host && offsets_host && dE, idx_bits,
+                                    dlrm_interact_gather_narrow_ok(F, D), self_interaction, dR, ldr, dx, dx_ld, dE, dE_ld,
+                                    (int64_t)(F - 1) * D, 0, [&] {
+        return fill_args(na, F, weight_host, rows_host, index_host, offsets_host, err, pred_flag, pred_nonzero, 15u);
+    });
     if (rc) return rc;
-    if (!dlrm_aligned16(x) || x_ld % 4 != 0 || !dlrm_aligned16(dR) || ldr % 4 != 0 || !dlrm_aligned16(dx) || dx_ld % 4 != 0) return DLRM_E_MODE;
-    if (F > 1 && (!dlrm_aligned16(dE) || dE_ld % 4 != 0)) return DLRM_E_MODE;
     hipStream_t st = (hipStream_t)stream;
     const int self = self_interaction & 7;
     NARROW_DISPATCH(launch_bwd, na, x, (long long)x_ld, (long long)B, F, self, dR, (long long)ldr, dx, (long long)dx_ld, dE, (long long)dE_ld, st);

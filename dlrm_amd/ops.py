@@ -1105,12 +1105,17 @@ def wait_spinning(ev, limit_s: Optional[float] = None) -> None:
             return
 
 
-def _gather_desc(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
-    """feature 0 = the [B, D] block x, features 1..T = the tables addressed through the bags' indices"""
-    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
+def _gather_one_lookup(bags: BagBatch, tables: int) -> None:
+    """what every fused lookup + interaction wrapper refuses first: the kernels fetch ONE row per bag and apply no pooling weight"""
+    if bags.T != tables or any(n != bags.B for n in bags.nnz):
         raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
     if bags._psw is not None:
         raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+
+
+def _gather_desc(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
+    """feature 0 = the [B, D] block x, features 1..T = the tables addressed through the bags' indices"""
+    _gather_one_lookup(bags, len(weights))
     _req(x, "x", ndim=2)
     ptrs = [x.data_ptr()] + [w.data_ptr() for w in weights]
     lds = [_ld(x)] + [D] * len(weights)
@@ -1138,16 +1143,14 @@ def _gather_tables_bf16(weights: Sequence[torch.Tensor], what: str) -> bool:
     return n16 > 0
 
 
-def _gather_desc_bf16(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
-    """_gather_desc for bf16 tables: the same refusals; table t is feature t + 1"""
-    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
-    if bags._psw is not None:
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+def _gather_desc_tables(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, weights_desc, kind: str):
+    """_gather_desc for the one-array table kinds: the same refusals; table t is feature t + 1.  weights_desc: _bf16_weights_desc (kind
+    "bf16") or _weights_desc (fp32 tables of D = 16 / 32 / 64, kind "narrow")"""
+    _gather_one_lookup(bags, len(weights))
     _req(x, "x", ndim=2)
-    Dw, wp, rows = _bf16_weights_desc(weights)
+    Dw, wp, rows = weights_desc(weights)
     if Dw != D or x.size(1) != D or x.size(0) != bags.B:
-        raise RuntimeError("dlrm_amd: the fused bf16 embedding + interaction path: shape mismatch")
+        raise RuntimeError("dlrm_amd: the fused %s embedding + interaction path: shape mismatch" % kind)
     return 1 + bags.T, wp, rows
 
 
@@ -1157,7 +1160,7 @@ def interact_fwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
     Tables all fp32, or all torch.bfloat16 (dlrm_interact_fwd_gather_bf16: the bits of emb_fwd_bf16 + interact_fwd)."""
     lib = _lib.load()
     if _gather_tables_bf16(weights, "interact_fwd_gather"):
-        F, wp, rows = _gather_desc_bf16(x, weights, bags, D)
+        F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "bf16")
         _req(R, "R", ndim=2)
         if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
             raise RuntimeError("dlrm_amd: interact_fwd_gather shape mismatch")
@@ -1198,10 +1201,7 @@ def qr_tables_aligned(weights: Sequence[torch.Tensor], weights_r: Sequence[Optio
 
 def _gather_desc_qr(x: torch.Tensor, weights, weights_r, rows, collisions, bags: BagBatch, D: int):
     """_gather_desc for a table list with QR tables: the same refusals; table t is feature t + 1"""
-    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
-    if bags._psw is not None:
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+    _gather_one_lookup(bags, len(weights))
     _req(x, "x", ndim=2)
     Dw, wp, wrp, rows_a, coll_a = _qr_desc(weights, weights_r, rows, collisions)
     if Dw != D or x.size(1) != D or x.size(0) != bags.B:
@@ -1265,11 +1265,7 @@ def interact_fwd_gather_quant(x: torch.Tensor, qweights: Sequence[torch.Tensor],
     """R = interaction of [x | one-hot rows of the packed tables], the rows fetched and dequantised by the kernel itself
     (dlrm_interact_fwd_gather_quant): the bits of emb_fwd_quant into a feature buffer + interact_fwd, without that buffer.  Forward only."""
     lib = _lib.load()
-    # validated as _gather_desc does: one lookup per bag, no per-sample weights
-    if bags.T != len(qweights) or any(n != bags.B for n in bags.nnz):
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
-    if bags._psw is not None:
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
+    _gather_one_lookup(bags, len(qweights))
     wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "interact_fwd_gather_quant")
     _req(x, "x", ndim=2)
     _req(R, "R", ndim=2)
@@ -1300,7 +1296,7 @@ def interact_bwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
         # bf16 tables (dlrm_interact_bwd_gather_bf16): the bits of interact_bwd over (x, the buffer emb_fwd_bf16 wrote)
         if presorted is not None:
             raise RuntimeError("dlrm_amd: interact_bwd_gather: the update inside the backward (presorted) exists for fp32 tables only")
-        F, wp, rows = _gather_desc_bf16(x, weights, bags, D)
+        F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "bf16")
         _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
         if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
             raise RuntimeError("dlrm_amd: interact_bwd_gather shape mismatch")
@@ -1343,25 +1339,12 @@ def gather_narrow_ok(F: int, D: int) -> bool:
     return bool(_lib.load().dlrm_interact_gather_narrow_ok(int(F), int(D)))
 
 
-def _gather_desc_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int):
-    """_gather_desc's refusals for the narrow kernels; table t is feature t + 1"""
-    if bags.T != len(weights) or any(n != bags.B for n in bags.nnz):
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
-    if bags._psw is not None:
-        raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
-    _req(x, "x", ndim=2)
-    Dw, wp, rows = _weights_desc(weights)
-    if Dw != D or x.size(1) != D or x.size(0) != bags.B:
-        raise RuntimeError("dlrm_amd: the fused narrow embedding + interaction path: shape mismatch")
-    return 1 + bags.T, wp, rows
-
-
 def interact_fwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
                                R: torch.Tensor, pred=None) -> torch.Tensor:
     """R = interaction of [x | one-hot rows of the fp32 tables], D = 16 / 32 / 64, the rows fetched by the kernel itself
     (dlrm_interact_fwd_gather_narrow): the bits of emb_fwd into a feature buffer + interact_fwd, without that buffer."""
     lib = _lib.load()
-    F, wp, rows = _gather_desc_narrow(x, weights, bags, D)
+    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _weights_desc, "narrow")
     _req(R, "R", ndim=2)
     if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
         raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow shape mismatch")
@@ -1380,7 +1363,7 @@ def interact_bwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor],
     """dx [B, D] = gradient of x; dE [B, T*D] = gradients of the T gathered rows (dlrm_interact_bwd_gather_narrow): the bits of
     interact_bwd over (x, the buffer emb_fwd wrote).  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
     lib = _lib.load()
-    F, wp, rows = _gather_desc_narrow(x, weights, bags, D)
+    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _weights_desc, "narrow")
     _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
     if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
         raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow shape mismatch")

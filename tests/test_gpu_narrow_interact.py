@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ROWS = [1, 37, 2000, 3, 513, 1200, 2, 64, 1999, 17, 300, 5, 1024, 77, 2000, 9, 450, 31, 1500, 4, 800, 129, 11, 1777, 256, 60]      # 26 tables
-# one pass of a launch's grid covers narrow_grid() x 4 samples (csrc/interact_narrow.hip): 4 waves per workgroup, one sample per wave, and at
+# one pass of a launch's grid covers gather_grid() x 4 samples (csrc/gather_common.h): 4 waves per workgroup, one sample per wave, and at
 # most 256 CUs x 2 workgroups = 512 workgroups (256 x 1 where a workgroup's LDS exceeds 80 KiB) -> at most 2048 samples.  Twice that is 4096.
 B_BIG = 4101
 # -0.0, fp32 subnormals of both signs, +0.0, the smallest normal
