@@ -86,6 +86,14 @@ SIGNATURES = {
     "dlrm_interact_fwd_gather_narrow": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dlrm_interact_bwd_gather_narrow": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64,
                                                _vp, _vp, _i32, _vp]),
+    "dlrm_interact_gather_narrow_bf16_ok": (_i32, [_i32, _i32]),
+    "dlrm_interact_gather_narrow_quant_ok": (_i32, [_i32, _i32, _i32]),
+    "dlrm_interact_fwd_gather_narrow_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _vp, _i32,
+                                                    _vp]),
+    "dlrm_interact_bwd_gather_narrow_bf16": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                    _i64, _vp, _vp, _i32, _vp]),
+    "dlrm_interact_fwd_gather_narrow_quant": (_i32, [_i64, _i32, _i32, _i32, _vp, _i64, _pp, _pi64, _pp, _pp, _i32, _i32, _vp, _i64, _vp, _vp,
+                                                     _i32, _vp]),
     "dlrm_interact_gather_qr_ok": (_i32, [_i32, _i32]),
     "dlrm_interact_fwd_gather_qr": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _i32, _i32, _vp, _i64,
                                            _vp, _vp, _i32, _vp]),

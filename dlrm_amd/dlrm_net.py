@@ -345,6 +345,8 @@ class DLRM_Net(nn.Module):
     # opt-in (launcher: --narrow-fuse-interact): a model with plain fp32 tables of D = 16 / 32 / 64 enters the fused lookup + interaction branch
     # of sequential_forward under the fp32 branch's conditions and runs csrc/interact_narrow.hip (forward and backward) instead of dlrm_emb_fwd
     # + the generic interaction kernels through the pooled [B, T*D] buffer — the same bits.  Off: such a model runs exactly the two-kernel form.
+    # Together with fuse_bf16_interact a bfloat16 model of those widths enters too (csrc/interact_narrow_rows.hip, forward and backward), and
+    # together with fuse_quant_interact a quantised model of those widths takes the narrow fused forward of that file (_quant_fused_forward).
     fuse_narrow_interact = False
     # opt-in (launcher: --fused-adagrad): a stock torch.optim.Adagrad that owns the tables (the reference's --optimizer=adagrad) gets the fused
     # exact Adagrad update (csrc/adagrad.hip dlrm_emb_bwd_adagrad) on ITS state[p]["sum"], the step pre-hook advances the tables'
@@ -1154,18 +1156,23 @@ class DLRM_Net(nn.Module):
                                               *self._emb_weights(self.emb_l))
 
     def _narrow_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
-        """The interaction output of a model with plain fp32 tables of D = 16 / 32 / 64 through csrc/interact_narrow.hip
-        (NarrowGatherInteractFunction), or None when the two-kernel form has to run: the conditions and the offsets state machine of the fp32
-        fused branch of sequential_forward — True -> the fused kernels alone; a device flag -> both forms behind the launch predicate, no host
+        """The interaction output of a model with plain fp32 tables of D = 16 / 32 / 64 through csrc/interact_narrow.hip, or — only with
+        fuse_bf16_interact set as well — of a model with bfloat16 tables of those widths through csrc/interact_narrow_rows.hip
+        (NarrowGatherInteractFunction dispatches on the tables' dtype), or None when the two-kernel form has to run: the conditions and the
+        offsets state machine of the fp32 fused branch of sequential_forward — True -> the fused kernels alone; a device flag -> both forms behind the launch predicate, no host
         wait; False (proven ragged) -> None.  ONE difference: None (a HIP graph is being captured) -> None too, because GraphedTrainStep proves
         the offsets of every incoming batch only for the shapes of ops.gather_ok.  The update stays the step-time one (bags.presort = None),
-        update_in_backward included: the update inside the backward exists at D = 128 only."""
-        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and self.emb_bf16 is None
-                and ops.gather_narrow_ok(1 + T, D) and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l)
+        update_in_backward included: the update inside the backward exists at D = 128 only.  SGD and row-wise Adagrad over bfloat16 rows
+        receive dE through the same sink as from the two-kernel form."""
+        bf16 = self.emb_bf16 is not None
+        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
+                and (ops.gather_narrow_ok(1 + T, D) if not bf16 else (self.fuse_bf16_interact and ops.gather_narrow_bf16_ok(1 + T, D)))
+                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l)
                 and not any(w is not None for w in (self.v_W_l or []))):
             return None
         bags = self._bags(lS_o, lS_i, None)
-        if not (all(n == B for n in bags.nnz) and all(e.weight.data_ptr() % 16 == 0 for e in self.emb_l)):
+        # (a lane's 4 columns are one 16-byte load of an fp32 row, one 8-byte load of a bfloat16 row)
+        if not (all(n == B for n in bags.nnz) and all(e.weight.data_ptr() % (8 if bf16 else 16) == 0 for e in self.emb_l)):
             return None
         proof = None
         if DEVICE_PREDICATE:
@@ -1187,14 +1194,17 @@ class DLRM_Net(nn.Module):
 
     def _quant_fused_forward(self, dense_x, lS_o, lS_i, B, T, D):
         """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run:
-        `cat`, multi-hot bags, pooling weights, D != 128, a forward that wants gradients (the fused kernel is forward only), or
-        fuse_quant_interact / fuse_emb_interact off.  The offsets' one-lookup-per-bag state decides as in the fp32 branch of
-        sequential_forward: True / None -> the fused kernel alone; a device flag -> the fused kernel behind (flag, 0) and
+        `cat`, multi-hot bags, pooling weights, a width without a fused kernel, a forward that wants gradients (the fused kernel is forward
+        only), or fuse_quant_interact / fuse_emb_interact off.  D = 128 runs csrc/interact_quant.hip; D = 16 / 32 / 64 run
+        dlrm_interact_fwd_gather_narrow_quant (csrc/interact_narrow_rows.hip), only with fuse_narrow_interact set as well — same rules.
+        The offsets' one-lookup-per-bag state decides as in the fp32 branch of sequential_forward: True / None -> the fused kernel alone; a device flag -> the fused kernel behind (flag, 0) and
         dlrm_emb_fwd_quant + dlrm_interact_fwd behind (flag, 1), no host wait; False -> None.  No autograd node: the tables are constants."""
         bits = self.quantize_bits
+        narrow = self.fuse_narrow_interact and ops.gather_narrow_quant_ok(1 + T, D, bits)
         if not (self.fuse_emb_interact and self.fuse_quant_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
-                and ops.gather_quant_ok(1 + T, D, bits) and not any(w is not None for w in (self.v_W_l or []))):
+                and (narrow or ops.gather_quant_ok(1 + T, D, bits)) and not any(w is not None for w in (self.v_W_l or []))):
             return None
+        fused = ops.interact_fwd_gather_narrow_quant if narrow else ops.interact_fwd_gather_quant
         if torch.is_grad_enabled() and (dense_x.requires_grad or (getattr(self.bot_l, "quant_bits", 32) == 32
                                                                   and any(p_.requires_grad for p_ in self.bot_l.parameters()))):
             return None          # (a forward whose bottom tower is being trained: InteractFunction carries the gradient of x)
@@ -1208,8 +1218,8 @@ class DLRM_Net(nn.Module):
         mode = self._interaction_mode()
         R = torch.empty((B, _functional._round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
         if not isinstance(state, torch.Tensor):
-            return ops.interact_fwd_gather_quant(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R)
-        ops.interact_fwd_gather_quant(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R, pred=(state, 0))
+            return fused(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R)
+        fused(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R, pred=(state, 0))
         ly = _functional.alloc2d(B, T * D, x)
         ops.emb_fwd_quant(self.emb_l_q, self.emb_q_rows, D, bits, bags, ly, pred=(state, 1))
         ops.interact_fwd((x, ly), D, mode, R, pred=(state, 1))

@@ -769,10 +769,11 @@ class GatherInteractFunction(Function):
 
 
 class NarrowGatherInteractFunction(Function):
-    """GatherInteractFunction for plain fp32 tables of D = 16 / 32 / 64 (csrc/interact_narrow.hip): the bits of EmbeddingBagsFunction +
+    """GatherInteractFunction for plain fp32 tables of D = 16 / 32 / 64 (csrc/interact_narrow.hip), or bfloat16 tables of those widths
+    (csrc/interact_narrow_rows.hip; the calls dispatch on the tables' dtype): the bits of EmbeddingBagsFunction / BF16EmbeddingBagsFunction +
     InteractFunction without the [B, T*D] pooled buffer.  With `bags.iota_flag` absent the fused kernels run alone; with a device flag they run
-    behind (flag, 0) and dlrm_emb_fwd + the generic interaction kernels behind (flag, 1), the pooled buffer saved for the backward.  dE goes
-    to `sink` either way: one update call per step.  There is no update inside the backward at these widths (`bags.presort` is not read)."""
+    behind (flag, 0) and dlrm_emb_fwd (dlrm_emb_fwd_bf16) + the generic interaction kernels behind (flag, 1), the pooled buffer saved for the
+    backward.  dE goes to `sink` either way: one update call per step.  There is no update inside the backward at these widths (`bags.presort` is not read)."""
 
     @staticmethod
     def forward(ctx, sink, D, self_interaction, bags, x, *weights):
@@ -782,16 +783,19 @@ class NarrowGatherInteractFunction(Function):
         R = torch.empty((x.size(0), _round4(ops.interact_out_width(F, D, mode))), dtype=torch.float32, device=x.device)
         flag = getattr(bags, "iota_flag", None)
         ly = None
+        # (bfloat16 tables: the kernels of csrc/interact_narrow_rows.hip, and emb_fwd_bf16 as the lookup of the two-kernel form)
+        bf16 = ops._gather_tables_bf16(weights, "NarrowGatherInteractFunction")
+        fwd = ops.interact_fwd_gather_narrow_bf16 if bf16 else ops.interact_fwd_gather_narrow
         if flag is None:
-            ops.interact_fwd_gather_narrow(x, weights, bags, D, mode, R)
+            fwd(x, weights, bags, D, mode, R)
         else:
-            ops.interact_fwd_gather_narrow(x, weights, bags, D, mode, R, pred=(flag, 0))
+            fwd(x, weights, bags, D, mode, R, pred=(flag, 0))
             ly = alloc2d(x.size(0), len(weights) * D, x)
-            ops.emb_fwd(weights, bags, ly, pred=(flag, 1))
+            (ops.emb_fwd_bf16 if bf16 else ops.emb_fwd)(weights, bags, ly, pred=(flag, 1))
             ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
         ctx.sink, ctx.bags, ctx.weights = sink, bags, weights
         ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
-        ctx.flag = flag
+        ctx.flag, ctx.bf16 = flag, bf16
         if ly is None:
             ctx.save_for_backward(x)
         else:
@@ -808,7 +812,8 @@ class NarrowGatherInteractFunction(Function):
         flat = torch.empty(B * (1 + T) * D, dtype=torch.float32, device=dR.device)
         dx, dE = flat[:B * D].view(B, D), flat[B * D:].view(B, T * D)
         pred = None if ctx.flag is None else (ctx.flag, 0)
-        ops.interact_bwd_gather_narrow(x, ctx.weights, ctx.bags, D, ctx.self_interaction, dR, dx, dE, pred=pred)
+        bwd = ops.interact_bwd_gather_narrow_bf16 if ctx.bf16 else ops.interact_bwd_gather_narrow
+        bwd(x, ctx.weights, ctx.bags, D, ctx.self_interaction, dR, dx, dE, pred=pred)
         if ctx.flag is not None:
             ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
         ctx.sink(ctx.weights, ctx.bags, dE)

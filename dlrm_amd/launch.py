@@ -93,18 +93,22 @@ def build_parser() -> argparse.ArgumentParser:
                          "reference's numpy float64 temporary does not fit host RAM); same distribution, torch RNG")
     ap.add_argument("--bf16-tables", choices=("stochastic", "nearest"), default=None,
                     help="store the embedding tables in bfloat16 (dlrm_amd.set_embedding_dtype): half the table bytes; the fused sparse "
-                         "update rounds each touched row once per step, stochastically (reproducible: --bf16-seed) or to nearest")
+                         "update rounds each touched row once per step, stochastically (reproducible: --bf16-seed) or to nearest; the rows can "
+                         "be fetched inside the interaction kernels: --bf16-fuse-interact (and --narrow-fuse-interact at widths 16 / 32 / 64)")
     ap.add_argument("--bf16-seed", type=int, default=0, help="seed of the stochastic rounding of --bf16-tables")
     ap.add_argument("--bf16-fuse-interact", action="store_true",
                     help="with --bf16-tables: fetch the bfloat16 rows inside the interaction kernels, forward and backward "
-                         "(DLRM_Net.fuse_bf16_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer)")
+                         "(DLRM_Net.fuse_bf16_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer); "
+                         "--arch-sparse-feature-size 128, or 16 / 32 / 64 together with --narrow-fuse-interact")
     ap.add_argument("--qr-fuse-interact", action="store_true",
                     help="with the reference's --qr-flag: fetch and compose the quotient / remainder rows inside the interaction kernels, "
                          "forward and backward (DLRM_Net.fuse_qr_interact; same bits as the default two-kernel form, no pooled [B, T*D] "
                          "buffer and no pooled sums kept for the backward)")
     ap.add_argument("--narrow-fuse-interact", action="store_true",
                     help="plain fp32 tables of --arch-sparse-feature-size 16 / 32 / 64: fetch the rows inside the interaction kernels, forward "
-                         "and backward (DLRM_Net.fuse_narrow_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer)")
+                         "and backward (DLRM_Net.fuse_narrow_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer).  "
+                         "Together with --bf16-tables --bf16-fuse-interact the same for bfloat16 tables of those widths; with the reference's "
+                         "--quantize-emb-with-bit 4|8 --inference-only the fused forward over the packed tables of those widths")
     ap.add_argument("--fused-adagrad", action="store_true",
                     help="with the reference's --optimizer=adagrad: update the embedding tables with the fused exact Adagrad kernel on "
                          "torch.optim.Adagrad's own state (DLRM_Net.fused_adagrad; no sparse COO gradient, the dense parameters stay with "
@@ -134,7 +138,7 @@ def main(argv=None) -> None:
         dlrm_amd.DLRM_Net.fuse_qr_interact = True          # every model run() builds from here on (a model without QR tables ignores it)
     if a.narrow_fuse_interact:
         import dlrm_amd
-        dlrm_amd.DLRM_Net.fuse_narrow_interact = True      # every model run() builds from here on (other widths and table kinds ignore it)
+        dlrm_amd.DLRM_Net.fuse_narrow_interact = True      # every model run() builds from here on (other widths ignore it)
     if a.fused_adagrad:
         import dlrm_amd
         dlrm_amd.DLRM_Net.fused_adagrad = True             # every model run() builds from here on (other optimizers ignore it)

@@ -1377,6 +1377,82 @@ def interact_bwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor],
     _lib.check(rc, "dlrm_interact_bwd_gather_narrow")
 
 
+# ---- ... and over bfloat16 / packed tables of those widths (csrc/interact_narrow_rows.hip: the same kernels over another row source).
+# Separate functions again: interact_*_gather (bf16) and interact_fwd_gather_quant keep refusing every D != 128
+def gather_narrow_bf16_ok(F: int, D: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_narrow_bf16_ok(int(F), int(D)))
+
+
+def gather_narrow_quant_ok(F: int, D: int, bits: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_narrow_quant_ok(int(F), int(D), int(bits)))
+
+
+def narrow_bf16_tables_aligned(weights: Sequence[torch.Tensor]) -> bool:
+    """what the narrow fused bf16 kernels need of the tables: a lane's 4 columns are one 8-byte load"""
+    return all(w.data_ptr() % 8 == 0 for w in weights)
+
+
+def interact_fwd_gather_narrow_bf16(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
+                                    R: torch.Tensor, pred=None) -> torch.Tensor:
+    """R = interaction of [x | one-hot rows of the bfloat16 tables], D = 16 / 32 / 64, the rows fetched and widened by the kernel itself
+    (dlrm_interact_fwd_gather_narrow_bf16): the bits of emb_fwd_bf16 into a feature buffer + interact_fwd, without that buffer."""
+    lib = _lib.load()
+    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "narrow bf16")
+    _req(R, "R", ndim=2)
+    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow_bf16 shape mismatch")
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_fwd_narrow_bf16"):
+        rc = lib.dlrm_interact_fwd_gather_narrow_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
+                                                      bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
+                                                      C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_fwd_gather_narrow_bf16")
+    return R
+
+
+def interact_bwd_gather_narrow_bf16(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
+                                    dR: torch.Tensor, dx: torch.Tensor, dE: torch.Tensor, pred=None) -> None:
+    """dx [B, D] = gradient of x; dE [B, T*D] = fp32 gradients of the T gathered bfloat16 rows (dlrm_interact_bwd_gather_narrow_bf16): the
+    bits of interact_bwd over (x, the buffer emb_fwd_bf16 wrote).  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
+    lib = _lib.load()
+    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "narrow bf16")
+    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
+    if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
+        raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow_bf16 shape mismatch")
+    st = _stream(dR)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_bwd_narrow_bf16"):
+        rc = lib.dlrm_interact_bwd_gather_narrow_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
+                                                      bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
+                                                      C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(dE.data_ptr()), _ld(dE),
+                                                      C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_bwd_gather_narrow_bf16")
+
+
+def interact_fwd_gather_narrow_quant(x: torch.Tensor, qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int,
+                                     bags: BagBatch, self_interaction, R: torch.Tensor, pred=None) -> torch.Tensor:
+    """R = interaction of [x | one-hot rows of the packed tables], D = 16 / 32 / 64, the rows fetched and dequantised by the kernel itself
+    (dlrm_interact_fwd_gather_narrow_quant): the bits of emb_fwd_quant into a feature buffer + interact_fwd, without that buffer.
+    Forward only."""
+    lib = _lib.load()
+    _gather_one_lookup(bags, len(qweights))
+    wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "interact_fwd_gather_narrow_quant")
+    _req(x, "x", ndim=2)
+    _req(R, "R", ndim=2)
+    F = 1 + bags.T
+    if x.size(1) != D or R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow_quant shape mismatch")
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_fwd_narrow_quant"):
+        rc = lib.dlrm_interact_fwd_gather_narrow_quant(bags.B, F, D, bits, C.c_void_p(x.data_ptr()), _ld(x), wp, rp, bags._idx, bags._off,
+                                                       bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
+                                                       C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_fwd_gather_narrow_quant")
+    return R
+
+
 def interact_bwd(blocks: Sequence[torch.Tensor], D: int, self_interaction: bool, dR: torch.Tensor,
                  dblocks: Sequence[torch.Tensor], order=None, pred=None) -> None:
     """`self_interaction` is the forward's mode, optionally OR-ed with INTERACT_RELU_X: feature 0 (the first D columns of blocks[0],

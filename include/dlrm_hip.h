@@ -421,6 +421,47 @@ int dlrm_interact_bwd_gather_narrow(int64_t B, int F, int D, const float* x, int
                                     float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
                                     const int32_t* pred_flag, int pred_nonzero, void* stream);
 
+/* Fused lookup + interaction over bfloat16 tables (FORWARD and BACKWARD) and over 8- / 4-bit row-wise quantised tables (FORWARD only) of
+ * D = 16 / 32 / 64 (csrc/interact_narrow_rows.hip: the kernels of csrc/interact_narrow.h over another row source; symbols added, the ABI
+ * version stays 17).  Replace, for one-lookup-per-bag batches without per-sample weights: dlrm_emb_fwd_bf16 / dlrm_emb_fwd_quant +
+ * dlrm_interact_fwd, and (bf16) dlrm_interact_bwd over the pooled buffer, at the widths where those run the generic interaction kernels;
+ * the D = 128 forms are dlrm_interact_{fwd,bwd}_gather_bf16 and dlrm_interact_fwd_gather_quant, which keep refusing every other width.
+ * Operands: dlrm_interact_{fwd,bwd}_gather_narrow_bf16 take the argument lists of dlrm_interact_{fwd,bwd}_gather_narrow, weight_host[f-1]
+ * being rows_host[f-1] rows of D bfloat16; dlrm_interact_fwd_gather_narrow_quant takes the argument list of dlrm_interact_fwd_gather_quant,
+ * qweight_host[f-1] being rows_host[f-1] rows in dlrm_emb_quantize_rows' format (D + 8 bytes at 8 bits, D/2 + 4 bytes at 4 bits).
+ *   forward : R is BIT-IDENTICAL to dlrm_emb_fwd_bf16 / dlrm_emb_fwd_quant (psw_host = NULL) into a feature buffer + dlrm_interact_fwd.
+ *   backward: dx, dE (fp32 — the dout of dlrm_emb_bwd_sgd_bf16 / dlrm_emb_bwd_rowwise_adagrad_bf16) are BIT-IDENTICAL to dlrm_interact_bwd
+ *             over (x, the buffer dlrm_emb_fwd_bf16 wrote), DLRM_INTERACT_RELU_X included, and are written exactly as
+ *             dlrm_interact_bwd_gather_narrow writes them.  The gradient row of an out-of-range lookup is written like any other.
+ *   element = fmaf(1.0f, upcast(bits), +0.0f) (bf16: -0.0 becomes +0.0) / fmaf(1.0f, fmaf(scale, (float)q, bias), +0.0f) (quantised; the fp16
+ *   scale / bias of the 4-bit form convert exactly, low nibble first);
+ *   offsets_host[t] : verified on the device to be 0, 1, 2, ... — a violation is reported through `err` with rows = -1;
+ *   an index outside [0, rows) is reported ({1, table, index, rows}) and contributes a row of +0.0;
+ *   row byte offsets are 64-bit;   pred_flag / pred_nonzero : launch predicate as dlrm_*_pred (NULL: always run).
+ * dlrm_interact_gather_narrow_bf16_ok (host only): 1 iff dlrm_interact_gather_narrow_ok(F, D).
+ * dlrm_interact_gather_narrow_quant_ok (host only): 1 iff bits is 4 or 8 and dlrm_interact_gather_narrow_ok(F, D).
+ * Return DLRM_E_MODE for shapes those functions refuse, a bf16 or 8-bit table base not aligned to 8 bytes, a 4-bit table base not aligned to
+ * 4 bytes, an x / R / dR / dx / dE not aligned to 16 bytes or a leading dimension that is not a multiple of 4; DLRM_E_RANGE for a table of
+ * more than 0xFFFFFFFF rows; DLRM_E_ARG for null operands, rows <= 0, leading dimensions smaller than their rows. */
+int dlrm_interact_gather_narrow_bf16_ok(int F, int D);
+int dlrm_interact_gather_narrow_quant_ok(int F, int D, int bits);
+int dlrm_interact_fwd_gather_narrow_bf16(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                         const void* const* weight_host, const int64_t* rows_host,
+                                         const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                         int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                         const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_interact_bwd_gather_narrow_bf16(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                         const void* const* weight_host, const int64_t* rows_host,
+                                         const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                         int self_interaction, const float* dR, int64_t ldr,
+                                         float* dx, int64_t dx_ld, float* dE, int64_t dE_ld, int64_t* err,
+                                         const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_interact_fwd_gather_narrow_quant(int64_t B, int F, int D, int bits, const float* x, int64_t x_ld,
+                                          const void* const* qweight_host, const int64_t* rows_host,
+                                          const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                          int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                          const int32_t* pred_flag, int pred_nonzero, void* stream);
+
 /* Fused lookup + interaction over quotient-remainder (QR) tables, FORWARD and BACKWARD (csrc/interact_qr.hip; symbols added, the ABI version
  * stays 17).  Replaces, for one-lookup-per-bag batches: dlrm_emb_fwd_qr + dlrm_interact_fwd, and dlrm_interact_bwd over the pooled buffer +
  * dlrm_emb_qr_bwd_split.  Feature 0 is the fp32 block x ([B, D], row stride x_ld); feature f = 1 .. F-1 is table f-1, whose operands follow

@@ -2,7 +2,8 @@
 """The fused narrow (D = 16 / 32 / 64) fp32 lookup + interaction kernels (forward and backward) beside the two-kernel form they replace, same
 process, same GPU, same inputs.
 
-    python tools/bench_narrow_interact.py [--repeats 20] [--warmup 3] [--max-rows 10000000] [--out profiles/narrow_interact/fused_rates.md]
+    python tools/bench_narrow_interact.py [--rows fp32|bf16|q8|q4] [--repeats 20] [--warmup 3] [--max-rows 10000000]
+                                          [--out profiles/narrow_interact/fused_rates.md]
 
 Shapes: 26 tables, one lookup per bag, int64 ids; D = 64 with the Criteo-Terabyte row counts and D = 16 with the Criteo-Kaggle row counts
 (bench.py WORKLOADS), each at B = 2048 and B = 65536; row counts capped at --max-rows per table.
@@ -13,7 +14,12 @@ Shapes: 26 tables, one lookup per bag, int64 ids; D = 64 with the Criteo-Terabyt
 Protocol (docs/MEASUREMENT.md): warm-up rounds, then `repeats` rounds; every round times each variant once between two HIP events (the
 variants alternate inside a round, so drift hits all alike); the MEDIAN over the rounds is reported with min / max.  Before timing, the
 fused results are compared with the two-kernel results bit for bit.  Algorithmic bytes: ids + offsets, table row bytes, x, R / dR, dx and
-dE; the two-kernel form adds the [B, T*D] fp32 buffer (forward: written and read back; backward: read).  No GPU: the tool fails."""
+dE; the two-kernel form adds the [B, T*D] fp32 buffer (forward: written and read back; backward: read).  No GPU: the tool fails.
+
+--rows bf16 | q8 | q4 (default fp32, whose output is unchanged): the same shapes over bfloat16 tables (dlrm_interact_{fwd,bwd}_gather_narrow_bf16
+against dlrm_emb_fwd_bf16 + the generic interaction kernels) or over 8- / 4-bit packed tables (dlrm_interact_fwd_gather_narrow_quant against
+dlrm_emb_fwd_quant + dlrm_interact_fwd; forward only: there is no backward over packed tables).  The table bytes of a lookup are then
+2 D, D + 8 and D/2 + 4 per row."""
 from __future__ import annotations
 
 import argparse
@@ -26,11 +32,22 @@ sys.path.insert(0, ROOT)
 
 import torch
 
-FWD_FUSED = "forward: fused (dlrm_interact_fwd_gather_narrow)"
-FWD_TWO = "forward: two kernels (dlrm_emb_fwd + dlrm_interact_fwd)"
-FWD_LOOKUP = "forward: lookup alone (dlrm_emb_fwd)"
-BWD_FUSED = "backward: fused (dlrm_interact_bwd_gather_narrow)"
-BWD_TWO = "backward: two-kernel form (dlrm_interact_bwd)"
+ROW_KINDS = ("fp32", "bf16", "q8", "q4")
+# per row kind: the suffix of the fused entry points, the lookup of the two-kernel form
+_SUFFIX = {"fp32": "", "bf16": "_bf16", "q8": "_quant", "q4": "_quant"}
+_LOOKUP = {"fp32": "dlrm_emb_fwd", "bf16": "dlrm_emb_fwd_bf16", "q8": "dlrm_emb_fwd_quant", "q4": "dlrm_emb_fwd_quant"}
+
+
+def labels(kind):
+    return ("forward: fused (dlrm_interact_fwd_gather_narrow%s)" % _SUFFIX[kind],
+            "forward: two kernels (%s + dlrm_interact_fwd)" % _LOOKUP[kind],
+            "forward: lookup alone (%s)" % _LOOKUP[kind],
+            "backward: fused (dlrm_interact_bwd_gather_narrow%s)" % _SUFFIX[kind],
+            "backward: two-kernel form (dlrm_interact_bwd)")
+
+
+def row_bytes(kind, D):
+    return {"fp32": 4 * D, "bf16": 2 * D, "q8": D + 8, "q4": D // 2 + 4}[kind]
 
 
 def time_ms(fn) -> float:
@@ -46,12 +63,23 @@ def same_bits(a, b) -> bool:
     return torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
-def make_tables(rows, D, dev, g):
-    return [torch.empty((n, D), dtype=torch.float32, device=dev).uniform_(-float(n) ** -0.5, float(n) ** -0.5, generator=g) for n in rows]
+def make_tables(rows, D, dev, g, kind="fp32"):
+    from dlrm_amd import ops
+    out = []
+    for n in rows:
+        w = torch.empty((n, D), dtype=torch.float32, device=dev).uniform_(-float(n) ** -0.5, float(n) ** -0.5, generator=g)
+        if kind == "bf16":
+            w = w.to(torch.bfloat16)
+        elif kind != "fp32":
+            w = ops.emb_quantize(w, 8 if kind == "q8" else 4)
+        out.append(w)
+    return out
 
 
 def run_shape(name, tables, D, B, args, dev, lines, g):
     from dlrm_amd import ops
+    kind = args.rows
+    FWD_FUSED, FWD_TWO, FWD_LOOKUP, BWD_FUSED, BWD_TWO = labels(kind)
     rows = [w.size(0) for w in tables]
     T = len(rows)
     F = T + 1
@@ -71,21 +99,33 @@ def run_shape(name, tables, D, B, args, dev, lines, g):
          for k in ("fused", "two")}
     mode = ops.INTERACT_RELU_X          # what the model's backward passes (the bottom tower ends in a ReLU)
 
+    bits = {"q8": 8, "q4": 4}.get(kind)
+    if kind == "fp32":
+        lookup = lambda: ops.emb_fwd(tables, bags, E)
+        fused_fwd = lambda: ops.interact_fwd_gather_narrow(x, tables, bags, D, 0, R["fused"])
+        fused_bwd = lambda: ops.interact_bwd_gather_narrow(x, tables, bags, D, mode, dR, *G["fused"])
+    elif kind == "bf16":
+        lookup = lambda: ops.emb_fwd_bf16(tables, bags, E)
+        fused_fwd = lambda: ops.interact_fwd_gather_narrow_bf16(x, tables, bags, D, 0, R["fused"])
+        fused_bwd = lambda: ops.interact_bwd_gather_narrow_bf16(x, tables, bags, D, mode, dR, *G["fused"])
+    else:
+        lookup = lambda: ops.emb_fwd_quant(tables, rows, D, bits, bags, E)
+        fused_fwd = lambda: ops.interact_fwd_gather_narrow_quant(x, tables, rows, D, bits, bags, 0, R["fused"])
+        fused_bwd = None                      # packed tables are constants: forward only
+
     def two_fwd():
-        ops.emb_fwd(tables, bags, E)
+        lookup()
         ops.interact_fwd((feat,), D, 0, R["two"])
-    kernels = {
-        FWD_FUSED: lambda: ops.interact_fwd_gather_narrow(x, tables, bags, D, 0, R["fused"]),
-        FWD_TWO: two_fwd,
-        FWD_LOOKUP: lambda: ops.emb_fwd(tables, bags, E),
-        BWD_FUSED: lambda: ops.interact_bwd_gather_narrow(x, tables, bags, D, mode, dR, *G["fused"]),
-        BWD_TWO: lambda: ops.interact_bwd((x, E), D, mode, dR, G["two"]),
-    }
+    kernels = {FWD_FUSED: fused_fwd, FWD_TWO: two_fwd, FWD_LOOKUP: lookup}
+    if fused_bwd is not None:
+        kernels[BWD_FUSED] = fused_bwd
+        kernels[BWD_TWO] = lambda: ops.interact_bwd((x, E), D, mode, dR, G["two"])
     # the results the timed kernels compute are the same bits
     for fn in kernels.values():
         fn()
     ops.check_index_errors(sync=True)
-    if not same_bits(R["fused"], R["two"]) or not same_bits(G["fused"][0], G["two"][0]) or not same_bits(G["fused"][1], G["two"][1]):
+    if not same_bits(R["fused"], R["two"]) or (fused_bwd is not None and (not same_bits(G["fused"][0], G["two"][0])
+                                                                         or not same_bits(G["fused"][1], G["two"][1]))):
         sys.exit("ERROR: %s: the fused narrow kernels and the two-kernel form differ" % name)
     for _ in range(args.warmup):
         for fn in kernels.values():
@@ -99,16 +139,17 @@ def run_shape(name, tables, D, B, args, dev, lines, g):
     sel = 2 * B * T * 8
     xb, rb, buf = B * D * 4, B * ldr * 4, B * T * D * 4
     grads = xb + buf                          # dx + dE
+    trow = B * T * row_bytes(kind, D)         # the table rows read (fp32 rows: as many bytes as the buffer)
     total = {
-        FWD_FUSED: sel + buf + xb + rb,       # (the table rows read are as many bytes as the buffer)
-        FWD_TWO: sel + buf + 2 * buf + xb + rb,
-        FWD_LOOKUP: sel + buf + buf,
-        BWD_FUSED: sel + buf + xb + rb + grads,
+        FWD_FUSED: sel + trow + xb + rb,
+        FWD_TWO: sel + trow + 2 * buf + xb + rb,
+        FWD_LOOKUP: sel + trow + buf,
+        BWD_FUSED: sel + trow + xb + rb + grads,
         BWD_TWO: buf + xb + rb + grads,
     }
     lines.append("")
-    lines.append("### %s: %d tables (%.1f M rows, at most %d per table), D = %d, B = %d, one lookup per bag, int64 ids" %
-                 (name, T, sum(rows) / 1e6, max(rows), D, B))
+    lines.append("### %s: %d tables (%.1f M rows, at most %d per table), D = %d, B = %d, one lookup per bag, int64 ids%s" %
+                 (name, T, sum(rows) / 1e6, max(rows), D, B, "" if kind == "fp32" else ", %s rows" % kind))
     lines.append("")
     lines.append("| kernel | median ms | min | max | algorithmic MB | GB/s |")
     lines.append("|---|---|---|---|---|---|")
@@ -117,7 +158,8 @@ def run_shape(name, tables, D, B, args, dev, lines, g):
         med[k] = statistics.median(ts)
         lines.append("| %s | %.4f | %.4f | %.4f | %.1f | %.0f |" % (k, med[k], min(ts), max(ts), total[k] / 1e6, total[k] / med[k] / 1e6))
     lines.append("")
-    for what, f, t in (("forward", med[FWD_FUSED], med[FWD_TWO]), ("backward", med[BWD_FUSED], med[BWD_TWO])):
+    pairs = [("forward", FWD_FUSED, FWD_TWO)] + ([("backward", BWD_FUSED, BWD_TWO)] if fused_bwd is not None else [])
+    for what, f, t in ((w, med[a], med[b]) for w, a, b in pairs):
         lines.append("%s: fused %.4f ms, two-kernel form %.4f ms (fused is %.2fx %s)" %
                      (what, f, t, t / f if f <= t else f / t, "faster" if f < t else "SLOWER"))
 
@@ -128,16 +170,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--max-rows", type=int, default=10_000_000, help="cap of every table's row count")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rows", choices=ROW_KINDS, default="fp32", help="row kind of the tables: fp32 (default), bfloat16, 8- or 4-bit packed")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("ERROR: tools/bench_narrow_interact.py measures on the GPU; none found")
     import bench
     dev = torch.device("cuda:0")
-    lines = ["GPU: %s; torch %s; %d repeats after %d warm-up rounds, HIP events, median; all kernels in one process, alternating inside every round" %
-             (torch.cuda.get_device_name(0), torch.__version__, args.repeats, args.warmup)]
+    lines = ["GPU: %s; torch %s; %d repeats after %d warm-up rounds, HIP events, median; all kernels in one process, alternating inside every round%s" %
+             (torch.cuda.get_device_name(0), torch.__version__, args.repeats, args.warmup, "" if args.rows == "fp32" else "; %s tables" % args.rows)]
     g = torch.Generator(device=dev).manual_seed(7)
     for workload, D in (("criteo_terabyte", 64), ("criteo_kaggle", 16)):
-        tables = make_tables([min(n, args.max_rows) for n in bench.WORKLOADS[workload]["rows"]], D, dev, g)
+        tables = make_tables([min(n, args.max_rows) for n in bench.WORKLOADS[workload]["rows"]], D, dev, g, args.rows)
         for B in (2048, 65536):
             run_shape("%s rows" % workload, tables, D, B, args, dev, lines, g)
         del tables
