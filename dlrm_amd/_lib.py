@@ -99,6 +99,11 @@ SIGNATURES = {
                                            _vp, _vp, _i32, _vp]),
     "dlrm_interact_bwd_gather_qr": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _i32, _i32, _vp, _i64,
                                            _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dlrm_interact_gather_narrow_qr_ok": (_i32, [_i32, _i32]),
+    "dlrm_interact_fwd_gather_narrow_qr": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _i32, _i32, _vp,
+                                                  _i64, _vp, _vp, _i32, _vp]),
+    "dlrm_interact_bwd_gather_narrow_qr": (_i32, [_i64, _i32, _i32, _vp, _i64, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _i32, _i32, _vp,
+                                                  _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dlrm_emb_fwd_qr_pred": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, C.POINTER(_i32), _i32, _pp, _pp, _pi64, _i32, _vp, _i64, _vp, _i64, _vp,
                                     _vp, _i32, _vp]),
     "dlrm_emb_qr_bwd_split_pred": (_i32, [_i32, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _vp]),

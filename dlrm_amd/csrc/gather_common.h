@@ -1,5 +1,5 @@
 // gather_common.h — what the fused lookup + interaction kernels of interact_bf16.hip, interact_quant.hip, interact_qr.hip and
-// interact_narrow.hip share: the selector hand-off, the kernarg tables' way into LDS, the dR row staging, the grid rule and the host-side
+// the interact_narrow*.hip files share: the selector hand-off, the kernarg tables' way into LDS, the dR row staging, the grid rule and the host-side
 // argument checks.  The D = 128 pipeline built on these is gather_pipeline.h; the narrow kernels use this header alone.
 #pragma once
 #include "common.h"

@@ -51,8 +51,11 @@
 //   The launch keeps at most two workgroups (eight waves) per CU, so neither registers (512 per lane at one wave per SIMD, 256 at two) nor
 //   LDS limits any instantiation below what the grid asks for.
 //   The kernels live in interact_narrow.h, templated over a row source; this file instantiates them for fp32 rows (F32Rows) and
-//   interact_narrow_rows.hip for bfloat16 and packed rows.  The table was re-taken after that split: the figures did not change, and the
-//   device assembly of the fp32 instantiations is instruction for instruction what the untemplated kernels compiled to.
+//   interact_narrow_rows.hip for bfloat16 and packed rows, interact_narrow_qr.hip for quotient-remainder tables.  The table was re-taken
+//   after that split and after the selector side (OneArraySide) became part of the source: the figures did not change.  After the split
+//   the device assembly of the fp32 instantiations was instruction for instruction what the untemplated kernels compiled to; with the
+//   selector side it has the same instruction count and differs in symbol names and in the order / register numbers of the moves and
+//   stores of the error report (dlrm_report_bad_index).
 #include "interact_narrow.h"
 
 extern "C" int dlrm_interact_gather_narrow_ok(int F, int D) {

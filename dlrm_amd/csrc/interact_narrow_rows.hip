@@ -59,7 +59,7 @@ __device__ __forceinline__ float f16_bits_to_f32(unsigned h) {
 }
 
 // bfloat16 rows: 4 columns = one 8-byte load
-struct Bf16Rows {
+struct Bf16Rows : OneArraySide {
     static constexpr int LB = 8;
     static constexpr unsigned long long pitch(int D) { return 2ull * D; }
     using Regs = uint2;
@@ -76,7 +76,7 @@ struct Bf16Rows {
 
 // packed rows of dlrm_emb_quantize_rows
 template <int BITS> struct QuantRows;
-template <> struct QuantRows<8> {
+template <> struct QuantRows<8> : OneArraySide {
     static constexpr int LB = 4;
     static constexpr unsigned long long pitch(int D) { return (unsigned long long)D + 8; }
     struct Regs { unsigned q; float2 sb; };
@@ -94,7 +94,7 @@ template <> struct QuantRows<8> {
         return make_float4(o[0], o[1], o[2], o[3]);
     }
 };
-template <> struct QuantRows<4> {
+template <> struct QuantRows<4> : OneArraySide {
     static constexpr int LB = 2;
     static constexpr unsigned long long pitch(int D) { return (unsigned long long)D / 2 + 4; }
     struct Regs { unsigned q; unsigned sb; };

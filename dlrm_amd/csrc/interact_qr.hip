@@ -38,32 +38,16 @@
 //   One wave per SIMD may use 512 registers (the NB = 2 instantiations keep the 104 row registers of the next sample partly in AGPRs), so
 //   registers limit no launch; LDS bounds the workgroups per CU, as the last column says.
 #include "gather_pipeline.h"
-#include "qr_split.h"
+#include "gather_qr.h"
 
 namespace {
 
 constexpr int BI_SRCB = BI_D * 4;           // bytes of a table row (fp32)
 
-// feature f >= 1 is table f - 1; slot 0 is unused (feature 0 = x)
-struct QrArgs {
-    const void* w[GC_MAXF];                 // weight_q of a QR table, the rows of a plain one
-    const void* wr[GC_MAXF];                // weight_r (nullptr: plain table)
-    const void* idx[GC_MAXF];
-    const void* off[GC_MAXF];               // bag starts: verified to be 0, 1, 2, ... (one lookup per bag)
-    long long   rows[GC_MAXF];              // n: the categories of the table
-    long long   rows_q[GC_MAXF];            // ceil(n / c) (plain: n)
-    int         coll[GC_MAXF];              // collisions (0: plain table)
-    int         vs[GC_MAXF];                // backward: virtual slot of the table (of its q component) in gout
-    long long*  err;
-    DlrmPred    pred;
-    int         op_add;                     // the composition: + (DLRM_QR_ADD) or *
-};
-
 struct QrSource {
     using Args = QrArgs;
-    // what the owner lane hands to the lanes of a row: the weight_q row (GC_BAD: the zero row) and the weight_r row
-    struct Row { unsigned q, r; };
-    static constexpr int NTAB = 7;          // [0] w  [1] wr  [2] idx  [3] off  [4] rows  [5] rows_q  [6] coll | vs << 32
+    using Row = QrRow;                      // gather_qr.h: the argument block, the LDS tables and the index split, shared with the narrow kernels
+    static constexpr int NTAB = QR_NTAB;
     static constexpr bool DUP = true;
     static constexpr int passes(int nb) { return nb == 1 ? 8 : 13; }     // rows 1 .. 16 NB - 1 (F <= 27), two per pass
 
@@ -83,17 +67,7 @@ struct QrSource {
     // the rows of one sample, as loaded: weight_q (or the plain table) and weight_r, one 16-byte quad per lane and pass
     template <int NP> struct Regs { floatx4 q[NP], r[NP]; };
 
-    static __device__ __forceinline__ void args_to_lds(const Args& ba, long long* tab, int F) {
-        const int tid = threadIdx.x;
-#pragma unroll
-        for (int f = 1; f < GC_MAXF; ++f)
-            if (tid == f && f < F) {
-                tab[0 * GC_MAXF + f] = (long long)ba.w[f];   tab[1 * GC_MAXF + f] = (long long)ba.wr[f];
-                tab[2 * GC_MAXF + f] = (long long)ba.idx[f]; tab[3 * GC_MAXF + f] = (long long)ba.off[f];
-                tab[4 * GC_MAXF + f] = ba.rows[f];           tab[5 * GC_MAXF + f] = ba.rows_q[f];
-                tab[6 * GC_MAXF + f] = (long long)(((unsigned long long)(unsigned)ba.vs[f] << 32) | (unsigned)ba.coll[f]);
-            }
-    }
+    static __device__ __forceinline__ void args_to_lds(const Args& ba, long long* tab, int F) { qr_args_to_lds(ba, tab, F); }
 
     template <int NP>
     static __device__ __forceinline__ void lane_init(Lane<NP>& bl, const long long* tab, int F, int lane) {
@@ -115,19 +89,10 @@ struct QrSource {
         bl.coll = bl.own ? (int)(tab[6 * GC_MAXF + lane] & 0xFFFFFFFFLL) : 0;
     }
 
-    // the owner lane's checks and the index split (emb_qr.hip's: a lookup dlrm_emb_fwd_qr skips selects the zero row and is reported)
+    // the owner lane's checks and the index split (gather_qr.h)
     template <typename IT, int NP>
     static __device__ __forceinline__ Row sel_resolve(const Lane<NP>& bl, const Sel<IT>& sel, long long s, int lane, long long* err, bool live) {
-        Row o; o.q = GC_BAD; o.r = 0u;
-        if (bl.own && live) {
-            const long long id = (long long)sel.id, of = (long long)sel.off;
-            if (of != s) dlrm_report_bad_index(err, lane - 1, -(of + 1), -1);               // not a one-lookup-per-bag batch (rows = -1 marks it)
-            long long q = id, r = 0;
-            const bool ok = bl.coll ? qr_split(id, bl.rows, bl.coll, bl.rows_q, &q, &r) : dlrm_index_ok(id, bl.rows);
-            if (!ok) dlrm_report_bad_index(err, lane - 1, id, bl.rows);
-            else { o.q = (unsigned)q; o.r = (unsigned)r; }
-        }
-        return o;
+        return qr_sel_resolve<IT>(bl, sel, s, lane, err, live);
     }
 
     // row loads of one sample into registers: NP passes, two rows per pass, nothing waits here.  weight_r is c rows: it stays in the caches
@@ -206,37 +171,6 @@ __global__ __launch_bounds__(256) void interact_qr_mult_kernel(QrArgs ba, long l
         *(float4*)o = make_float4(d.x * sr.x, d.y * sr.y, d.z * sr.z, d.w * sr.w);
         *(float4*)(o + BI_D) = make_float4(d.x * sq.x, d.y * sq.y, d.z * sq.z, d.w * sq.w);
     }
-}
-
-// the argument block shared by both entry points; 0 or a DLRM_E_* code.  *n_qr: the QR tables of the call (Tv = F - 1 + *n_qr)
-int fill_args(QrArgs& ba, int F, const void* const* weight_host, const void* const* weight_r_host, const int64_t* rows_host,
-              const int32_t* collisions_host, const void* const* index_host, const void* const* offsets_host, int64_t* err,
-              const int32_t* pred_flag, int pred_nonzero, int* n_qr) {
-    ba.err = (long long*)err;
-    ba.pred = DlrmPred{(const int*)pred_flag, pred_nonzero};
-    int vslot = 0;
-    *n_qr = 0;
-    for (int f = 0; f < GC_MAXF; ++f) {
-        const bool live = f >= 1 && f < F;
-        const int t = live ? f - 1 : (F > 1 ? 0 : -1);                   // unused slots repeat table 0 (never dereferenced)
-        const int c = t >= 0 ? collisions_host[t] : 0;
-        ba.w[f] = t >= 0 ? weight_host[t] : nullptr;
-        ba.wr[f] = (t >= 0 && c > 0) ? weight_r_host[t] : nullptr;
-        ba.idx[f] = t >= 0 ? index_host[t] : nullptr;
-        ba.off[f] = t >= 0 ? offsets_host[t] : nullptr;
-        ba.rows[f] = t >= 0 ? rows_host[t] : 0;
-        ba.rows_q[f] = (t >= 0 && c > 0) ? (rows_host[t] + c - 1) / c : ba.rows[f];
-        ba.coll[f] = c;
-        ba.vs[f] = live ? vslot : 0;
-        if (live) {
-            if (!ba.w[f] || !ba.idx[f] || !ba.off[f] || ba.rows[f] <= 0 || c < 0 || (c > 0 && !ba.wr[f])) return DLRM_E_ARG;
-            if (ba.rows_q[f] > 0xFFFFFFFFLL) return DLRM_E_RANGE;         // row selectors travel as 32-bit values inside the kernels
-            if (!dlrm_aligned16(ba.w[f]) || (c > 0 && !dlrm_aligned16(ba.wr[f]))) return DLRM_E_MODE;      // a lane's 4 columns are one 16-byte load
-            vslot += c > 0 ? 2 : 1;
-            *n_qr += c > 0;
-        }
-    }
-    return 0;
 }
 
 }  // namespace

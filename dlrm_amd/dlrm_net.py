@@ -340,13 +340,14 @@ class DLRM_Net(nn.Module):
     # opt-in (launcher: --qr-fuse-interact): a model with quotient-remainder tables enters the fused lookup + interaction branch of
     # sequential_forward under the fp32 branch's conditions and runs csrc/interact_qr.hip (forward and backward) instead of dlrm_emb_fwd_qr + the
     # interaction kernels + dlrm_emb_qr_bwd_split through the pooled [B, T*D] buffer and the [B, 2*Tq*D] pooled sums — the same bits.  Off: a QR
-    # model runs exactly the two-kernel form.
+    # model runs exactly the two-kernel form.  D = 128; D = 16 / 32 / 64 (csrc/interact_narrow_qr.hip) only with fuse_narrow_interact set as well.
     fuse_qr_interact = False
     # opt-in (launcher: --narrow-fuse-interact): a model with plain fp32 tables of D = 16 / 32 / 64 enters the fused lookup + interaction branch
     # of sequential_forward under the fp32 branch's conditions and runs csrc/interact_narrow.hip (forward and backward) instead of dlrm_emb_fwd
     # + the generic interaction kernels through the pooled [B, T*D] buffer — the same bits.  Off: such a model runs exactly the two-kernel form.
     # Together with fuse_bf16_interact a bfloat16 model of those widths enters too (csrc/interact_narrow_rows.hip, forward and backward), and
-    # together with fuse_quant_interact a quantised model of those widths takes the narrow fused forward of that file (_quant_fused_forward).
+    # together with fuse_quant_interact a quantised model of those widths takes the narrow fused forward of that file (_quant_fused_forward),
+    # and together with fuse_qr_interact a model with QR tables of those widths enters too (csrc/interact_narrow_qr.hip, forward and backward).
     fuse_narrow_interact = False
     # opt-in (launcher: --fused-adagrad): a stock torch.optim.Adagrad that owns the tables (the reference's --optimizer=adagrad) gets the fused
     # exact Adagrad update (csrc/adagrad.hip dlrm_emb_bwd_adagrad) on ITS state[p]["sum"], the step pre-hook advances the tables'
@@ -1126,9 +1127,11 @@ class DLRM_Net(nn.Module):
         """The interaction output of a model with QR tables through csrc/interact_qr.hip (QRGatherInteractFunction), or None when the two-kernel
         form has to run: the conditions and the offsets state machine of the fp32 fused branch of sequential_forward — True / None -> the fused
         kernels alone; a device flag -> both forms behind the launch predicate, no host wait; False (proven ragged) -> None.  The update stays
-        the step-time one (bags.presort = None), update_in_backward included."""
+        the step-time one (bags.presort = None), update_in_backward included.  D = 16 / 32 / 64 run csrc/interact_narrow_qr.hip, only with
+        fuse_narrow_interact set as well and under _narrow_fused_forward's rule: None (a HIP graph is being captured) -> None too."""
+        narrow = self.fuse_narrow_interact and ops.gather_narrow_qr_ok(1 + T, D)
         if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and self.emb_bf16 is None
-                and ops.gather_qr_ok(1 + T, D) and not self._has_md(self.emb_l)
+                and (narrow or ops.gather_qr_ok(1 + T, D)) and not self._has_md(self.emb_l)
                 and not any(w is not None for w in (self.v_W_l or []))):
             return None
         bags = self._bags(lS_o, lS_i, None)
@@ -1143,12 +1146,12 @@ class DLRM_Net(nn.Module):
         else:
             proof = ops.offsets_are_iota_start(lS_o)
             state = proof if (proof is None or isinstance(proof, bool)) else "pending"
-        if state is False:
+        if state is False or (narrow and state is None):
             return None
         x = self.apply_mlp(dense_x, self.bot_l, consumer_applies_last_act=bool(rx))
         if proof is not None and state == "pending":
             state = ops.offsets_are_iota_finish(proof)
-        if state is False:
+        if state is False or (narrow and state is None):
             return None          # a ragged batch with nnz == B after all: the two-kernel form (the bottom tower runs again, into its slot)
         bags.iota_flag = state if isinstance(state, torch.Tensor) else None
         bags.presort = None

@@ -821,7 +821,8 @@ class NarrowGatherInteractFunction(Function):
 
 
 class QRGatherInteractFunction(Function):
-    """GatherInteractFunction for a table list with quotient-remainder tables (csrc/interact_qr.hip): R = [x | lower-triangular dots of
+    """GatherInteractFunction for a table list with quotient-remainder tables (csrc/interact_qr.hip at D = 128, csrc/interact_narrow_qr.hip at
+    D = 16 / 32 / 64: the calls dispatch on the width, the offsets-state logic below is the same): R = [x | lower-triangular dots of
     (x, the composed rows Wq[q] o Wr[r], plain rows)], the rows fetched and composed by the interaction kernel itself — the bits of
     QREmbeddingBagsFunction + InteractFunction without the [B, T*D] pooled buffer, its gradient or the [B, 2*Tq*D] pooled sums.
     spec = (rows, collisions, operation, keep_sums) and `vweights` = the VIRTUAL table list, as QREmbeddingBagsFunction takes them.  Backward
@@ -843,10 +844,12 @@ class QRGatherInteractFunction(Function):
         # `bags.iota_flag`: as GatherInteractFunction.forward — the fused kernel behind (flag, 0), the two-kernel form behind (flag, 1)
         flag = getattr(bags, "iota_flag", None)
         ly = saved = None
+        narrow = ops.gather_narrow_qr_ok(1 + T, D)
+        fwd = ops.interact_fwd_gather_narrow_qr if narrow else ops.interact_fwd_gather_qr
         if flag is None:
-            ops.interact_fwd_gather_qr(x, weights, weights_r, rows, collisions, op, bags, D, mode, R)
+            fwd(x, weights, weights_r, rows, collisions, op, bags, D, mode, R)
         else:
-            ops.interact_fwd_gather_qr(x, weights, weights_r, rows, collisions, op, bags, D, mode, R, pred=(flag, 0))
+            fwd(x, weights, weights_r, rows, collisions, op, bags, D, mode, R, pred=(flag, 0))
             ly = alloc2d(B, T * D, x)
             if keep_sums and op == "mult":
                 saved = torch.empty((B, 2 * D * sum(1 for c in collisions if c)), dtype=torch.float32, device=x.device)
@@ -856,7 +859,7 @@ class QRGatherInteractFunction(Function):
         ctx.tables = (weights, weights_r)
         ctx.vweights = vweights      # parameters (leaves) — kept by reference, not via save_for_backward
         ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
-        ctx.flag, ctx.saved = flag, saved
+        ctx.flag, ctx.saved, ctx.narrow = flag, saved, narrow
         if ly is None:
             ctx.save_for_backward(x)
         else:
@@ -876,7 +879,8 @@ class QRGatherInteractFunction(Function):
         dx = torch.empty((B, D), dtype=torch.float32, device=dR.device)
         gout = torch.empty((B, Tv * D), dtype=torch.float32, device=dR.device)
         pred = None if ctx.flag is None else (ctx.flag, 0)
-        ops.interact_bwd_gather_qr(x, weights, weights_r, rows, collisions, op, ctx.bags, D, ctx.self_interaction, dR, dx, gout, pred=pred)
+        bwd = ops.interact_bwd_gather_narrow_qr if ctx.narrow else ops.interact_bwd_gather_qr
+        bwd(x, weights, weights_r, rows, collisions, op, ctx.bags, D, ctx.self_interaction, dR, dx, gout, pred=pred)
         if ctx.flag is not None:
             if op == "mult" and ctx.saved is None:
                 raise RuntimeError("dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept")

@@ -103,12 +103,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--qr-fuse-interact", action="store_true",
                     help="with the reference's --qr-flag: fetch and compose the quotient / remainder rows inside the interaction kernels, "
                          "forward and backward (DLRM_Net.fuse_qr_interact; same bits as the default two-kernel form, no pooled [B, T*D] "
-                         "buffer and no pooled sums kept for the backward)")
+                         "buffer and no pooled sums kept for the backward); --arch-sparse-feature-size 128, or 16 / 32 / 64 together with "
+                         "--narrow-fuse-interact")
     ap.add_argument("--narrow-fuse-interact", action="store_true",
                     help="plain fp32 tables of --arch-sparse-feature-size 16 / 32 / 64: fetch the rows inside the interaction kernels, forward "
                          "and backward (DLRM_Net.fuse_narrow_interact; same bits as the default two-kernel form, no pooled [B, T*D] buffer).  "
                          "Together with --bf16-tables --bf16-fuse-interact the same for bfloat16 tables of those widths; with the reference's "
-                         "--quantize-emb-with-bit 4|8 --inference-only the fused forward over the packed tables of those widths")
+                         "--quantize-emb-with-bit 4|8 --inference-only the fused forward over the packed tables of those widths; with the "
+                         "reference's --qr-flag and --qr-fuse-interact the same for quotient-remainder tables of those widths")
     ap.add_argument("--fused-adagrad", action="store_true",
                     help="with the reference's --optimizer=adagrad: update the embedding tables with the fused exact Adagrad kernel on "
                          "torch.optim.Adagrad's own state (DLRM_Net.fused_adagrad; no sparse COO gradient, the dense parameters stay with "

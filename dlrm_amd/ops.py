@@ -1251,6 +1251,52 @@ def interact_bwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], wei
     _lib.check(rc, "dlrm_interact_bwd_gather_qr")
 
 
+# ---- ... and over QR tables of D = 16 / 32 / 64 (csrc/interact_narrow_qr.hip: the narrow kernels over a QR row source)
+def gather_narrow_qr_ok(F: int, D: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_narrow_qr_ok(int(F), int(D)))
+
+
+def interact_fwd_gather_narrow_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]],
+                                  rows: Sequence[int], collisions: Sequence[int], op: str, bags: BagBatch, D: int, self_interaction,
+                                  R: torch.Tensor, pred=None) -> torch.Tensor:
+    """interact_fwd_gather_qr for tables of D = 16 / 32 / 64 (dlrm_interact_fwd_gather_narrow_qr): the bits of emb_fwd_qr into a feature
+    buffer + interact_fwd, without that buffer."""
+    lib = _lib.load()
+    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
+    _req(R, "R", ndim=2)
+    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
+        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow_qr shape mismatch")
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_fwd_narrow_qr"):
+        rc = lib.dlrm_interact_fwd_gather_narrow_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
+                                                    bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()),
+                                                    _ld(R), C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_fwd_gather_narrow_qr")
+    return R
+
+
+def interact_bwd_gather_narrow_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]],
+                                  rows: Sequence[int], collisions: Sequence[int], op: str, bags: BagBatch, D: int, self_interaction,
+                                  dR: torch.Tensor, dx: torch.Tensor, gout: torch.Tensor, pred=None) -> None:
+    """interact_bwd_gather_qr for tables of D = 16 / 32 / 64 (dlrm_interact_bwd_gather_narrow_qr): dx and the gradient buffer of the
+    VIRTUAL table list with the bits of interact_bwd over (x, the buffer emb_fwd_qr wrote) + emb_qr_bwd_split."""
+    lib = _lib.load()
+    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
+    Tv = bags.T + sum(1 for c in collisions if c)
+    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(gout, "gout", ndim=2)
+    if dR.size(0) != bags.B or dx.size(0) != bags.B or gout.size(0) != bags.B or dx.size(1) < D or gout.size(1) < Tv * D:
+        raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow_qr shape mismatch")
+    st = _stream(dR)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed("emb_interact_bwd_narrow_qr"):
+        rc = lib.dlrm_interact_bwd_gather_narrow_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
+                                                    bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()),
+                                                    _ld(dR), C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(gout.data_ptr()), _ld(gout),
+                                                    C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, "dlrm_interact_bwd_gather_narrow_qr")
+
+
 def gather_quant_ok(F: int, D: int, bits: int) -> bool:
     return bool(_lib.load().dlrm_interact_gather_quant_ok(int(F), int(D), int(bits)))
 

@@ -512,6 +512,46 @@ int dlrm_emb_qr_bwd_split_pred(int T, int64_t B, int D, const int32_t* collision
                                const float* saved, int64_t saved_ld, float* gout, int64_t gout_ld,
                                const int32_t* pred_flag, int pred_nonzero, void* stream);
 
+/* Fused lookup + interaction over quotient-remainder (QR) tables of D = 16 / 32 / 64, FORWARD and BACKWARD (csrc/interact_narrow_qr.hip: the
+ * kernels of csrc/interact_narrow.h over a QR row source; symbols added, the ABI version stays 17).  Replace, for one-lookup-per-bag batches:
+ * dlrm_emb_fwd_qr + dlrm_interact_fwd, and dlrm_interact_bwd over the pooled buffer + dlrm_emb_qr_bwd_split, at the widths where those run the
+ * generic interaction kernels; the D = 128 forms are dlrm_interact_{fwd,bwd}_gather_qr, which keep refusing every other width.
+ * Operands: the argument lists of dlrm_interact_{fwd,bwd}_gather_qr, name for name — collisions_host[t] == 0 a plain fp32 table
+ * (weight_r_host[t] ignored), > 0 a QR table (weight_host[t] = weight_q [ceil(n / c), D], weight_r_host[t] = weight_r [c, D], rows_host[t] = n);
+ * op = DLRM_QR_MULT | DLRM_QR_ADD for the whole call; 1 <= F <= 32; any c >= 1.
+ *   forward : R is BIT-IDENTICAL to dlrm_emb_fwd_qr (saved = NULL) into a feature buffer + dlrm_interact_fwd (mode word 0 / 1 / 2, R[:, :D] = x,
+ *             zero-filled padding columns up to ldr).
+ *   backward: writes dx [B, D] and gout [B, >= Tv*D] (row stride gout_ld), the gradient buffer of the VIRTUAL table list as
+ *             dlrm_emb_qr_bwd_split lays it out (a QR table is a q slot then an r slot, Tv = T + Tq): dout * sr then dout * sq (MULT), dout
+ *             twice (ADD), one copy for a plain table.  dx and gout are BIT-IDENTICAL to dlrm_interact_bwd over (x, the buffer dlrm_emb_fwd_qr
+ *             wrote), DLRM_INTERACT_RELU_X included, followed by dlrm_emb_qr_bwd_split with the sums that forward would have saved.  For MULT a
+ *             second kernel of the same call gathers the two rows again and multiplies in place; one predicate covers both launches.
+ *   element = fmaf(1, Wq[q], +0) * fmaf(1, Wr[r], +0) (MULT) | ... + ... (ADD), each rounded once; a plain table fmaf(1, W[id], +0): -0.0 in
+ *             a table row becomes +0.0 before the composition.  q, r: the index split of dlrm_emb_fwd_qr (FLOAT32 quotient).
+ *   a lane's 4 columns of weight_q are one 16-byte load, a QR table costs a second 16-byte load of weight_r[r] through the caches; row byte
+ *   offsets are 64-bit;
+ *   offsets_host[t] : verified on the device to be 0, 1, 2, ... — a violation is reported through `err` with rows = -1;
+ *   a lookup dlrm_emb_fwd_qr skips (id outside [0, n), quotient >= ceil(n / c)) is reported ({1, table, id, n}) and contributes the ZERO row; its
+ *   gout rows are dout * (+0) (MULT) or dout (ADD), as the two-kernel form writes them.  pred_flag / pred_nonzero: launch predicate (NULL: run).
+ * dlrm_interact_gather_narrow_qr_ok (host only): 1 iff dlrm_interact_gather_narrow_ok(F, D); independent of the collisions.
+ * Return DLRM_E_MODE for shapes that function refuses, a weight_q / weight_r / plain table / x / R / dR / dx / gout not aligned to 16 bytes or a
+ * leading dimension that is not a multiple of 4; DLRM_E_RANGE for more than 0xFFFFFFFF rows in weight_q or in a plain table; DLRM_E_ARG for null
+ * operands (weight_r of a QR table included), rows <= 0, collisions < 0, an unknown op, leading dimensions smaller than their rows. */
+int dlrm_interact_gather_narrow_qr_ok(int F, int D);
+int dlrm_interact_fwd_gather_narrow_qr(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                       const void* const* weight_host, const void* const* weight_r_host, const int64_t* rows_host,
+                                       const int32_t* collisions_host, int op,
+                                       const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                       int self_interaction, float* R, int64_t ldr, int64_t* err,
+                                       const int32_t* pred_flag, int pred_nonzero, void* stream);
+int dlrm_interact_bwd_gather_narrow_qr(int64_t B, int F, int D, const float* x, int64_t x_ld,
+                                       const void* const* weight_host, const void* const* weight_r_host, const int64_t* rows_host,
+                                       const int32_t* collisions_host, int op,
+                                       const void* const* index_host, const void* const* offsets_host, int idx_bits,
+                                       int self_interaction, const float* dR, int64_t ldr,
+                                       float* dx, int64_t dx_ld, float* gout, int64_t gout_ld, int64_t* err,
+                                       const int32_t* pred_flag, int pred_nonzero, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * K6  dot interaction forward.
  * Replaces: torch.cat + torch.bmm + Z[:, li, lj] + torch.cat in DLRM_Net.interact_features
