@@ -1066,42 +1066,22 @@ class DLRM_Net(nn.Module):
             z = self._narrow_fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
             if z is not None:
                 return self._clamp(self.apply_mlp(z, self.top_l))
-        # (a bfloat16 model enters only with fuse_bf16_interact set, and then runs the kernels of csrc/interact_bf16.hip: ops.interact_*_gather
-        # dispatch on the tables' dtype)
-        bf16_fused = self.emb_bf16 is not None and self.fuse_bf16_interact
-        if (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
-                and (ops.gather_ok(1 + T, D) if self.emb_bf16 is None else (bf16_fused and ops.gather_bf16_ok(1 + T, D)))
-                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l)
-                and not any(w is not None for w in (self.v_W_l or []))):
-            bags = self._bags(lS_o, lS_i, None)
-            # nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the
-            # reference computes it): ops.offsets_are_iota (dlrm_amd/iota.py) proves offsets == arange(B) on the device, once per offsets tensor
-            # object (None = undecided, only while a HIP graph is being captured: GraphedTrainStep proves every incoming batch).
-            if all(n == B for n in bags.nnz) and all(e.weight.data_ptr() % 16 == 0 for e in self.emb_l):
-                # True / None (capturing): the fused kernels alone.  A tensor nobody vouched for: its proof is a device pass whose verdict
-                # STAYS on the device (round 6; until then the host waited for it, which ended the host's run-ahead once per step) —
-                # GatherInteractFunction enqueues the fused kernels and the two-kernel form, each behind the launch predicate, and the
-                # host goes on.  False (this tensor object was proven ragged before): the two kernels below.
-                # (DLRM_DEVICE_PREDICATE=0: the host-side proof of rounds 4-6 — started on its own stream, the bottom tower enqueued, then the
-                # host waits for the verdict — kept for A/B and for the tests of that path)
-                proof = None
-                if DEVICE_PREDICATE:
-                    state = ops.offsets_iota_state(lS_o)
-                else:
-                    proof = ops.offsets_are_iota_start(lS_o)
-                    state = proof if (proof is None or isinstance(proof, bool)) else "pending"
-                if state is not False:
-                    x = self.apply_mlp(dense_x, self.bot_l, consumer_applies_last_act=bool(rx))
-                    if proof is not None and state == "pending":
-                        state = ops.offsets_are_iota_finish(proof)
-                    if state is not False:
-                        bags.iota_flag = state if isinstance(state, torch.Tensor) else None
-                        # (bfloat16 tables: no update inside the backward — update_in_backward falls back to the step-time update)
-                        bags.presort = self._presort_for_backward if (self.update_in_backward and self.emb_bf16 is None) else None
-                        z = GatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x,
-                                                         *self._emb_weights(self.emb_l))
-                        return self._clamp(self.apply_mlp(z, self.top_l))
-                    del x        # a ragged batch with nnz == B after all: the two kernels below (the bottom tower runs again, into its slot)
+        # fp32 tables of D = 128 — or bfloat16 ones, only with fuse_bf16_interact set, through csrc/interact_bf16.hip: ops.interact_*_gather
+        # dispatch on the tables' dtype.  Undecided offsets (a HIP graph is being captured) run the fused kernels alone: GraphedTrainStep
+        # proves every incoming batch.
+        bf16 = self.emb_bf16 is not None
+        gate = self._fused_gate(dense_x, lS_o, lS_i, B,
+                                lambda: ((self.fuse_bf16_interact and ops.gather_bf16_ok(1 + T, D)) if bf16 else ops.gather_ok(1 + T, D))
+                                and not self._has_qr(self.emb_l),
+                                ops.ROW_KINDS["bf16"].align if bf16 else ops.GATHER_ALIGN)
+        if gate is not None:
+            bags, ws = gate
+            x = self._fused_bottom(dense_x, lS_o, bags, rx, none_fused=True)
+            if x is not None:
+                # (bfloat16 tables: no update inside the backward — update_in_backward falls back to the step-time update)
+                bags.presort = self._presort_for_backward if (self.update_in_backward and not bf16) else None
+                z = GatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x, *ws)
+                return self._clamp(self.apply_mlp(z, self.top_l))
         feat = torch.empty((B, n_out + T * D), dtype=torch.float32, device=dense_x.device)
         if self.overlap_streams and dense_x.is_cuda:
             # pooled lookups (HBM-bound) on the side stream beside the bottom-MLP GEMMs (MFMA-bound): they only meet at the
@@ -1123,110 +1103,106 @@ class DLRM_Net(nn.Module):
             z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)   # [B, round4(width)], zero padded
         return self._clamp(self.apply_mlp(z, self.top_l))
 
-    def _qr_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
-        """The interaction output of a model with QR tables through csrc/interact_qr.hip (QRGatherInteractFunction), or None when the two-kernel
-        form has to run: the conditions and the offsets state machine of the fp32 fused branch of sequential_forward — True / None -> the fused
-        kernels alone; a device flag -> both forms behind the launch predicate, no host wait; False (proven ragged) -> None.  The update stays
-        the step-time one (bags.presort = None), update_in_backward included.  D = 16 / 32 / 64 run csrc/interact_narrow_qr.hip, only with
-        fuse_narrow_interact set as well and under _narrow_fused_forward's rule: None (a HIP graph is being captured) -> None too."""
-        narrow = self.fuse_narrow_interact and ops.gather_narrow_qr_ok(1 + T, D)
-        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and self.emb_bf16 is None
-                and (narrow or ops.gather_qr_ok(1 + T, D)) and not self._has_md(self.emb_l)
-                and not any(w is not None for w in (self.v_W_l or []))):
+    def _fused_gate(self, dense_x, lS_o, lS_i, B, shape_ok, align):
+        """What every fused lookup + interaction path asks first: fuse_emb_interact, the dot interaction, a GPU batch, shape_ok() (the caller's
+        own rule: a kernel for this F, D and table kind, and the flags that admit it), no mixed-dimension table, no pooling weights, B lookups
+        per table, and every table's base address a multiple of `align` bytes (one lane's load: ops.RowKind.align).
+        -> (bags, the tables as the kernels see them), or None: the two-kernel form."""
+        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and shape_ok()
+                and not self._has_md(self.emb_l) and not any(w is not None for w in (self.v_W_l or []))):
             return None
         bags = self._bags(lS_o, lS_i, None)
-        qr = [isinstance(e, QREmbeddingBagHolder) for e in self.emb_l]
-        if not (all(n == B for n in bags.nnz)
-                and ops.qr_tables_aligned([e.weight_q if q else e.weight for e, q in zip(self.emb_l, qr)],
-                                          [e.weight_r if q else None for e, q in zip(self.emb_l, qr)])):
+        tables = self.emb_l_q if self.quantize_emb else self._emb_weights(self.emb_l)
+        if not (all(n == B for n in bags.nnz) and ops.tables_aligned(tables, align)):
             return None
+        return bags, tables
+
+    def _fused_bottom(self, dense_x, lS_o, bags, rx, none_fused, host_proof=True):
+        """The offsets decision of the fused paths, with the bottom tower in its middle -> the tower's output x with bags.iota_flag set, or None:
+        the two-kernel form (where the verdict came only after the tower, the tower runs again, into its slot).
+        nnz == B does not prove one lookup per bag (an empty bag next to a two-lookup bag is legal EmbeddingBag input and the reference
+        computes it): dlrm_amd/iota.py proves offsets == arange(B) on the device, once per offsets tensor object.  True -> the fused kernels
+        alone (iota_flag None).  A tensor nobody vouched for -> its proof is a device pass whose verdict STAYS on the device: iota_flag is that
+        flag, the Function enqueues the fused kernels and the two-kernel form, each behind the launch predicate, and the host goes on.  False
+        (this tensor object was proven ragged before) -> None.  None (undecided, only while a HIP graph is being captured) -> the fused
+        kernels alone if `none_fused`, else None.
+        DLRM_DEVICE_PREDICATE=0 with `host_proof`: the host-side proof — started on its own stream, the bottom tower enqueued, then the host
+        waits for the verdict — kept for A/B and for the tests of that path."""
         proof = None
-        if DEVICE_PREDICATE:
+        if DEVICE_PREDICATE or not host_proof:
             state = ops.offsets_iota_state(lS_o)
         else:
             proof = ops.offsets_are_iota_start(lS_o)
             state = proof if (proof is None or isinstance(proof, bool)) else "pending"
-        if state is False or (narrow and state is None):
+        if state is False or (state is None and not none_fused):
             return None
         x = self.apply_mlp(dense_x, self.bot_l, consumer_applies_last_act=bool(rx))
         if proof is not None and state == "pending":
             state = ops.offsets_are_iota_finish(proof)
-        if state is False or (narrow and state is None):
-            return None          # a ragged batch with nnz == B after all: the two-kernel form (the bottom tower runs again, into its slot)
+            if state is False or (state is None and not none_fused):
+                return None
         bags.iota_flag = state if isinstance(state, torch.Tensor) else None
+        return x
+
+    def _qr_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
+        """The interaction output of a model with QR tables through csrc/interact_qr.hip (QRGatherInteractFunction), or None when the two-kernel
+        form has to run.  D = 16 / 32 / 64 run csrc/interact_narrow_qr.hip, only with fuse_narrow_interact set as well, and then undecided offsets
+        take the two-kernel form (_narrow_fused_forward's rule).  The update stays the step-time one, update_in_backward included."""
+        narrow = self.fuse_narrow_interact and ops.gather_narrow_qr_ok(1 + T, D)
+        gate = self._fused_gate(dense_x, lS_o, lS_i, B, lambda: self.emb_bf16 is None and (narrow or ops.gather_qr_ok(1 + T, D)),
+                                ops.ROW_KINDS["narrow_qr" if narrow else "qr"].align)
+        x = None if gate is None else self._fused_bottom(dense_x, lS_o, gate[0], rx, none_fused=not narrow)
+        if x is None:
+            return None
+        bags, ws = gate
         bags.presort = None
-        return QRGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, self._qr_spec(self.emb_l), x,
-                                              *self._emb_weights(self.emb_l))
+        return QRGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, self._qr_spec(self.emb_l), x, *ws)
 
     def _narrow_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
         """The interaction output of a model with plain fp32 tables of D = 16 / 32 / 64 through csrc/interact_narrow.hip, or — only with
         fuse_bf16_interact set as well — of a model with bfloat16 tables of those widths through csrc/interact_narrow_rows.hip
-        (NarrowGatherInteractFunction dispatches on the tables' dtype), or None when the two-kernel form has to run: the conditions and the
-        offsets state machine of the fp32 fused branch of sequential_forward — True -> the fused kernels alone; a device flag -> both forms behind the launch predicate, no host
-        wait; False (proven ragged) -> None.  ONE difference: None (a HIP graph is being captured) -> None too, because GraphedTrainStep proves
-        the offsets of every incoming batch only for the shapes of ops.gather_ok.  The update stays the step-time one (bags.presort = None),
-        update_in_backward included: the update inside the backward exists at D = 128 only.  SGD and row-wise Adagrad over bfloat16 rows
-        receive dE through the same sink as from the two-kernel form."""
+        (NarrowGatherInteractFunction dispatches on the tables' dtype), or None when the two-kernel form has to run.  Undecided offsets take
+        the two-kernel form: GraphedTrainStep proves the offsets of every incoming batch only for the shapes of ops.gather_ok.  The update
+        stays the step-time one, update_in_backward included: the update inside the backward exists at D = 128 only."""
         bf16 = self.emb_bf16 is not None
-        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
-                and (ops.gather_narrow_ok(1 + T, D) if not bf16 else (self.fuse_bf16_interact and ops.gather_narrow_bf16_ok(1 + T, D)))
-                and not self._has_qr(self.emb_l) and not self._has_md(self.emb_l)
-                and not any(w is not None for w in (self.v_W_l or []))):
+        gate = self._fused_gate(dense_x, lS_o, lS_i, B,
+                                lambda: ((self.fuse_bf16_interact and ops.gather_narrow_bf16_ok(1 + T, D)) if bf16
+                                         else ops.gather_narrow_ok(1 + T, D)) and not self._has_qr(self.emb_l),
+                                ops.ROW_KINDS["narrow_bf16" if bf16 else "narrow"].align)
+        x = None if gate is None else self._fused_bottom(dense_x, lS_o, gate[0], rx, none_fused=False)
+        if x is None:
             return None
-        bags = self._bags(lS_o, lS_i, None)
-        # (a lane's 4 columns are one 16-byte load of an fp32 row, one 8-byte load of a bfloat16 row)
-        if not (all(n == B for n in bags.nnz) and all(e.weight.data_ptr() % (8 if bf16 else 16) == 0 for e in self.emb_l)):
-            return None
-        proof = None
-        if DEVICE_PREDICATE:
-            state = ops.offsets_iota_state(lS_o)
-        else:
-            proof = ops.offsets_are_iota_start(lS_o)
-            state = proof if (proof is None or isinstance(proof, bool)) else "pending"
-        if state is False or state is None:
-            return None
-        x = self.apply_mlp(dense_x, self.bot_l, consumer_applies_last_act=bool(rx))
-        if proof is not None and state == "pending":
-            state = ops.offsets_are_iota_finish(proof)
-        if state is False or state is None:
-            return None          # a ragged batch with nnz == B after all: the two-kernel form (the bottom tower runs again, into its slot)
-        bags.iota_flag = state if isinstance(state, torch.Tensor) else None
+        bags, ws = gate
         bags.presort = None
-        return NarrowGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x,
-                                                  *self._emb_weights(self.emb_l))
+        return NarrowGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x, *ws)
 
     def _quant_fused_forward(self, dense_x, lS_o, lS_i, B, T, D):
-        """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run:
-        `cat`, multi-hot bags, pooling weights, a width without a fused kernel, a forward that wants gradients (the fused kernel is forward
-        only), or fuse_quant_interact / fuse_emb_interact off.  D = 128 runs csrc/interact_quant.hip; D = 16 / 32 / 64 run
-        dlrm_interact_fwd_gather_narrow_quant (csrc/interact_narrow_rows.hip), only with fuse_narrow_interact set as well — same rules.
-        The offsets' one-lookup-per-bag state decides as in the fp32 branch of sequential_forward: True / None -> the fused kernel alone; a device flag -> the fused kernel behind (flag, 0) and
-        dlrm_emb_fwd_quant + dlrm_interact_fwd behind (flag, 1), no host wait; False -> None.  No autograd node: the tables are constants."""
+        """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run;
+        besides the common gate: fuse_quant_interact off, or a forward that wants gradients (the fused kernel is forward only).  D = 128 runs
+        csrc/interact_quant.hip; D = 16 / 32 / 64 run dlrm_interact_fwd_gather_narrow_quant (csrc/interact_narrow_rows.hip), only with
+        fuse_narrow_interact set as well — same rules.  The offsets' state is always the device-side one; undecided offsets run the fused
+        kernel alone.  No autograd node: the tables are constants, the bottom tower keeps its own last activation."""
         bits = self.quantize_bits
         narrow = self.fuse_narrow_interact and ops.gather_narrow_quant_ok(1 + T, D, bits)
-        if not (self.fuse_emb_interact and self.fuse_quant_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda
-                and (narrow or ops.gather_quant_ok(1 + T, D, bits)) and not any(w is not None for w in (self.v_W_l or []))):
+
+        def shape_ok():
+            if not (self.fuse_quant_interact and (narrow or ops.gather_quant_ok(1 + T, D, bits))):
+                return False
+            # (a forward whose bottom tower is being trained: InteractFunction carries the gradient of x)
+            return not (torch.is_grad_enabled() and (dense_x.requires_grad or (getattr(self.bot_l, "quant_bits", 32) == 32
+                                                                               and any(p_.requires_grad for p_ in self.bot_l.parameters()))))
+
+        gate = self._fused_gate(dense_x, lS_o, lS_i, B, shape_ok, ops.packed_align(bits))
+        x = None if gate is None else self._fused_bottom(dense_x, lS_o, gate[0], 0, none_fused=True, host_proof=False)
+        if x is None:
             return None
+        bags, qws = gate
         fused = ops.interact_fwd_gather_narrow_quant if narrow else ops.interact_fwd_gather_quant
-        if torch.is_grad_enabled() and (dense_x.requires_grad or (getattr(self.bot_l, "quant_bits", 32) == 32
-                                                                  and any(p_.requires_grad for p_ in self.bot_l.parameters()))):
-            return None          # (a forward whose bottom tower is being trained: InteractFunction carries the gradient of x)
-        bags = self._bags(lS_o, lS_i, None)
-        if not (all(n == B for n in bags.nnz) and ops.quant_tables_aligned(self.emb_l_q, bits)):
-            return None
-        state = ops.offsets_iota_state(lS_o)
-        if state is False:
-            return None
-        x = _functional._rowmajor(self.apply_mlp(dense_x, self.bot_l))
-        mode = self._interaction_mode()
-        R = torch.empty((B, _functional._round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
-        if not isinstance(state, torch.Tensor):
-            return fused(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R)
-        fused(x, self.emb_l_q, self.emb_q_rows, D, bits, bags, mode, R, pred=(state, 0))
-        ly = _functional.alloc2d(B, T * D, x)
-        ops.emb_fwd_quant(self.emb_l_q, self.emb_q_rows, D, bits, bags, ly, pred=(state, 1))
-        ops.interact_fwd((x, ly), D, mode, R, pred=(state, 1))
-        return R
+        x = _functional._rowmajor(x)
+        return _functional.gather_interact_fwd(
+            None, None, D, self._interaction_mode(), bags, x, T,
+            lambda mode, R, pred: fused(x, qws, self.emb_q_rows, D, bits, bags, mode, R, pred=pred),
+            lambda ly, pred: ops.emb_fwd_quant(qws, self.emb_q_rows, D, bits, bags, ly, pred=pred))
 
     def distributed_forward(self, dense_x, lS_o, lS_i):
         """Table-wise sharded embeddings + batch-split MLPs (dlrm_s_pytorch.py:528-585): every rank pools

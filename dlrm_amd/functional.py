@@ -706,6 +706,53 @@ class InteractFunction(Function):
         return (None, None, None, *dblocks) if ctx.order is None else (None, None, None, None, *dblocks)
 
 
+def gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, T, fused, lookup):
+    """The forward every fused lookup + interaction Function shares (and, with ctx = None, DLRM_Net._quant_fused_forward, which needs no autograd
+    node): R [B, round4(width)] = interaction of [x | one row per bag of T tables].
+    `bags.iota_flag` (a device int32, ops.offsets_iota_state in dlrm_amd/iota.py): whether the batch really has ONE lookup per bag is known on the
+    device only — nnz == B does not prove it.  Absent: fused(mode, R, None) runs alone.  Present: both implementations are enqueued with that launch
+    predicate (ABI 16) — fused(mode, R, (flag, 0)) runs if the flag is zero; lookup(ly, (flag, 1)) + the plain interaction (the reference's
+    apply_emb + interact_features as two kernels, through a pooled buffer ly that then has to live until backward) run if it is not.  The launches
+    that do not run return at once; the host never waits.  `lookup` also allocates whatever else its kind keeps for the backward."""
+    mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
+    R = torch.empty((x.size(0), _round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
+    flag = getattr(bags, "iota_flag", None)
+    ly = None
+    if flag is None:
+        fused(mode, R, None)
+    else:
+        fused(mode, R, (flag, 0))
+        ly = alloc2d(x.size(0), T * D, x)
+        lookup(ly, (flag, 1))
+        ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
+    if ctx is not None:
+        ctx.sink, ctx.bags, ctx.flag = sink, bags, flag
+        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
+        ctx.save_for_backward(*((x,) if ly is None else (x, ly)))
+    return R                                   # zero padding columns (what MLPFunction takes as is)
+
+
+def _gather_interact_bwd(ctx, x, dR, dx, fused, pooled_grad, split=None):
+    """... and the backward: fused(pred) writes dx and the gradient of the gathered rows; with a flag it runs behind (flag, 0), and behind
+    (flag, 1) the plain interaction backward over (x, the saved pooled buffer) writes dx and dE = pooled_grad(), which split(dE), if any, turns
+    into what the sink takes"""
+    fused(None if ctx.flag is None else (ctx.flag, 0))
+    if ctx.flag is not None:
+        dE = pooled_grad()
+        ops.interact_bwd((x, ctx.saved_tensors[1]), ctx.D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
+        if split is not None:
+            split(dE)
+
+
+def _flat_dx_dE(B, D, T, device):
+    """dx [B, D] | dE [B, T*D] out of one allocation"""
+    flat = torch.empty(B * (1 + T) * D, dtype=torch.float32, device=device)
+    return flat[:B * D].view(B, D), flat[B * D:].view(B, T * D)
+
+
+_NO_SINK = "dlrm_amd: embedding backward needs a gradient sink (fused update)"
+
+
 class GatherInteractFunction(Function):
     """apply_emb + interact_features fused for one-lookup-per-bag batches (dlrm_s_pytorch.py:407-462 + 483-504):
     R = [x | lower-triangular dots of (x, E_1[idx_1], ..., E_T[idx_T])], the embedding rows fetched by the interaction kernel
@@ -715,52 +762,34 @@ class GatherInteractFunction(Function):
 
     @staticmethod
     def forward(ctx, sink, D, self_interaction, bags, x, *weights):
-        # `bags.iota_flag` (a device int32, ops.offsets_iota_state in dlrm_amd/iota.py): whether the batch really has ONE lookup per bag is known on the device
-        # only — nnz == B does not prove it.  Both implementations are enqueued with that launch predicate (ABI 16): the fused kernel runs if
-        # the flag is zero; dlrm_emb_fwd + the plain interaction (the reference's apply_emb + interact_features as two kernels, through a pooled
-        # buffer that then has to live until backward) run if it is not.  The launches that do not run return at once; the host never waits.
         x = _rowmajor(x)
-        F = 1 + len(weights)
-        mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
-        Wd = ops.interact_out_width(F, D, mode)
-        R = torch.empty((x.size(0), _round4(Wd)), dtype=torch.float32, device=x.device)
-        flag = getattr(bags, "iota_flag", None)
-        ly = None
-        if flag is None:
-            ops.interact_fwd_gather(x, weights, bags, D, mode, R)
-        else:
-            ops.interact_fwd_gather(x, weights, bags, D, mode, R, pred=(flag, 0))
-            ly = alloc2d(x.size(0), len(weights) * D, x)
-            # (bfloat16 tables: the fused call above dispatched on the dtype; so does the lookup of the two-kernel form)
-            (ops.emb_fwd_bf16 if weights[0].dtype == torch.bfloat16 else ops.emb_fwd)(weights, bags, ly, pred=(flag, 1))
-            ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
-        ctx.sink, ctx.bags, ctx.weights = sink, bags, weights
-        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
-        ctx.flag = flag
-        if ly is None:
-            ctx.save_for_backward(x)
-        else:
-            ctx.save_for_backward(x, ly)
-        return R                                   # [B, round4(width)], zero padding columns (what MLPFunction takes as is)
+        ctx.weights = weights
+        # (bfloat16 tables: ops.interact_fwd_gather dispatches on the dtype; so does the lookup of the two-kernel form)
+        return gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, len(weights),
+                                   lambda mode, R, pred: ops.interact_fwd_gather(x, weights, bags, D, mode, R, pred=pred),
+                                   lambda ly, pred: (ops.emb_fwd_bf16 if weights[0].dtype == torch.bfloat16 else ops.emb_fwd)(
+                                       weights, bags, ly, pred=pred))
 
     @staticmethod
     def backward(ctx, dR):
         x = ctx.saved_tensors[0]
         dR = _rowmajor(dR)
-        B, D, T = x.size(0), ctx.D, len(ctx.weights)
-        flat = torch.empty(B * (1 + T) * D, dtype=torch.float32, device=dR.device)
-        dx, dE = flat[:B * D].view(B, D), flat[B * D:].view(B, T * D)
+        T = len(ctx.weights)
+        dx, dE = _flat_dx_dE(x.size(0), ctx.D, T, dR.device)
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         # `bags.presort` (DLRM_Net._presort_for_backward; None unless the model was told to update in backward and knows its SGD optimizer): the
         # sort of the sparse update runs NOW and the fused kernel takes the SGD step of every row a single lookup of the batch names (its table
         # row is staged in LDS anyway) — ops.Presorted travels to the sink, which applies the rest from the same sorted workspace
-        pred = None if ctx.flag is None else (ctx.flag, 0)
         presort = getattr(ctx.bags, "presort", None)
-        pre = presort(ctx.weights, ctx.bags, pred) if presort is not None else None
-        ops.interact_bwd_gather(x, ctx.weights, ctx.bags, D, ctx.self_interaction, dR, dx, dE, pred=pred, presorted=pre)
-        if ctx.flag is not None:
-            ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
+        pre = None
+
+        def fused(pred):
+            nonlocal pre
+            pre = presort(ctx.weights, ctx.bags, pred) if presort is not None else None
+            ops.interact_bwd_gather(x, ctx.weights, ctx.bags, ctx.D, ctx.self_interaction, dR, dx, dE, pred=pred, presorted=pre)
+
+        _gather_interact_bwd(ctx, x, dR, dx, fused, lambda: dE)
         if pre is None:
             ctx.sink(ctx.weights, ctx.bags, dE)
         else:
@@ -771,60 +800,40 @@ class GatherInteractFunction(Function):
 class NarrowGatherInteractFunction(Function):
     """GatherInteractFunction for plain fp32 tables of D = 16 / 32 / 64 (csrc/interact_narrow.hip), or bfloat16 tables of those widths
     (csrc/interact_narrow_rows.hip; the calls dispatch on the tables' dtype): the bits of EmbeddingBagsFunction / BF16EmbeddingBagsFunction +
-    InteractFunction without the [B, T*D] pooled buffer.  With `bags.iota_flag` absent the fused kernels run alone; with a device flag they run
-    behind (flag, 0) and dlrm_emb_fwd (dlrm_emb_fwd_bf16) + the generic interaction kernels behind (flag, 1), the pooled buffer saved for the
-    backward.  dE goes to `sink` either way: one update call per step.  There is no update inside the backward at these widths (`bags.presort` is not read)."""
+    InteractFunction without the [B, T*D] pooled buffer.  dE goes to `sink` with or without a flag: one update call per step.  There is no update
+    inside the backward at these widths (`bags.presort` is not read)."""
 
     @staticmethod
     def forward(ctx, sink, D, self_interaction, bags, x, *weights):
         x = _rowmajor(x)
-        F = 1 + len(weights)
-        mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
-        R = torch.empty((x.size(0), _round4(ops.interact_out_width(F, D, mode))), dtype=torch.float32, device=x.device)
-        flag = getattr(bags, "iota_flag", None)
-        ly = None
-        # (bfloat16 tables: the kernels of csrc/interact_narrow_rows.hip, and emb_fwd_bf16 as the lookup of the two-kernel form)
-        bf16 = ops._gather_tables_bf16(weights, "NarrowGatherInteractFunction")
+        ctx.weights = weights
+        ctx.bf16 = bf16 = ops._gather_tables_bf16(weights, "NarrowGatherInteractFunction")
         fwd = ops.interact_fwd_gather_narrow_bf16 if bf16 else ops.interact_fwd_gather_narrow
-        if flag is None:
-            fwd(x, weights, bags, D, mode, R)
-        else:
-            fwd(x, weights, bags, D, mode, R, pred=(flag, 0))
-            ly = alloc2d(x.size(0), len(weights) * D, x)
-            (ops.emb_fwd_bf16 if bf16 else ops.emb_fwd)(weights, bags, ly, pred=(flag, 1))
-            ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
-        ctx.sink, ctx.bags, ctx.weights = sink, bags, weights
-        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
-        ctx.flag, ctx.bf16 = flag, bf16
-        if ly is None:
-            ctx.save_for_backward(x)
-        else:
-            ctx.save_for_backward(x, ly)
-        return R                                   # [B, round4(width)], zero padding columns (what MLPFunction takes as is)
+        lookup = ops.emb_fwd_bf16 if bf16 else ops.emb_fwd
+        return gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, len(weights),
+                                   lambda mode, R, pred: fwd(x, weights, bags, D, mode, R, pred=pred),
+                                   lambda ly, pred: lookup(weights, bags, ly, pred=pred))
 
     @staticmethod
     def backward(ctx, dR):
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         x = ctx.saved_tensors[0]
         dR = _rowmajor(dR)
-        B, D, T = x.size(0), ctx.D, len(ctx.weights)
-        flat = torch.empty(B * (1 + T) * D, dtype=torch.float32, device=dR.device)
-        dx, dE = flat[:B * D].view(B, D), flat[B * D:].view(B, T * D)
-        pred = None if ctx.flag is None else (ctx.flag, 0)
+        T = len(ctx.weights)
+        dx, dE = _flat_dx_dE(x.size(0), ctx.D, T, dR.device)
         bwd = ops.interact_bwd_gather_narrow_bf16 if ctx.bf16 else ops.interact_bwd_gather_narrow
-        bwd(x, ctx.weights, ctx.bags, D, ctx.self_interaction, dR, dx, dE, pred=pred)
-        if ctx.flag is not None:
-            ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
+        _gather_interact_bwd(ctx, x, dR, dx,
+                             lambda pred: bwd(x, ctx.weights, ctx.bags, ctx.D, ctx.self_interaction, dR, dx, dE, pred=pred), lambda: dE)
         ctx.sink(ctx.weights, ctx.bags, dE)
         return (None, None, None, None, dx) + (None,) * T
 
 
 class QRGatherInteractFunction(Function):
     """GatherInteractFunction for a table list with quotient-remainder tables (csrc/interact_qr.hip at D = 128, csrc/interact_narrow_qr.hip at
-    D = 16 / 32 / 64: the calls dispatch on the width, the offsets-state logic below is the same): R = [x | lower-triangular dots of
-    (x, the composed rows Wq[q] o Wr[r], plain rows)], the rows fetched and composed by the interaction kernel itself — the bits of
-    QREmbeddingBagsFunction + InteractFunction without the [B, T*D] pooled buffer, its gradient or the [B, 2*Tq*D] pooled sums.
+    D = 16 / 32 / 64: the calls dispatch on the width): R = [x | lower-triangular dots of (x, the composed rows Wq[q] o Wr[r], plain rows)], the
+    rows fetched and composed by the interaction kernel itself — the bits of QREmbeddingBagsFunction + InteractFunction without the [B, T*D]
+    pooled buffer, its gradient or the [B, 2*Tq*D] pooled sums.
     spec = (rows, collisions, operation, keep_sums) and `vweights` = the VIRTUAL table list, as QREmbeddingBagsFunction takes them.  Backward
     gathers the rows again, writes dx and the gradient buffer of the virtual list and hands (virtual weights, virtual bags, buffer) to `sink`:
     exactly what QREmbeddingBagsFunction.backward hands over."""
@@ -838,38 +847,25 @@ class QRGatherInteractFunction(Function):
             weights.append(next(it))
             weights_r.append(next(it) if c else None)
         x = _rowmajor(x)
-        B, T = x.size(0), len(weights)
-        mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
-        R = torch.empty((B, _round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
-        # `bags.iota_flag`: as GatherInteractFunction.forward — the fused kernel behind (flag, 0), the two-kernel form behind (flag, 1)
-        flag = getattr(bags, "iota_flag", None)
-        ly = saved = None
-        narrow = ops.gather_narrow_qr_ok(1 + T, D)
-        fwd = ops.interact_fwd_gather_narrow_qr if narrow else ops.interact_fwd_gather_qr
-        if flag is None:
-            fwd(x, weights, weights_r, rows, collisions, op, bags, D, mode, R)
-        else:
-            fwd(x, weights, weights_r, rows, collisions, op, bags, D, mode, R, pred=(flag, 0))
-            ly = alloc2d(B, T * D, x)
-            if keep_sums and op == "mult":
-                saved = torch.empty((B, 2 * D * sum(1 for c in collisions if c)), dtype=torch.float32, device=x.device)
-            ops.emb_fwd_qr(weights, weights_r, rows, collisions, op, bags, ly, saved, pred=(flag, 1))
-            ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
-        ctx.sink, ctx.bags, ctx.spec = sink, bags, spec
-        ctx.tables = (weights, weights_r)
+        T = len(weights)
+        ctx.spec, ctx.tables = spec, (weights, weights_r)
         ctx.vweights = vweights      # parameters (leaves) — kept by reference, not via save_for_backward
-        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
-        ctx.flag, ctx.saved, ctx.narrow = flag, saved, narrow
-        if ly is None:
-            ctx.save_for_backward(x)
-        else:
-            ctx.save_for_backward(x, ly)
-        return R                                   # [B, round4(width)], zero padding columns (what MLPFunction takes as is)
+        ctx.saved = None
+        ctx.narrow = narrow = ops.gather_narrow_qr_ok(1 + T, D)
+        fwd = ops.interact_fwd_gather_narrow_qr if narrow else ops.interact_fwd_gather_qr
+
+        def lookup(ly, pred):
+            if keep_sums and op == "mult":
+                ctx.saved = torch.empty((x.size(0), 2 * D * sum(1 for c in collisions if c)), dtype=torch.float32, device=x.device)
+            ops.emb_fwd_qr(weights, weights_r, rows, collisions, op, bags, ly, ctx.saved, pred=pred)
+
+        return gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, T,
+                                   lambda mode, R, pred: fwd(x, weights, weights_r, rows, collisions, op, bags, D, mode, R, pred=pred), lookup)
 
     @staticmethod
     def backward(ctx, dR):
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         x = ctx.saved_tensors[0]
         dR = _rowmajor(dR)
         rows, collisions, op, _ = ctx.spec
@@ -878,15 +874,17 @@ class QRGatherInteractFunction(Function):
         Tv = T + sum(1 for c in collisions if c)
         dx = torch.empty((B, D), dtype=torch.float32, device=dR.device)
         gout = torch.empty((B, Tv * D), dtype=torch.float32, device=dR.device)
-        pred = None if ctx.flag is None else (ctx.flag, 0)
         bwd = ops.interact_bwd_gather_narrow_qr if ctx.narrow else ops.interact_bwd_gather_qr
-        bwd(x, weights, weights_r, rows, collisions, op, ctx.bags, D, ctx.self_interaction, dR, dx, gout, pred=pred)
-        if ctx.flag is not None:
+
+        def pooled_grad():
             if op == "mult" and ctx.saved is None:
                 raise RuntimeError("dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept")
-            dE = torch.empty((B, T * D), dtype=torch.float32, device=dR.device)
-            ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
-            ops.emb_qr_bwd_split(collisions, op, D, dE, ctx.saved, gout, pred=(ctx.flag, 1))
+            return torch.empty((B, T * D), dtype=torch.float32, device=dR.device)
+
+        _gather_interact_bwd(ctx, x, dR, dx,
+                             lambda pred: bwd(x, weights, weights_r, rows, collisions, op, ctx.bags, D, ctx.self_interaction, dR, dx, gout,
+                                              pred=pred),
+                             pooled_grad, lambda dE: ops.emb_qr_bwd_split(collisions, op, D, dE, ctx.saved, gout, pred=(ctx.flag, 1)))
         ctx.sink(ctx.vweights, ops.qr_virtual_bags(rows, collisions, ctx.bags), gout)
         return (None, None, None, None, None, dx) + (None,) * len(ctx.vweights)
 

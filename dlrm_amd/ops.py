@@ -11,7 +11,7 @@ import os
 import time
 
 import ctypes as C
-from typing import List, Optional, Sequence, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -1107,7 +1107,7 @@ def wait_spinning(ev, limit_s: Optional[float] = None) -> None:
 
 def _gather_one_lookup(bags: BagBatch, tables: int) -> None:
     """what every fused lookup + interaction wrapper refuses first: the kernels fetch ONE row per bag and apply no pooling weight"""
-    if bags.T != tables or any(n != bags.B for n in bags.nnz):
+    if bags.T != tables or bags.nnz.count(bags.B) != len(bags.nnz):       # (a list of ints: count() instead of a generator per call)
         raise RuntimeError("dlrm_amd: the fused embedding + interaction path needs exactly one lookup per bag")
     if bags._psw is not None:
         raise RuntimeError("dlrm_amd: the fused embedding + interaction path does not take per-sample weights")
@@ -1126,15 +1126,6 @@ def _gather_desc(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatc
     return F, _lib.ptr_array(ptrs), _lib.i64_array(lds), gidx, goff, rows
 
 
-def gather_bf16_ok(F: int, D: int) -> bool:
-    return bool(_lib.load().dlrm_interact_gather_bf16_ok(int(F), int(D)))
-
-
-def bf16_tables_aligned(weights: Sequence[torch.Tensor]) -> bool:
-    """what the fused bf16 kernels need of the tables: a lane's 8 columns are one 16-byte load"""
-    return all(w.data_ptr() % 16 == 0 for w in weights)
-
-
 def _gather_tables_bf16(weights: Sequence[torch.Tensor], what: str) -> bool:
     """True: every table is torch.bfloat16 (the calls of csrc/interact_bf16.hip); False: none is; a mixture is refused"""
     n16 = sum(1 for w in weights if w.dtype == torch.bfloat16)
@@ -1143,35 +1134,119 @@ def _gather_tables_bf16(weights: Sequence[torch.Tensor], what: str) -> bool:
     return n16 > 0
 
 
-def _gather_desc_tables(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, weights_desc, kind: str):
-    """_gather_desc for the one-array table kinds: the same refusals; table t is feature t + 1.  weights_desc: _bf16_weights_desc (kind
-    "bf16") or _weights_desc (fp32 tables of D = 16 / 32 / 64, kind "narrow")"""
-    _gather_one_lookup(bags, len(weights))
+# ---- fused lookup + interaction over every table kind but fp32 at D = 128: bf16 (csrc/interact_bf16.hip), fp32 / bf16 / packed rows of D = 16 /
+# 32 / 64 (interact_narrow.hip, interact_narrow_rows.hip), QR at both widths (interact_qr.hip, interact_narrow_qr.hip), packed at D = 128
+# (interact_quant.hip).  Their C calls share ONE argument list
+#     (B, F, D, [bits,] x, ldx, <the tables>, idx, off, idx_bits, mode, R | dR, ld, [dx, ld, dE | gout, ld,] err, flag, nonzero, stream)
+# and one set of refusals, so there is one forward and one backward wrapper (_fwd_gather_rows, _bwd_gather_rows) over ROW_KINDS, which holds
+# what differs.  `tables` is the argument list of the kind's descriptor, the list of table tensors first; desc(*tables) checks the tables and
+# returns (their embedding dimension, then the ctypes arguments between `x, ldx` and `idx, off`).  These calls are on the per-step host
+# path: the entries hold finished strings and the descriptors are called without a frame in between.
+def _qr_rows_desc(weights, weights_r, rows, collisions, op):
+    return _qr_desc(weights, weights_r, rows, collisions) + (_qr_op(op),)
+
+
+def _packed_rows_desc(qweights, rows, D, bits, T, what):
+    return (D,) + _packed_tables_desc(qweights, rows, D, bits, T, what)
+
+
+class RowKind(NamedTuple):
+    fwd: str                # the C symbols; bwd None: forward only (packed tables are constants)
+    bwd: Optional[str]
+    timer_fwd: str          # the timer categories
+    timer_bwd: Optional[str]
+    desc: Callable          # see above
+    word: str               # the kind in "the fused <word> embedding + interaction path: shape mismatch"
+    align: int              # bytes a table's base address is a multiple of: one lane's load of a row (packed: of 8-bit rows; 4-bit rows half)
+
+
+ROW_KINDS = {
+    "bf16": RowKind("dlrm_interact_fwd_gather_bf16", "dlrm_interact_bwd_gather_bf16", "emb_interact_fwd_bf16", "emb_interact_bwd_bf16",
+                    _bf16_weights_desc, "bf16", 16),
+    "narrow": RowKind("dlrm_interact_fwd_gather_narrow", "dlrm_interact_bwd_gather_narrow", "emb_interact_fwd_narrow", "emb_interact_bwd_narrow",
+                      _weights_desc, "narrow", 16),
+    "narrow_bf16": RowKind("dlrm_interact_fwd_gather_narrow_bf16", "dlrm_interact_bwd_gather_narrow_bf16", "emb_interact_fwd_narrow_bf16",
+                           "emb_interact_bwd_narrow_bf16", _bf16_weights_desc, "narrow bf16", 8),
+    "qr": RowKind("dlrm_interact_fwd_gather_qr", "dlrm_interact_bwd_gather_qr", "emb_interact_fwd_qr", "emb_interact_bwd_qr",
+                  _qr_rows_desc, "QR", 16),
+    "narrow_qr": RowKind("dlrm_interact_fwd_gather_narrow_qr", "dlrm_interact_bwd_gather_narrow_qr", "emb_interact_fwd_narrow_qr",
+                         "emb_interact_bwd_narrow_qr", _qr_rows_desc, "QR", 16),
+    "quant": RowKind("dlrm_interact_fwd_gather_quant", None, "emb_interact_fwd_quant", None, _packed_rows_desc, "quantised", 8),
+    "narrow_quant": RowKind("dlrm_interact_fwd_gather_narrow_quant", None, "emb_interact_fwd_narrow_quant", None, _packed_rows_desc,
+                            "narrow quantised", 8),
+}
+GATHER_ALIGN = 16       # ... and of the fp32 D = 128 kernels (dlrm_interact_fwd_gather): a lane's 4 columns are one 16-byte load
+
+
+def _fwd_gather_rows(kind: str, x: torch.Tensor, tables, bags: BagBatch, D: int, mode, R: torch.Tensor, pred, lead=()) -> torch.Tensor:
+    """R = interaction of [x | one row per bag of the tables of `kind`]; table t is feature t + 1.  lead: the scalars in front of x (packed:
+    bits).  pred: see _pred_args; None = (NULL, 0), the launch always runs."""
+    k = ROW_KINDS[kind]
+    lib = _lib.load()
+    _gather_one_lookup(bags, len(tables[0]))
     _req(x, "x", ndim=2)
-    Dw, wp, rows = weights_desc(weights)
-    if Dw != D or x.size(1) != D or x.size(0) != bags.B:
-        raise RuntimeError("dlrm_amd: the fused %s embedding + interaction path: shape mismatch" % kind)
-    return 1 + bags.T, wp, rows
+    d = k.desc(*tables)
+    if d[0] != D or x.size(1) != D or x.size(0) != bags.B:
+        raise RuntimeError("dlrm_amd: the fused %s embedding + interaction path: shape mismatch" % k.word)
+    _req(R, "R", ndim=2)
+    F = 1 + bags.T
+    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, mode):
+        raise RuntimeError("dlrm_amd: %s shape mismatch" % k.fwd[5:])
+    st = _stream(R)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed(k.timer_fwd):
+        rc = getattr(lib, k.fwd)(bags.B, F, D, *lead, C.c_void_p(x.data_ptr()), _ld(x), *d[1:], bags._idx, bags._off, bags.idx_bits,
+                                 int(mode), C.c_void_p(R.data_ptr()), _ld(R), C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, k.fwd)
+    return R
+
+
+def _bwd_gather_rows(kind: str, x: torch.Tensor, tables, bags: BagBatch, D: int, mode, dR: torch.Tensor, dx: torch.Tensor, dE: torch.Tensor,
+                     grad_tables: int, pred) -> None:
+    """dx [B, D] = gradient of x; dE [B, >= grad_tables * D] = gradients of the gathered rows (QR: `gout`, the buffer of the VIRTUAL table
+    list, grad_tables = its length).  `mode | INTERACT_RELU_X` as interact_bwd."""
+    k = ROW_KINDS[kind]
+    if k.bwd is None:
+        raise RuntimeError("dlrm_amd: the fused %s embedding + interaction path is forward only" % k.word)
+    lib = _lib.load()
+    _gather_one_lookup(bags, len(tables[0]))
+    _req(x, "x", ndim=2)
+    d = k.desc(*tables)
+    if d[0] != D or x.size(1) != D or x.size(0) != bags.B:
+        raise RuntimeError("dlrm_amd: the fused %s embedding + interaction path: shape mismatch" % k.word)
+    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE | gout", ndim=2)
+    if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < grad_tables * D:
+        raise RuntimeError("dlrm_amd: %s shape mismatch" % k.bwd[5:])
+    st = _stream(dR)
+    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
+    with _timed(k.timer_bwd):
+        rc = getattr(lib, k.bwd)(bags.B, 1 + bags.T, D, C.c_void_p(x.data_ptr()), _ld(x), *d[1:], bags._idx, bags._off, bags.idx_bits,
+                                 int(mode), C.c_void_p(dR.data_ptr()), _ld(dR), C.c_void_p(dx.data_ptr()), _ld(dx),
+                                 C.c_void_p(dE.data_ptr()), _ld(dE), C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
+    _lib.check(rc, k.bwd)
+
+
+def tables_aligned(tensors, align: int) -> bool:
+    """every table's base address a multiple of `align` bytes (RowKind.align, GATHER_ALIGN)"""
+    return all(t.data_ptr() % align == 0 for t in tensors)
+
+
+def gather_bf16_ok(F: int, D: int) -> bool:
+    return bool(_lib.load().dlrm_interact_gather_bf16_ok(int(F), int(D)))
+
+
+def bf16_tables_aligned(weights: Sequence[torch.Tensor]) -> bool:
+    """what the fused bf16 kernels need of the tables: a lane's 8 columns are one 16-byte load"""
+    return tables_aligned(weights, ROW_KINDS["bf16"].align)
 
 
 def interact_fwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction: bool,
                         R: torch.Tensor, pred=None) -> torch.Tensor:
     """R = interaction of [x | one-hot embedding rows], the rows fetched by the kernel itself (no pooled-embedding buffer).
     Tables all fp32, or all torch.bfloat16 (dlrm_interact_fwd_gather_bf16: the bits of emb_fwd_bf16 + interact_fwd)."""
-    lib = _lib.load()
     if _gather_tables_bf16(weights, "interact_fwd_gather"):
-        F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "bf16")
-        _req(R, "R", ndim=2)
-        if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-            raise RuntimeError("dlrm_amd: interact_fwd_gather shape mismatch")
-        st = _stream(R)
-        flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-        with _timed("emb_interact_fwd_bf16"):
-            rc = lib.dlrm_interact_fwd_gather_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
-                                                   bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
-                                                   C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-        _lib.check(rc, "dlrm_interact_fwd_gather_bf16")
-        return R
+        return _fwd_gather_rows("bf16", x, (weights,), bags, D, self_interaction, R, pred)
+    lib = _lib.load()
     F, p, ld, gidx, goff, rows = _gather_desc(x, weights, bags, D)
     _req(R, "R", ndim=2)
     if R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
@@ -1196,17 +1271,7 @@ def gather_qr_ok(F: int, D: int) -> bool:
 
 def qr_tables_aligned(weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]]) -> bool:
     """what the fused QR kernels need of weight_q / weight_r / plain tables: a lane's 4 columns are one 16-byte load"""
-    return all(w.data_ptr() % 16 == 0 for w in weights) and all(wr is None or wr.data_ptr() % 16 == 0 for wr in weights_r)
-
-
-def _gather_desc_qr(x: torch.Tensor, weights, weights_r, rows, collisions, bags: BagBatch, D: int):
-    """_gather_desc for a table list with QR tables: the same refusals; table t is feature t + 1"""
-    _gather_one_lookup(bags, len(weights))
-    _req(x, "x", ndim=2)
-    Dw, wp, wrp, rows_a, coll_a = _qr_desc(weights, weights_r, rows, collisions)
-    if Dw != D or x.size(1) != D or x.size(0) != bags.B:
-        raise RuntimeError("dlrm_amd: the fused QR embedding + interaction path: shape mismatch")
-    return 1 + bags.T, wp, wrp, rows_a, coll_a
+    return tables_aligned([*weights, *(wr for wr in weights_r if wr is not None)], ROW_KINDS["qr"].align)
 
 
 def interact_fwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]], rows: Sequence[int],
@@ -1214,19 +1279,7 @@ def interact_fwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], wei
                            pred=None) -> torch.Tensor:
     """R = interaction of [x | the composed rows of the tables], the rows fetched and composed by the kernel itself
     (dlrm_interact_fwd_gather_qr): the bits of emb_fwd_qr into a feature buffer + interact_fwd, without that buffer."""
-    lib = _lib.load()
-    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
-    _req(R, "R", ndim=2)
-    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-        raise RuntimeError("dlrm_amd: interact_fwd_gather_qr shape mismatch")
-    st = _stream(R)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_fwd_qr"):
-        rc = lib.dlrm_interact_fwd_gather_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
-                                             bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
-                                             C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_fwd_gather_qr")
-    return R
+    return _fwd_gather_rows("qr", x, (weights, weights_r, rows, collisions, op), bags, D, self_interaction, R, pred)
 
 
 def interact_bwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]], rows: Sequence[int],
@@ -1235,20 +1288,8 @@ def interact_bwd_gather_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], wei
     """dx [B, D] = gradient of x; gout [B, >= Tv*D] = the gradient buffer of the VIRTUAL table list, as emb_qr_bwd_split lays it out
     (dlrm_interact_bwd_gather_qr): the bits of interact_bwd over (x, the buffer emb_fwd_qr wrote) + emb_qr_bwd_split, without the pooled
     buffer, its gradient or the saved sums.  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
-    lib = _lib.load()
-    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
-    Tv = bags.T + sum(1 for c in collisions if c)
-    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(gout, "gout", ndim=2)
-    if dR.size(0) != bags.B or dx.size(0) != bags.B or gout.size(0) != bags.B or dx.size(1) < D or gout.size(1) < Tv * D:
-        raise RuntimeError("dlrm_amd: interact_bwd_gather_qr shape mismatch")
-    st = _stream(dR)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_bwd_qr"):
-        rc = lib.dlrm_interact_bwd_gather_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
-                                             bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
-                                             C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(gout.data_ptr()), _ld(gout),
-                                             C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_bwd_gather_qr")
+    _bwd_gather_rows("qr", x, (weights, weights_r, rows, collisions, op), bags, D, self_interaction, dR, dx, gout,
+                     bags.T + sum(1 for c in collisions if c), pred)
 
 
 # ---- ... and over QR tables of D = 16 / 32 / 64 (csrc/interact_narrow_qr.hip: the narrow kernels over a QR row source)
@@ -1261,19 +1302,7 @@ def interact_fwd_gather_narrow_qr(x: torch.Tensor, weights: Sequence[torch.Tenso
                                   R: torch.Tensor, pred=None) -> torch.Tensor:
     """interact_fwd_gather_qr for tables of D = 16 / 32 / 64 (dlrm_interact_fwd_gather_narrow_qr): the bits of emb_fwd_qr into a feature
     buffer + interact_fwd, without that buffer."""
-    lib = _lib.load()
-    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
-    _req(R, "R", ndim=2)
-    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow_qr shape mismatch")
-    st = _stream(R)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_fwd_narrow_qr"):
-        rc = lib.dlrm_interact_fwd_gather_narrow_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
-                                                    bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()),
-                                                    _ld(R), C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_fwd_gather_narrow_qr")
-    return R
+    return _fwd_gather_rows("narrow_qr", x, (weights, weights_r, rows, collisions, op), bags, D, self_interaction, R, pred)
 
 
 def interact_bwd_gather_narrow_qr(x: torch.Tensor, weights: Sequence[torch.Tensor], weights_r: Sequence[Optional[torch.Tensor]],
@@ -1281,51 +1310,31 @@ def interact_bwd_gather_narrow_qr(x: torch.Tensor, weights: Sequence[torch.Tenso
                                   dR: torch.Tensor, dx: torch.Tensor, gout: torch.Tensor, pred=None) -> None:
     """interact_bwd_gather_qr for tables of D = 16 / 32 / 64 (dlrm_interact_bwd_gather_narrow_qr): dx and the gradient buffer of the
     VIRTUAL table list with the bits of interact_bwd over (x, the buffer emb_fwd_qr wrote) + emb_qr_bwd_split."""
-    lib = _lib.load()
-    F, wp, wrp, rows_a, coll_a = _gather_desc_qr(x, weights, weights_r, rows, collisions, bags, D)
-    Tv = bags.T + sum(1 for c in collisions if c)
-    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(gout, "gout", ndim=2)
-    if dR.size(0) != bags.B or dx.size(0) != bags.B or gout.size(0) != bags.B or dx.size(1) < D or gout.size(1) < Tv * D:
-        raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow_qr shape mismatch")
-    st = _stream(dR)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_bwd_narrow_qr"):
-        rc = lib.dlrm_interact_bwd_gather_narrow_qr(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, wrp, rows_a, coll_a, _qr_op(op),
-                                                    bags._idx, bags._off, bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()),
-                                                    _ld(dR), C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(gout.data_ptr()), _ld(gout),
-                                                    C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_bwd_gather_narrow_qr")
+    _bwd_gather_rows("narrow_qr", x, (weights, weights_r, rows, collisions, op), bags, D, self_interaction, dR, dx, gout,
+                     bags.T + sum(1 for c in collisions if c), pred)
 
 
 def gather_quant_ok(F: int, D: int, bits: int) -> bool:
     return bool(_lib.load().dlrm_interact_gather_quant_ok(int(F), int(D), int(bits)))
 
 
+def packed_align(bits: int) -> int:
+    """a lane's codes are one 8-byte (8 bits) / 4-byte (4 bits) load"""
+    align = ROW_KINDS["quant"].align
+    return align if bits == 8 else align // 2
+
+
 def quant_tables_aligned(qweights: Sequence[torch.Tensor], bits: int) -> bool:
-    """what interact_fwd_gather_quant needs of the packed tables: a lane's codes are one 8-byte (8 bits) / 4-byte (4 bits) load"""
-    return all(q.data_ptr() % (8 if bits == 8 else 4) == 0 for q in qweights)
+    """what interact_fwd_gather_quant needs of the packed tables: packed_align(bits)"""
+    return tables_aligned(qweights, packed_align(bits))
 
 
 def interact_fwd_gather_quant(x: torch.Tensor, qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, bags: BagBatch,
                               self_interaction, R: torch.Tensor, pred=None) -> torch.Tensor:
     """R = interaction of [x | one-hot rows of the packed tables], the rows fetched and dequantised by the kernel itself
     (dlrm_interact_fwd_gather_quant): the bits of emb_fwd_quant into a feature buffer + interact_fwd, without that buffer.  Forward only."""
-    lib = _lib.load()
-    _gather_one_lookup(bags, len(qweights))
-    wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "interact_fwd_gather_quant")
-    _req(x, "x", ndim=2)
-    _req(R, "R", ndim=2)
-    F = 1 + bags.T
-    if x.size(1) != D or R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-        raise RuntimeError("dlrm_amd: interact_fwd_gather_quant shape mismatch")
-    st = _stream(R)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_fwd_quant"):
-        rc = lib.dlrm_interact_fwd_gather_quant(bags.B, F, D, bits, C.c_void_p(x.data_ptr()), _ld(x), wp, rp, bags._idx, bags._off,
-                                                bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
-                                                C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_fwd_gather_quant")
-    return R
+    return _fwd_gather_rows("quant", x, (qweights, rows, D, bits, bags.T, "interact_fwd_gather_quant"), bags, D, self_interaction, R, pred,
+                            (bits,))
 
 
 INTERACT_RELU_X = 4         # DLRM_INTERACT_RELU_X of include/dlrm_hip.h: OR-ed into the backward kernels' interaction mode
@@ -1337,24 +1346,12 @@ def interact_bwd_gather(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: 
     `self_interaction | INTERACT_RELU_X`: x is a ReLU output and dx comes back multiplied by [x > 0] (see interact_bwd).
     presorted (emb_presort): the sparse SGD step of the single lookups is taken here — their tables rows are UPDATED, their dE rows not
     written; emb_bwd_sgd_presorted applies the rest (dlrm_interact_bwd_gather_sgd, ABI 17)."""
-    lib = _lib.load()
     if _gather_tables_bf16(weights, "interact_bwd_gather"):
         # bf16 tables (dlrm_interact_bwd_gather_bf16): the bits of interact_bwd over (x, the buffer emb_fwd_bf16 wrote)
         if presorted is not None:
             raise RuntimeError("dlrm_amd: interact_bwd_gather: the update inside the backward (presorted) exists for fp32 tables only")
-        F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "bf16")
-        _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
-        if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
-            raise RuntimeError("dlrm_amd: interact_bwd_gather shape mismatch")
-        st = _stream(dR)
-        flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-        with _timed("emb_interact_bwd_bf16"):
-            rc = lib.dlrm_interact_bwd_gather_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
-                                                   bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
-                                                   C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(dE.data_ptr()), _ld(dE),
-                                                   C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
-        _lib.check(rc, "dlrm_interact_bwd_gather_bf16")
-        return
+        return _bwd_gather_rows("bf16", x, (weights,), bags, D, self_interaction, dR, dx, dE, bags.T, pred)
+    lib = _lib.load()
     F, p, ld, gidx, goff, rows = _gather_desc(x, weights, bags, D)
     _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
     dptrs = [dx.data_ptr()] + [dE.data_ptr() + 4 * k * D for k in range(bags.T)]
@@ -1389,38 +1386,14 @@ def interact_fwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor],
                                R: torch.Tensor, pred=None) -> torch.Tensor:
     """R = interaction of [x | one-hot rows of the fp32 tables], D = 16 / 32 / 64, the rows fetched by the kernel itself
     (dlrm_interact_fwd_gather_narrow): the bits of emb_fwd into a feature buffer + interact_fwd, without that buffer."""
-    lib = _lib.load()
-    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _weights_desc, "narrow")
-    _req(R, "R", ndim=2)
-    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow shape mismatch")
-    st = _stream(R)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_fwd_narrow"):
-        rc = lib.dlrm_interact_fwd_gather_narrow(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
-                                                 bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
-                                                 C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_fwd_gather_narrow")
-    return R
+    return _fwd_gather_rows("narrow", x, (weights,), bags, D, self_interaction, R, pred)
 
 
 def interact_bwd_gather_narrow(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
                                dR: torch.Tensor, dx: torch.Tensor, dE: torch.Tensor, pred=None) -> None:
     """dx [B, D] = gradient of x; dE [B, T*D] = gradients of the T gathered rows (dlrm_interact_bwd_gather_narrow): the bits of
     interact_bwd over (x, the buffer emb_fwd wrote).  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
-    lib = _lib.load()
-    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _weights_desc, "narrow")
-    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
-    if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
-        raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow shape mismatch")
-    st = _stream(dR)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_bwd_narrow"):
-        rc = lib.dlrm_interact_bwd_gather_narrow(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
-                                                 bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
-                                                 C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(dE.data_ptr()), _ld(dE),
-                                                 C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_bwd_gather_narrow")
+    _bwd_gather_rows("narrow", x, (weights,), bags, D, self_interaction, dR, dx, dE, bags.T, pred)
 
 
 # ---- ... and over bfloat16 / packed tables of those widths (csrc/interact_narrow_rows.hip: the same kernels over another row source).
@@ -1435,45 +1408,21 @@ def gather_narrow_quant_ok(F: int, D: int, bits: int) -> bool:
 
 def narrow_bf16_tables_aligned(weights: Sequence[torch.Tensor]) -> bool:
     """what the narrow fused bf16 kernels need of the tables: a lane's 4 columns are one 8-byte load"""
-    return all(w.data_ptr() % 8 == 0 for w in weights)
+    return tables_aligned(weights, ROW_KINDS["narrow_bf16"].align)
 
 
 def interact_fwd_gather_narrow_bf16(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
                                     R: torch.Tensor, pred=None) -> torch.Tensor:
     """R = interaction of [x | one-hot rows of the bfloat16 tables], D = 16 / 32 / 64, the rows fetched and widened by the kernel itself
     (dlrm_interact_fwd_gather_narrow_bf16): the bits of emb_fwd_bf16 into a feature buffer + interact_fwd, without that buffer."""
-    lib = _lib.load()
-    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "narrow bf16")
-    _req(R, "R", ndim=2)
-    if R.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow_bf16 shape mismatch")
-    st = _stream(R)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_fwd_narrow_bf16"):
-        rc = lib.dlrm_interact_fwd_gather_narrow_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
-                                                      bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
-                                                      C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_fwd_gather_narrow_bf16")
-    return R
+    return _fwd_gather_rows("narrow_bf16", x, (weights,), bags, D, self_interaction, R, pred)
 
 
 def interact_bwd_gather_narrow_bf16(x: torch.Tensor, weights: Sequence[torch.Tensor], bags: BagBatch, D: int, self_interaction,
                                     dR: torch.Tensor, dx: torch.Tensor, dE: torch.Tensor, pred=None) -> None:
     """dx [B, D] = gradient of x; dE [B, T*D] = fp32 gradients of the T gathered bfloat16 rows (dlrm_interact_bwd_gather_narrow_bf16): the
     bits of interact_bwd over (x, the buffer emb_fwd_bf16 wrote).  `self_interaction | INTERACT_RELU_X` as interact_bwd."""
-    lib = _lib.load()
-    F, wp, rows = _gather_desc_tables(x, weights, bags, D, _bf16_weights_desc, "narrow bf16")
-    _req(dR, "dR", ndim=2); _req(dx, "dx", ndim=2); _req(dE, "dE", ndim=2)
-    if dR.size(0) != bags.B or dx.size(0) != bags.B or dE.size(0) != bags.B or dx.size(1) < D or dE.size(1) < bags.T * D:
-        raise RuntimeError("dlrm_amd: interact_bwd_gather_narrow_bf16 shape mismatch")
-    st = _stream(dR)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_bwd_narrow_bf16"):
-        rc = lib.dlrm_interact_bwd_gather_narrow_bf16(bags.B, F, D, C.c_void_p(x.data_ptr()), _ld(x), wp, rows, bags._idx, bags._off,
-                                                      bags.idx_bits, int(self_interaction), C.c_void_p(dR.data_ptr()), _ld(dR),
-                                                      C.c_void_p(dx.data_ptr()), _ld(dx), C.c_void_p(dE.data_ptr()), _ld(dE),
-                                                      C.c_void_p(_err_block(dR.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_bwd_gather_narrow_bf16")
+    _bwd_gather_rows("narrow_bf16", x, (weights,), bags, D, self_interaction, dR, dx, dE, bags.T, pred)
 
 
 def interact_fwd_gather_narrow_quant(x: torch.Tensor, qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int,
@@ -1481,22 +1430,8 @@ def interact_fwd_gather_narrow_quant(x: torch.Tensor, qweights: Sequence[torch.T
     """R = interaction of [x | one-hot rows of the packed tables], D = 16 / 32 / 64, the rows fetched and dequantised by the kernel itself
     (dlrm_interact_fwd_gather_narrow_quant): the bits of emb_fwd_quant into a feature buffer + interact_fwd, without that buffer.
     Forward only."""
-    lib = _lib.load()
-    _gather_one_lookup(bags, len(qweights))
-    wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "interact_fwd_gather_narrow_quant")
-    _req(x, "x", ndim=2)
-    _req(R, "R", ndim=2)
-    F = 1 + bags.T
-    if x.size(1) != D or R.size(0) != bags.B or x.size(0) != bags.B or R.size(1) < interact_out_width(F, D, self_interaction):
-        raise RuntimeError("dlrm_amd: interact_fwd_gather_narrow_quant shape mismatch")
-    st = _stream(R)
-    flag, nonzero = (None, 0) if pred is None else _pred_args(pred, st)
-    with _timed("emb_interact_fwd_narrow_quant"):
-        rc = lib.dlrm_interact_fwd_gather_narrow_quant(bags.B, F, D, bits, C.c_void_p(x.data_ptr()), _ld(x), wp, rp, bags._idx, bags._off,
-                                                       bags.idx_bits, int(self_interaction), C.c_void_p(R.data_ptr()), _ld(R),
-                                                       C.c_void_p(_err_block(R.device).data_ptr()), flag, nonzero, st)
-    _lib.check(rc, "dlrm_interact_fwd_gather_narrow_quant")
-    return R
+    return _fwd_gather_rows("narrow_quant", x, (qweights, rows, D, bits, bags.T, "interact_fwd_gather_narrow_quant"), bags, D,
+                            self_interaction, R, pred, (bits,))
 
 
 def interact_bwd(blocks: Sequence[torch.Tensor], D: int, self_interaction: bool, dR: torch.Tensor,
