@@ -17,23 +17,10 @@
 //     what keeps HBM busy for one-hot (Criteo) inputs where every bag has exactly one row.
 //   * bags with more rows continue with a 4-deep load pipeline per bag.
 #include <stdlib.h>
-#include "common.h"
+#include "emb_lookup.h"
 
 namespace {
 
-template <int VEC> struct Vec;
-template <> struct Vec<4> { using T = float4; };
-template <> struct Vec<1> { using T = float; };
-
-__device__ __forceinline__ void v_zero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void v_zero(float& a) { a = 0.f; }
-// acc = fma(w, v, acc) per component.  With w == 1.0f this is exactly acc + v (single rounding),
-// so the unweighted path reproduces the reference's plain in-order sum bit for bit.
-__device__ __forceinline__ void v_fma(float4& a, float w, const float4& v) {
-    a.x = __builtin_fmaf(w, v.x, a.x); a.y = __builtin_fmaf(w, v.y, a.y);
-    a.z = __builtin_fmaf(w, v.z, a.z); a.w = __builtin_fmaf(w, v.w, a.w);
-}
-__device__ __forceinline__ void v_fma(float& a, float w, const float& v) { a = __builtin_fmaf(w, v, a); }
 __device__ __forceinline__ float4 v_scale(float s, const float4& v) {
     return make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
 }
@@ -46,138 +33,12 @@ __device__ __forceinline__ void v_atomic_add(float* p, const float4& v) {
 __device__ __forceinline__ void v_atomic_add(float* p, const float& v) { atomicAdd(p, v); }
 
 // -------------------------------------------------------------------------------------------
-// forward
+// forward: emb_lookup.h's body over fp32 rows (LOOP: see there)
 // -------------------------------------------------------------------------------------------
-// LOOP (dlrm_emb_fwd_pred only): a capped grid walks the bags with a grid stride.  A predicated launch that does NOT run still has its
-// workgroups dispatched, and the plain launch has one workgroup per 16 bags (106 k workgroups at Criteo-Terabyte shapes: ~20 us of dispatch
-// for a launch that returns at once); LOOP = false is the straight-line kernel of every other call, unchanged.
 template <int VEC, int LPB, int NCH, typename IT, int U, bool LOOP = false>
 __global__ __launch_bounds__(256) void emb_fwd_kernel(EmbArgs a, long long B, int D,
                                                       float* __restrict__ out, long long out_ld) {
-    using VT = typename Vec<VEC>::T;
-    if (a.pred.skip()) return;      // (dlrm_emb_fwd_pred: the other implementation of this step runs instead)
-    const int t = blockIdx.y;
-    const float* __restrict__ W = a.w[t];
-    const IT* __restrict__ idx = (const IT*)a.idx[t];
-    const IT* __restrict__ off = (const IT*)a.off[t];
-    const float* __restrict__ psw = a.psw[t];
-    const long long nnz = a.nnz[t];
-    const long long rows = a.rows[t];
-
-    constexpr int GPB = 256 / LPB;  // groups (bags in flight) per workgroup
-    const int g = threadIdx.x / LPB;
-    const int lig = threadIdx.x % LPB;
-    long long b0 = ((long long)blockIdx.x * GPB + g) * U;
-    if (b0 >= B) return;
-  for (;;) {
-    long long s[U], e[U];
-    {
-        long long o[U + 1];
-#pragma unroll
-        for (int u = 0; u <= U; ++u) {
-            const long long b = b0 + u;
-            o[u] = (b < B) ? (long long)off[b] : nnz;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) { s[u] = o[u]; e[u] = (b0 + u < B) ? o[u + 1] : o[u]; }
-    }
-
-    VT acc[U][NCH];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) v_zero(acc[u][c]);
-
-    // ---- phase 1: first row of every bag, all loads in flight together --------------------
-    // an out-of-range index contributes nothing and is reported (the reference raises on it)
-    long long r0[U];
-    float w0[U];
-    bool ok0[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        r0[u] = 0; w0[u] = 1.f; ok0[u] = false;
-        if (s[u] < e[u]) {
-            r0[u] = (long long)idx[s[u]];
-            if (psw) w0[u] = psw[s[u]];
-            ok0[u] = dlrm_index_ok(r0[u], rows);
-            if (!ok0[u]) dlrm_report_bad_index(a.err, a.slot[t], r0[u], rows);
-        }
-    }
-    VT v0[U][NCH];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int col = (c * LPB + lig) * VEC;
-            v_zero(v0[u][c]);
-            if (ok0[u] && col < D) v0[u][c] = *(const VT*)(W + r0[u] * D + col);
-        }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        if (ok0[u]) {
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) v_fma(acc[u][c], w0[u], v0[u][c]);
-        }
-
-    // ---- phase 2: remaining rows of multi-hot bags, 4 row loads in flight per bag ----------
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        long long i = s[u] + 1;
-        const long long end = e[u];
-        for (; i + 4 <= end; i += 4) {
-            long long r[4]; float w[4]; VT v[4][NCH];
-            bool ok[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r[k] = (long long)idx[i + k]; w[k] = psw ? psw[i + k] : 1.f;
-                ok[k] = dlrm_index_ok(r[k], rows);
-                if (!ok[k]) dlrm_report_bad_index(a.err, a.slot[t], r[k], rows);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    const int col = (c * LPB + lig) * VEC;
-                    v_zero(v[k][c]);
-                    if (ok[k] && col < D) v[k][c] = *(const VT*)(W + r[k] * D + col);
-                }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (ok[k]) {
-#pragma unroll
-                    for (int c = 0; c < NCH; ++c) v_fma(acc[u][c], w[k], v[k][c]);
-                }
-            }
-        }
-        for (; i < end; ++i) {
-            const long long r = (long long)idx[i];
-            const float w = psw ? psw[i] : 1.f;
-            if (!dlrm_index_ok(r, rows)) { dlrm_report_bad_index(a.err, a.slot[t], r, rows); continue; }
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int col = (c * LPB + lig) * VEC;
-                if (col < D) { VT v = *(const VT*)(W + r * D + col); v_fma(acc[u][c], w, v); }
-            }
-        }
-    }
-
-    // ---- store: bag b of table t goes to out[b, (slot_base+t)*D : +D] ------------------------
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const long long b = b0 + u;
-        if (b < B) {
-            float* o = out + b * out_ld + (long long)a.slot[t] * D;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int col = (c * LPB + lig) * VEC;
-                if (col < D) *(VT*)(o + col) = acc[u][c];
-            }
-        }
-    }
-    if constexpr (!LOOP) break;
-    b0 += (long long)gridDim.x * GPB * U;
-    if (b0 >= B) break;
-  }
+    emb_lookup_body<Fp32Rows<VEC>, LPB, NCH, IT, U, LOOP>(a, B, D, out, out_ld);
 }
 
 // -------------------------------------------------------------------------------------------
@@ -412,80 +273,7 @@ __global__ __launch_bounds__(256) void emb_psw_grad_kernel(EmbArgs a, PoolArgs p
 // -------------------------------------------------------------------------------------------
 // host-side dispatch
 // -------------------------------------------------------------------------------------------
-struct Shape { int vec, lpb, nch; };
-
-static int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
-static bool pick_shape(int D, bool vec_ok, Shape* s) {
-    if (vec_ok && D % 4 == 0) {
-        const int d4 = D / 4;
-        int lpb = pow2ceil(d4); if (lpb < 4) lpb = 4; if (lpb > 64) lpb = 64;
-        const int nch = (d4 + lpb - 1) / lpb;
-        if (nch > 4) return false;
-        *s = {4, lpb, nch == 3 ? 4 : nch};
-        return true;
-    }
-    int lpb = pow2ceil(D); if (lpb < 4) lpb = 4; if (lpb > 64) lpb = 64;
-    const int nch = (D + lpb - 1) / lpb;
-    if (nch > 4) return false;
-    *s = {1, lpb, nch == 3 ? 4 : nch};
-    return true;
-}
-
 constexpr int kU = 4;  // bags per group
-
-#define EMB_DISPATCH_SHAPE(KERNEL, IT, ...)                                                        \
-    do {                                                                                           \
-        const int key = sh.vec * 10000 + sh.lpb * 10 + sh.nch;                                     \
-        switch (key) {                                                                             \
-            case 4 * 10000 + 4 * 10 + 1:  hipLaunchKernelGGL((KERNEL<4, 4, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break;  \
-            case 4 * 10000 + 8 * 10 + 1:  hipLaunchKernelGGL((KERNEL<4, 8, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break;  \
-            case 4 * 10000 + 16 * 10 + 1: hipLaunchKernelGGL((KERNEL<4, 16, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 4 * 10000 + 32 * 10 + 1: hipLaunchKernelGGL((KERNEL<4, 32, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 4 * 10000 + 64 * 10 + 1: hipLaunchKernelGGL((KERNEL<4, 64, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 4 * 10000 + 64 * 10 + 2: hipLaunchKernelGGL((KERNEL<4, 64, 2, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 4 * 10000 + 64 * 10 + 4: hipLaunchKernelGGL((KERNEL<4, 64, 4, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 1 * 10000 + 4 * 10 + 1:  hipLaunchKernelGGL((KERNEL<1, 4, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break;  \
-            case 1 * 10000 + 8 * 10 + 1:  hipLaunchKernelGGL((KERNEL<1, 8, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break;  \
-            case 1 * 10000 + 16 * 10 + 1: hipLaunchKernelGGL((KERNEL<1, 16, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 1 * 10000 + 32 * 10 + 1: hipLaunchKernelGGL((KERNEL<1, 32, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 1 * 10000 + 64 * 10 + 1: hipLaunchKernelGGL((KERNEL<1, 64, 1, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 1 * 10000 + 64 * 10 + 2: hipLaunchKernelGGL((KERNEL<1, 64, 2, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            case 1 * 10000 + 64 * 10 + 4: hipLaunchKernelGGL((KERNEL<1, 64, 4, IT, kU>), grid, block, 0, st, __VA_ARGS__); break; \
-            default: return DLRM_E_RANGE;                                                          \
-        }                                                                                          \
-    } while (0)
-
-static int check_common(int T, int64_t B, int D, const void* const* weight_host, const int64_t* rows_host,
-                        const void* const* indices_host, const void* const* offsets_host,
-                        const int64_t* nnz_host, int idx_bits) {
-    if (T <= 0 || B <= 0 || D <= 0) return DLRM_E_ARG;
-    if (!weight_host || !rows_host || !indices_host || !offsets_host || !nnz_host) return DLRM_E_ARG;
-    if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
-    for (int t = 0; t < T; ++t) {
-        if (!weight_host[t] || !offsets_host[t]) return DLRM_E_ARG;
-        if (nnz_host[t] < 0 || rows_host[t] <= 0) return DLRM_E_ARG;
-        if (nnz_host[t] > 0 && !indices_host[t]) return DLRM_E_ARG;
-    }
-    return 0;
-}
-
-static void fill_args(EmbArgs& a, const int* ids, int n, void* const* weight_host, const int64_t* rows_host,
-                      const void* const* indices_host, const void* const* offsets_host,
-                      const int64_t* nnz_host, const void* const* psw_host, int64_t* err) {
-    a.err = (long long*)err;
-    a.pred.flag = nullptr; a.pred.nonzero = 0;
-    for (int k = 0; k < DLRM_MAX_TABLES_PER_LAUNCH; ++k) {
-        const int t = ids[k < n ? k : 0];
-        a.w[k] = (float*)weight_host[t];
-        a.idx[k] = indices_host[t];
-        a.off[k] = offsets_host[t];
-        a.psw[k] = psw_host ? (const float*)psw_host[t] : nullptr;
-        a.nnz[k] = nnz_host[t];
-        a.rows[k] = rows_host[t];
-        a.slot[k] = t;
-    }
-}
 
 }  // namespace
 
@@ -518,7 +306,7 @@ static int emb_fwd_impl(int T, int64_t B, int D, const void* const* weight_host,
                         const void* const* offsets_host, const int64_t* nnz_host,
                         const void* const* psw_host, int idx_bits, float* out, int64_t out_ld,
                         int64_t* err, DlrmPred pred, void* stream) {
-    int rc = check_common(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, idx_bits);
+    int rc = emb_check_common(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, idx_bits);
     if (rc) return rc;
     if (!out || out_ld < (int64_t)T * D) return DLRM_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -526,18 +314,15 @@ static int emb_fwd_impl(int T, int64_t B, int D, const void* const* weight_host,
     bool vec_ok = dlrm_aligned16(out) && (out_ld % 4 == 0);
     for (int t = 0; t < T; ++t) vec_ok = vec_ok && dlrm_aligned16(weight_host[t]);
     Shape sh;
-    if (!pick_shape(D, vec_ok, &sh)) {
+    if (pick(D, vec_ok, &sh)) {
         fprintf(stderr, "libdlrm_hip: dlrm_emb_fwd: embedding dim %d not supported (max 1024, or 256 unaligned)\n", D);
         return DLRM_E_RANGE;
     }
     const int bags_per_block = (256 / sh.lpb) * kU;
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
-        int ids[DLRM_MAX_TABLES_PER_LAUNCH];
-        for (int k = 0; k < n; ++k) ids[k] = t0 + k;
         EmbArgs a;
-        fill_args(a, ids, n, (void* const*)weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err);
-        a.pred = pred;
+        emb_fill_args(a, t0, n, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err, pred);
         dim3 grid((unsigned)((B + bags_per_block - 1) / bags_per_block), (unsigned)n, 1), block(256, 1, 1);
         if (pred.flag) {           // predicated: the shapes of the fused paths' fallbacks only (D = 128; D = 16 / 32 / 64), capped grid + grid stride
             if (sh.vec == 4 && sh.nch == 1 && (sh.lpb == 4 || sh.lpb == 8 || sh.lpb == 16)) {
@@ -572,9 +357,14 @@ static int emb_fwd_impl(int T, int64_t B, int D, const void* const* weight_host,
             DLRM_LAUNCH_CHECK();
             continue;
         }
-        if (idx_bits == 64) EMB_DISPATCH_SHAPE(emb_fwd_kernel, long long, a, (long long)B, D, out, (long long)out_ld);
-        else                EMB_DISPATCH_SHAPE(emb_fwd_kernel, int, a, (long long)B, D, out, (long long)out_ld);
-        DLRM_LAUNCH_CHECK();
+        rc = dispatch_shape(sh, [&](auto vec, auto lpb, auto nch) {
+            constexpr int V = decltype(vec)::value, LP = decltype(lpb)::value, NC = decltype(nch)::value;
+            if (idx_bits == 64) hipLaunchKernelGGL((emb_fwd_kernel<V, LP, NC, long long, kU>), grid, block, 0, st, a, (long long)B, D, out, (long long)out_ld);
+            else                hipLaunchKernelGGL((emb_fwd_kernel<V, LP, NC, int, kU>), grid, block, 0, st, a, (long long)B, D, out, (long long)out_ld);
+            DLRM_LAUNCH_CHECK();
+            return 0;
+        });
+        if (rc) return rc;
     }
     return 0;
 }
@@ -585,7 +375,7 @@ extern "C" int dlrm_emb_bwd_sgd(int T, int64_t B, int D, void* const* weight_hos
                                 const void* const* psw_host, int idx_bits, const float* dout,
                                 int64_t dout_ld, float lr, const float* lr_dev, int mode, void* workspace,
                                 int64_t workspace_bytes, int64_t* err, void* stream) {
-    int rc = check_common(T, B, D, (const void* const*)weight_host, rows_host, indices_host, offsets_host,
+    int rc = emb_check_common(T, B, D, (const void* const*)weight_host, rows_host, indices_host, offsets_host,
                           nnz_host, idx_bits);
     if (rc) return rc;
     if (!dout || dout_ld < (int64_t)T * D) return DLRM_E_ARG;
@@ -600,10 +390,8 @@ extern "C" int dlrm_emb_bwd_sgd(int T, int64_t B, int D, void* const* weight_hos
     if (mode == DLRM_UPD_DETERMINISTIC) {
         for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
             const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
-            int ids[DLRM_MAX_TABLES_PER_LAUNCH];
-            for (int k = 0; k < n; ++k) ids[k] = t0 + k;
             EmbArgs a;
-            fill_args(a, ids, n, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err);
+            emb_fill_args(a, t0, n, (const void* const*)weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err);
             dim3 grid(64, (unsigned)n, 1);
             if (idx_bits == 64)
                 hipLaunchKernelGGL(emb_bwd_sgd_det_kernel<long long>, grid, block, 0, st, a, (long long)B, D, dout, (long long)dout_ld, neg_lr);
@@ -621,7 +409,7 @@ extern "C" int dlrm_emb_bwd_sgd(int T, int64_t B, int D, void* const* weight_hos
     bool vec_ok = dlrm_aligned16(dout) && (dout_ld % 4 == 0);
     for (int t = 0; t < T; ++t) vec_ok = vec_ok && dlrm_aligned16(weight_host[t]);
     Shape sh;
-    if (!pick_shape(D, vec_ok, &sh)) return DLRM_E_RANGE;
+    if (pick(D, vec_ok, &sh)) return DLRM_E_RANGE;
     const int bags_per_block = (256 / sh.lpb) * kU;
 
     for (int cls = 0; cls < 2; ++cls) {       // 0 = general, 1 = tiny
@@ -638,7 +426,7 @@ extern "C" int dlrm_emb_bwd_sgd(int T, int64_t B, int D, void* const* weight_hos
             }
             if (n == 0) break;
             EmbArgs a;
-            fill_args(a, ids, n, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err);
+            emb_fill_args(a, ids, n, (const void* const*)weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err);
             if (cls == 1) {
                 const size_t lds = (size_t)(max_rows * D * 4);
                 // enough bags per workgroup to amortise the flush, enough workgroups to fill the chip
@@ -651,8 +439,13 @@ extern "C" int dlrm_emb_bwd_sgd(int T, int64_t B, int D, void* const* weight_hos
                     hipLaunchKernelGGL(emb_bwd_sgd_lds_kernel<int>, grid, block, lds, st, a, (long long)B, D, dout, (long long)dout_ld, neg_lr, bpb);
             } else {
                 dim3 grid((unsigned)((B + bags_per_block - 1) / bags_per_block), (unsigned)n, 1);
-                if (idx_bits == 64) EMB_DISPATCH_SHAPE(emb_bwd_sgd_atomic_kernel, long long, a, (long long)B, D, dout, (long long)dout_ld, neg_lr);
-                else                EMB_DISPATCH_SHAPE(emb_bwd_sgd_atomic_kernel, int, a, (long long)B, D, dout, (long long)dout_ld, neg_lr);
+                rc = dispatch_shape(sh, [&](auto vec, auto lpb, auto nch) {
+                    constexpr int V = decltype(vec)::value, LP = decltype(lpb)::value, NC = decltype(nch)::value;
+                    if (idx_bits == 64) hipLaunchKernelGGL((emb_bwd_sgd_atomic_kernel<V, LP, NC, long long, kU>), grid, block, 0, st, a, (long long)B, D, dout, (long long)dout_ld, neg_lr);
+                    else                hipLaunchKernelGGL((emb_bwd_sgd_atomic_kernel<V, LP, NC, int, kU>), grid, block, 0, st, a, (long long)B, D, dout, (long long)dout_ld, neg_lr);
+                    return 0;
+                });
+                if (rc) return rc;
             }
             DLRM_LAUNCH_CHECK();
         }
@@ -716,7 +509,7 @@ extern "C" int dlrm_pool_weights_gather(int T, const int64_t* rows_host, const v
 extern "C" int dlrm_emb_psw_grad(int T, int64_t B, int D, const void* const* weight_host, const int64_t* rows_host,
                                  const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
                                  int idx_bits, const float* dout, int64_t dout_ld, void* const* dvw_host, void* stream) {
-    int rc = check_common(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, idx_bits);
+    int rc = emb_check_common(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, idx_bits);
     if (rc) return rc;
     if (!dout || dout_ld < (int64_t)T * D || !dvw_host) return DLRM_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -727,10 +520,8 @@ extern "C" int dlrm_emb_psw_grad(int T, int64_t B, int D, const void* const* wei
     }
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
-        int ids[DLRM_MAX_TABLES_PER_LAUNCH];
-        for (int k = 0; k < n; ++k) ids[k] = t0 + k;
         EmbArgs a;
-        fill_args(a, ids, n, (void* const*)weight_host, rows_host, indices_host, offsets_host, nnz_host, nullptr, nullptr);
+        emb_fill_args(a, t0, n, weight_host, rows_host, indices_host, offsets_host, nnz_host, nullptr, nullptr);
         PoolArgs pa = {};
         for (int k = 0; k < DLRM_MAX_TABLES_PER_LAUNCH; ++k) pa.vw[k] = (float*)dvw_host[t0 + (k < n ? k : 0)];
         dim3 grid((unsigned)((B + 3) / 4), (unsigned)n, 1), block(256);

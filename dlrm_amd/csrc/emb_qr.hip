@@ -20,7 +20,7 @@
 // are in flight before the first dependent add; further lookups of a bag go two at a time (again 4 loads).  weight_r is c rows (2 KiB at
 // c = 4, D = 128): every workgroup reads the same few lines, which stay in the vector L1 / L2 — it is not staged in LDS.
 // A table with collisions == 0 is a plain table: one sum, no composition, the bits dlrm_emb_fwd gives.
-#include "common.h"
+#include "emb_lookup.h"
 #include "qr_split.h"
 
 namespace {
@@ -273,23 +273,19 @@ __global__ __launch_bounds__(256) void emb_qr_split_indices_kernel(IdxSplitArgs 
     }
 }
 
-int pow2ceil_qr(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
 int emb_fwd_qr_impl(int T, int64_t B, int D, const void* const* weight_host, const void* const* weight_r_host,
                     const int64_t* rows_host, const int32_t* collisions_host, int op,
                     const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host, int idx_bits,
                     float* out, int64_t out_ld, float* saved, int64_t saved_ld, int64_t* err, DlrmPred pred, void* stream) {
-    if (T <= 0 || B <= 0 || D <= 0) return DLRM_E_ARG;
-    if (!weight_host || !weight_r_host || !rows_host || !collisions_host || !indices_host || !offsets_host || !nnz_host) return DLRM_E_ARG;
-    if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
+    const int rc = emb_check_lists(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, idx_bits, weight_r_host && collisions_host);
+    if (rc) return rc;
     if (op != DLRM_QR_MULT && op != DLRM_QR_ADD) return DLRM_E_MODE;
     if (!out || out_ld < (int64_t)T * D) return DLRM_E_ARG;
     DLRM_REQUIRE(D <= 512, DLRM_E_RANGE, "embedding dimension above 512");
     int n_qr = 0;
     bool vec_ok = D % 4 == 0 && dlrm_aligned16(out) && out_ld % 4 == 0;
     for (int t = 0; t < T; ++t) {
-        if (!weight_host[t] || !offsets_host[t] || nnz_host[t] < 0 || rows_host[t] <= 0 || collisions_host[t] < 0) return DLRM_E_ARG;
-        if (nnz_host[t] > 0 && !indices_host[t]) return DLRM_E_ARG;
+        if (emb_check_table(t, weight_host, rows_host, indices_host, offsets_host, nnz_host) || collisions_host[t] < 0) return DLRM_E_ARG;
         if (collisions_host[t] > 0) { if (!weight_r_host[t]) return DLRM_E_ARG; ++n_qr; vec_ok = vec_ok && dlrm_aligned16(weight_r_host[t]); }
         vec_ok = vec_ok && dlrm_aligned16(weight_host[t]);
     }
@@ -301,21 +297,19 @@ int emb_fwd_qr_impl(int T, int64_t B, int D, const void* const* weight_host, con
     int lpb = 0, nch = 0;
     if (vec_ok) {
         const int d4 = D / 4;
-        lpb = pow2ceil_qr(d4); if (lpb < 4) lpb = 4; if (lpb > 64) lpb = 64;
+        lpb = lanes_per_bag(d4);
         nch = (d4 + lpb - 1) / lpb;                  // 1 or 2 (D <= 512)
     }
     constexpr int U = 2;
     int qslot = 0;
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
-        EmbArgs a = {};
+        EmbArgs a;
         QrArgs qa = {};
-        a.err = (long long*)err; a.pred = pred;
+        emb_fill_args(a, t0, n, weight_host, rows_host, indices_host, offsets_host, nnz_host, nullptr, err, pred);
         for (int k = 0; k < n; ++k) {
             const int t = t0 + k;
             const int c = collisions_host[t];
-            a.w[k] = (float*)weight_host[t]; a.idx[k] = indices_host[t]; a.off[k] = offsets_host[t];
-            a.nnz[k] = nnz_host[t]; a.rows[k] = rows_host[t]; a.slot[k] = t;
             qa.coll[k] = c;
             qa.wr[k] = c ? (const float*)weight_r_host[t] : nullptr;
             qa.rows_q[k] = c ? (rows_host[t] + c - 1) / c : rows_host[t];

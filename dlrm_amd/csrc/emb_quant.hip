@@ -28,7 +28,7 @@
 //   * each group takes U bags at once and issues the U first-row loads back to back before any dependent arithmetic (the one-hot Criteo
 //     case is latency-bound otherwise); longer bags continue with four row loads in flight;
 //   * any other D (and unaligned operands): a byte-wise kernel, 16 lanes per bag, that only has to be correct.
-#include "common.h"
+#include "emb_lookup.h"
 
 namespace {
 
@@ -153,108 +153,27 @@ __device__ __forceinline__ void q_accum(float (&acc)[8], float w, const QRow<4>&
     for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(w, __builtin_fmaf(scale, (float)((v.q >> (4 * j)) & 0xFu), bias), acc[j]);
 }
 
+// emb_lookup.h's row source: the packed row's bytes, the lane's 8 codes and the row's scale / bias pair loaded together
+template <int BITS>
+struct QuantRows {
+    using Elem = uint8_t;
+    using Staged = QRow<BITS>;
+    using Acc = float[8];
+    static constexpr int COLS = 8;
+    static __device__ __forceinline__ long long pitch(int D) { return BITS == 8 ? (long long)D + 8 : (long long)D / 2 + 4; }
+    static __device__ __forceinline__ void zero(Staged& v) { q_zero(v); }
+    static __device__ __forceinline__ void clear(Acc& a) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = 0.f;
+    }
+    static __device__ __forceinline__ void load(Staged& v, const uint8_t* __restrict__ row, int D, int col) { q_load(v, row, D, col); }
+    static __device__ __forceinline__ void accum(Acc& a, float w, const Staged& v) { q_accum(a, w, v); }
+    static __device__ __forceinline__ void store(float* o, const Acc& a) { store8(o, a); }
+};
+
 template <int BITS, int LPB, typename IT, int U>
 __global__ __launch_bounds__(256) void emb_fwd_quant_kernel(EmbArgs a, long long B, int D, float* __restrict__ out, long long out_ld) {
-    if (a.pred.skip()) return;      // (dlrm_emb_fwd_quant_pred: the fused lookup + interaction kernel runs instead)
-    const int t = blockIdx.y;
-    const uint8_t* __restrict__ W = (const uint8_t*)a.w[t];
-    const IT* __restrict__ idx = (const IT*)a.idx[t];
-    const IT* __restrict__ off = (const IT*)a.off[t];
-    const float* __restrict__ psw = a.psw[t];
-    const long long nnz = a.nnz[t];
-    const long long rows = a.rows[t];
-    const long long RB = BITS == 8 ? (long long)D + 8 : (long long)D / 2 + 4;
-
-    constexpr int GPB = 256 / LPB;  // groups (bags in flight) per workgroup
-    const int g = threadIdx.x / LPB;
-    const int col = (threadIdx.x % LPB) * 8;
-    const bool live = col < D;
-    const long long b0 = ((long long)blockIdx.x * GPB + g) * U;
-    if (b0 >= B) return;
-
-    long long s[U], e[U];
-    {
-        long long o[U + 1];
-#pragma unroll
-        for (int u = 0; u <= U; ++u) {
-            const long long b = b0 + u;
-            o[u] = (b < B) ? (long long)off[b] : nnz;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) { s[u] = o[u]; e[u] = (b0 + u < B) ? o[u + 1] : o[u]; }
-    }
-
-    float acc[U][8];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[u][j] = 0.f;
-
-    // ---- phase 1: first row of every bag, all loads in flight together --------------------
-    long long r0[U];
-    float w0[U];
-    bool ok0[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        r0[u] = 0; w0[u] = 1.f; ok0[u] = false;
-        if (s[u] < e[u]) {
-            r0[u] = (long long)idx[s[u]];
-            if (psw) w0[u] = psw[s[u]];
-            ok0[u] = dlrm_index_ok(r0[u], rows);
-            if (!ok0[u]) dlrm_report_bad_index(a.err, a.slot[t], r0[u], rows);
-        }
-    }
-    QRow<BITS> v0[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        q_zero(v0[u]);
-        if (ok0[u] && live) q_load(v0[u], W + r0[u] * RB, D, col);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        if (ok0[u]) q_accum(acc[u], w0[u], v0[u]);
-
-    // ---- phase 2: remaining rows of multi-hot bags, 4 row loads in flight per bag ----------
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        long long i = s[u] + 1;
-        const long long end = e[u];
-        for (; i + 4 <= end; i += 4) {
-            long long r[4]; float w[4]; QRow<BITS> v[4];
-            bool ok[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r[k] = (long long)idx[i + k]; w[k] = psw ? psw[i + k] : 1.f;
-                ok[k] = dlrm_index_ok(r[k], rows);
-                if (!ok[k]) dlrm_report_bad_index(a.err, a.slot[t], r[k], rows);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                q_zero(v[k]);
-                if (ok[k] && live) q_load(v[k], W + r[k] * RB, D, col);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ok[k]) q_accum(acc[u], w[k], v[k]);
-        }
-        for (; i < end; ++i) {
-            const long long r = (long long)idx[i];
-            const float w = psw ? psw[i] : 1.f;
-            if (!dlrm_index_ok(r, rows)) { dlrm_report_bad_index(a.err, a.slot[t], r, rows); continue; }
-            if (live) { QRow<BITS> v; q_load(v, W + r * RB, D, col); q_accum(acc[u], w, v); }
-        }
-    }
-
-    // ---- store: bag b of table t goes to out[b, slot*D : +D] ----------------------------------
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const long long b = b0 + u;
-        if (b < B && live) {
-            float* o = out + b * out_ld + (long long)a.slot[t] * D + col;
-            *(float4*)(o) = make_float4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
-            *(float4*)(o + 4) = make_float4(acc[u][4], acc[u][5], acc[u][6], acc[u][7]);
-        }
-    }
+    emb_lookup_body<QuantRows<BITS>, LPB, 1, IT, U, false>(a, B, D, out, out_ld);
 }
 
 // -------------------------------------------------------------------------------------------
@@ -302,8 +221,6 @@ __global__ __launch_bounds__(256) void emb_fwd_quant_bytes_kernel(EmbArgs a, lon
     }
 }
 
-int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
 constexpr int kU = 4;  // bags per lane group
 
 template <int BITS, typename IT>
@@ -335,9 +252,7 @@ extern "C" int dlrm_emb_quantize_rows(int64_t rows, int D, int bits, const float
     DLRM_REQUIRE(bits == 8 || D % 2 == 0, DLRM_E_ARG, "the 4-bit row format needs an even embedding dimension");
     hipStream_t st = (hipStream_t)stream;
     const bool vec = D % 4 == 0 && dlrm_aligned16(weight) && (((uintptr_t)packed) & 3u) == 0;
-    int lpr = pow2ceil(vec ? D / 4 : (bits == 4 ? D / 2 : D));
-    if (lpr < 4) lpr = 4;
-    if (lpr > 64) lpr = 64;
+    const int lpr = lanes_per_bag(vec ? D / 4 : (bits == 4 ? D / 2 : D));
     const long long gpb = 256 / lpr;
     long long nb = (rows + gpb - 1) / gpb;
     if (nb > (1LL << 20)) nb = 1LL << 20;            // grid stride beyond that
@@ -378,16 +293,11 @@ extern "C" int dlrm_emb_fwd_quant_pred(int T, int64_t B, int D, int bits, const 
 static int emb_fwd_quant_impl(int T, int64_t B, int D, int bits, const void* const* weight_host, const int64_t* rows_host,
                               const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
                               const void* const* psw_host, int idx_bits, float* out, int64_t out_ld, int64_t* err, DlrmPred pred, void* stream) {
-    if (T <= 0 || B <= 0 || D <= 0) return DLRM_E_ARG;
-    if (!weight_host || !rows_host || !indices_host || !offsets_host || !nnz_host) return DLRM_E_ARG;
-    if (idx_bits != 32 && idx_bits != 64) return DLRM_E_MODE;
+    int rc = emb_check_lists(T, B, D, weight_host, rows_host, indices_host, offsets_host, nnz_host, idx_bits);
+    if (rc) return rc;
     if (bits != 4 && bits != 8) return DLRM_E_MODE;
     DLRM_REQUIRE(bits == 8 || D % 2 == 0, DLRM_E_ARG, "the 4-bit row format needs an even embedding dimension");
-    for (int t = 0; t < T; ++t) {
-        if (!weight_host[t] || !offsets_host[t]) return DLRM_E_ARG;
-        if (nnz_host[t] < 0 || rows_host[t] <= 0) return DLRM_E_ARG;
-        if (nnz_host[t] > 0 && !indices_host[t]) return DLRM_E_ARG;
-    }
+    if (emb_check_tables(T, weight_host, rows_host, indices_host, offsets_host, nnz_host)) return DLRM_E_ARG;
     if (!out || out_ld < (int64_t)T * D) return DLRM_E_ARG;
     hipStream_t st = (hipStream_t)stream;
 
@@ -396,24 +306,12 @@ static int emb_fwd_quant_impl(int T, int64_t B, int D, int bits, const void* con
     bool vec_ok = D % 8 == 0 && D <= 512 && dlrm_aligned16(out) && (out_ld % 4 == 0);
     for (int t = 0; t < T; ++t) vec_ok = vec_ok && (((uintptr_t)weight_host[t]) & row_align) == 0;
     int lpb = 0;                                     // 0: the byte-wise kernel
-    if (vec_ok) { lpb = pow2ceil(D / 8); if (lpb < 4) lpb = 4; }
+    if (vec_ok) lpb = lanes_per_bag(D / 8);
 
     for (int t0 = 0; t0 < T; t0 += DLRM_MAX_TABLES_PER_LAUNCH) {
         const int n = (T - t0 < DLRM_MAX_TABLES_PER_LAUNCH) ? T - t0 : DLRM_MAX_TABLES_PER_LAUNCH;
         EmbArgs a;
-        a.err = (long long*)err;
-        a.pred = pred;
-        for (int k = 0; k < DLRM_MAX_TABLES_PER_LAUNCH; ++k) {
-            const int t = t0 + (k < n ? k : 0);
-            a.w[k] = (float*)weight_host[t];         // (packed bytes; the kernels read them as uint8_t)
-            a.idx[k] = indices_host[t];
-            a.off[k] = offsets_host[t];
-            a.psw[k] = psw_host ? (const float*)psw_host[t] : nullptr;
-            a.nnz[k] = nnz_host[t];
-            a.rows[k] = rows_host[t];
-            a.slot[k] = t;
-        }
-        int rc;
+        emb_fill_args(a, t0, n, weight_host, rows_host, indices_host, offsets_host, nnz_host, psw_host, err, pred);
         if (bits == 8) rc = idx_bits == 64 ? launch_fwd_quant<8, long long>(lpb, a, n, B, D, out, out_ld, st)
                                            : launch_fwd_quant<8, int>(lpb, a, n, B, D, out, out_ld, st);
         else           rc = idx_bits == 64 ? launch_fwd_quant<4, long long>(lpb, a, n, B, D, out, out_ld, st)

@@ -1,25 +1,14 @@
-// sorted_common.h — pieces shared by the sort-based embedding updates (emb_sorted.hip: SGD, adagrad.hip: row-wise
-// Adagrad): vector helpers, the (table,row) key expansion kernel, and the workspace layout around rocPRIM's radix sort.
+// sorted_common.h — pieces shared by the sort-based embedding updates (emb_sorted.hip: SGD; sorted_walk.h: the walk of adagrad.hip and
+// emb_bf16.hip): vector helpers, the (table,row) key expansion kernel, and the workspace layout around rocPRIM's radix sort.
 #pragma once
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
-#include "common.h"
+#include "emb_lookup.h"
 #include "seg_sort.h"
 
 namespace {
 
-
-template <int VEC> struct Vec;
-template <> struct Vec<4> { using T = float4; };
-template <> struct Vec<1> { using T = float; };
-
-__device__ __forceinline__ void v_zero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void v_zero(float& a) { a = 0.f; }
-__device__ __forceinline__ void v_fma(float4& a, float w, const float4& v) {
-    a.x = __builtin_fmaf(w, v.x, a.x); a.y = __builtin_fmaf(w, v.y, a.y);
-    a.z = __builtin_fmaf(w, v.z, a.z); a.w = __builtin_fmaf(w, v.w, a.w);
-}
-__device__ __forceinline__ void v_fma(float& a, float w, const float& v) { a = __builtin_fmaf(w, v, a); }
+// (Vec, v_zero, v_fma, pow2ceil and the lane geometry: emb_lookup.h)
 __device__ __forceinline__ float4 v_mul(float s, const float4& v) { return make_float4(s * v.x, s * v.y, s * v.z, s * v.w); }
 __device__ __forceinline__ float v_mul(float s, const float& v) { return s * v; }
 __device__ __forceinline__ void v_atomic_add(float* p, const float4& v) {
@@ -146,7 +135,6 @@ __global__ __launch_bounds__(256) void single_mask_kernel(long long L, int row_b
     if (sorted_entry_is_single<KT>(k, hp, pk, hn, nk, bag)) atomicOr(mask + bag, 1u << (unsigned)(k >> row_bits));
 }
 
-static int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 static int bits_for(long long n) { int b = 0; while (((long long)1 << b) < n) ++b; return b < 1 ? 1 : b; }
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -52,7 +52,7 @@ ROWS = [1000, 50, 7]
 
 
 @pytest.mark.parametrize("kind", ["onehot", "ragged"])
-@pytest.mark.parametrize("D", [8, 16, 64, 128, 136, 12])       # 12: the 2-bytes-per-lane path
+@pytest.mark.parametrize("D", [8, 16, 64, 128, 136, 256, 512, 12])       # 256 / 512: 32 / 64 lanes per bag; 12: the 2-bytes-per-lane path
 def test_lookup_is_bit_identical_to_the_fp32_lookup_on_upcast_tables(D, kind):
     from dlrm_amd import ops
     rng = np.random.default_rng(1000 * D + len(kind))
@@ -74,6 +74,31 @@ def test_lookup_is_bit_identical_to_the_fp32_lookup_on_upcast_tables(D, kind):
                     ops.emb_fwd_bf16(tables[:T], ops.BagBatch(lS_o, lS_i, psw), feat_b[:, D:(T + 1) * D])
                     assert torch.equal(feat_a.view(torch.int32), feat_b.view(torch.int32)), (D, kind, B, T, idx_dtype, with_psw)
                     assert bool((feat_b[:, :D] == 7.0).all()) and bool((feat_b[:, (T + 1) * D:] == 7.0).all())
+    ops.check_index_errors(sync=True)
+
+
+def test_lookup_of_33_tables_crosses_the_launch_group_bit_identically():
+    """33 tables of 7 rows, B = 5 bags of 0, 1, 5, 9 and 3 lookups: launch groups of 32 + 1; the first-row phase, one and two rounds of the
+    4-deep loop and its tail"""
+    from dlrm_amd import ops
+    rng = np.random.default_rng(3333)
+    T, rows, D, B = 33, 7, 16, 5
+    tables = [bf16_table(random_bf16(rng, (rows, D))) for _ in range(T)]
+    up = [w.float() for w in tables]
+    off = np.asarray([0, 0, 1, 6, 15], dtype=np.int64)
+    idx = [rng.integers(0, rows, size=18).astype(np.int64) for _ in range(T)]
+    for idx_dtype in (torch.int64, torch.int32):
+        for with_psw in (False, True):
+            lS_o = [to_dev(off, idx_dtype)] * T
+            lS_i = [to_dev(i, idx_dtype) for i in idx]
+            psw = [to_dev(rng.uniform(0.5, 1.5, size=18).astype(np.float32)) for _ in range(T)] if with_psw else None
+            # into a wider feature buffer, as the test above
+            a = torch.full((B, (T + 2) * D), 7.0, dtype=torch.float32, device=dev())
+            b = torch.full((B, (T + 2) * D), 7.0, dtype=torch.float32, device=dev())
+            ops.emb_fwd(up, ops.BagBatch(lS_o, lS_i, psw), a[:, D:(T + 1) * D])
+            ops.emb_fwd_bf16(tables, ops.BagBatch(lS_o, lS_i, psw), b[:, D:(T + 1) * D])
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (idx_dtype, with_psw)
+            assert bool((b[:, :D] == 7.0).all()) and bool((b[:, (T + 1) * D:] == 7.0).all())
     ops.check_index_errors(sync=True)
 
 
@@ -206,7 +231,7 @@ def dup_case(seed, D, with_psw):
 
 
 @pytest.mark.parametrize("with_psw", [False, True])
-@pytest.mark.parametrize("D", [16, 128, 6])
+@pytest.mark.parametrize("D", [16, 128, 6, 66, 512])          # 66 / 512: two chunks per lane at one / four columns per lane
 def test_rowwise_adagrad_has_the_fp32_kernels_accumulators_and_its_rows_rounded_once(D, with_psw):
     from dlrm_amd import ops
     W, offs, idxs, g, psw = dup_case(100 + D, D, with_psw)
@@ -233,6 +258,36 @@ def test_rowwise_adagrad_has_the_fp32_kernels_accumulators_and_its_rows_rounded_
             want = W[t].copy()
             want[touched] = H.round_rows(ref_rows[t][touched], mode, t, touched, seed)
             assert np.array_equal(bits_of(tabs[t]), want), (mode, t)
+
+
+def test_rowwise_adagrad_of_a_row_with_700_lookups_has_the_fp32_kernels_accumulator():
+    """one row named by 700 of 760 lookups: its run spans more than nine 64-entry groups, so the fix-up pass's 8-deep loop and its tail both
+    run; accumulators and rows as in the test above"""
+    from dlrm_amd import ops
+    rng = np.random.default_rng(700)
+    D, rows, B = 16, 50, 760
+    W = random_bf16(rng, (rows, D))
+    idx = rng.integers(0, rows, size=B).astype(np.int64)
+    idx[rng.permutation(B)[:700]] = 5
+    g = rng.uniform(-1.0, 1.0, size=(B, D)).astype(np.float32)
+    state0 = rng.uniform(0.0, 0.1, size=rows).astype(np.float32)
+    lr, eps = 0.01, 1e-8
+
+    def bags():
+        return ops.BagBatch([to_dev(np.arange(B, dtype=np.int64))], [to_dev(idx)])
+
+    ref_w, ref_s = [bf16_table(W).float()], [to_dev(state0)]
+    ops.emb_bwd_rowwise_adagrad(ref_w, ref_s, bags(), to_dev(g), lr, eps)
+    ref_rows = ref_w[0].cpu().numpy()
+    touched = np.unique(idx)
+    for mode, seed in (("nearest", 0), ("stochastic", 31337)):
+        tabs, st = [bf16_table(W)], [to_dev(state0)]
+        ops.emb_bwd_rowwise_adagrad_bf16(tabs, st, bags(), to_dev(g), lr, eps, mode, seed)
+        ops.check_index_errors(sync=True)
+        assert torch.equal(st[0].view(torch.int32), ref_s[0].view(torch.int32)), mode
+        want = W.copy()
+        want[touched] = H.round_rows(ref_rows[touched], mode, 0, touched, seed)
+        assert np.array_equal(bits_of(tabs[0]), want), mode
 
 
 def sgd_band(W, offs, idxs, g, psw, D, lr):

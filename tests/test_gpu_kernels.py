@@ -34,7 +34,8 @@ def to_dev(a, dtype=None):
 
 
 # ------------------------------------------------------------------------------------------ embeddings
-@pytest.mark.parametrize("D", [1, 2, 12, 16, 64, 128, 200, 256, 512])
+# 6: one column per lane, 8 lanes; 66 / 130: one column per lane, 64 lanes, 2 / 4 chunks; 1024: four columns per lane, 4 chunks
+@pytest.mark.parametrize("D", [1, 2, 6, 12, 16, 64, 66, 128, 130, 200, 256, 512, 1024])
 @pytest.mark.parametrize("idx_dtype", [torch.int64, torch.int32])
 def test_emb_fwd_bit_exact(D, idx_dtype):
     from dlrm_amd import ops
@@ -58,6 +59,26 @@ def test_emb_fwd_bit_exact(D, idx_dtype):
     got = out.cpu().numpy()
     assert np.array_equal(got, want)
     assert torch.all(buf[:, :D] == -7.0) and torch.all(buf[:, D + len(rows) * D:] == -7.0)
+
+
+def launch_group_bags(rng, T, rows):
+    """B = 5 bags per table of 0, 1, 5, 9 and 3 lookups: none, the first-row phase alone, one and two rounds of the 4-deep loop, its tail"""
+    off = np.asarray([0, 0, 1, 6, 15], dtype=np.int64)
+    return [(off, rng.integers(0, rows, size=18).astype(np.int64)) for _ in range(T)]
+
+
+def test_emb_fwd_33_tables_cross_the_launch_group_bit_exact():
+    """33 tables: one call, launch groups of 32 + 1 (DLRM_MAX_TABLES_PER_LAUNCH)"""
+    from dlrm_amd import ops
+    rng = np.random.default_rng(33)
+    T, rows, D, B = 33, 7, 16, 5
+    Ws = [rng.standard_normal((rows, D)).astype(np.float32) for _ in range(T)]
+    bags = launch_group_bags(rng, T, rows)
+    want = np.concatenate([O.emb_fwd(W, i, o) for W, (o, i) in zip(Ws, bags)], axis=1)
+    out = torch.empty(B, T * D, device=dev())
+    ops.emb_fwd([to_dev(W) for W in Ws], ops.BagBatch([to_dev(o) for o, _ in bags], [to_dev(i) for _, i in bags]), out)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy(), want)
 
 
 @pytest.mark.parametrize("idx_dtype", [torch.int64, torch.int32])
@@ -1487,7 +1508,8 @@ def test_multihot_generated_tables_match_philox_oracle():
 
 # ------------------------------------------------------------------------------------------ K4: row-wise Adagrad
 @pytest.mark.parametrize("D,rows,B,max_len", [(16, [3, 40, 5000], 300, 5), (128, [4, 10, 130, 100000], 700, 3),
-                                              (6, [2, 9], 97, 4), (64, [1, 3], 5000, 2), (200, [7, 300], 260, 6)])
+                                              (6, [2, 9], 97, 4), (64, [1, 3], 5000, 2), (200, [7, 300], 260, 6),
+                                              (66, [3, 40], 150, 4), (512, [2, 30], 120, 3)])     # 2 chunks at either lane width
 @pytest.mark.parametrize("idx_dtype", [torch.int64, torch.int32])
 def test_emb_bwd_rowwise_adagrad_matches_oracle(D, rows, B, max_len, idx_dtype):
     """Fused backward + row-wise sparse Adagrad vs the C oracle (pinned to optim/rwsadagrad.py by

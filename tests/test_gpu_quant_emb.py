@@ -96,12 +96,12 @@ def make_bags(rng, rows_list, B, kind, weighted):
     return offs, idxs, psws
 
 
-def run_and_check(bits, D, rows_list, B, kind, idx_dtype, weighted, wide, seed, tables=None):
+def run_and_check(bits, D, rows_list, B, kind, idx_dtype, weighted, wide, seed, tables=None, bags=None):
     from dlrm_amd import ops
     rng = np.random.default_rng(seed)
     T = len(rows_list)
     q_dev, q_host = tables if tables is not None else make_tables(rows_list, D, bits, seed)
-    offs, idxs, psws = make_bags(rng, rows_list, B, kind, weighted)
+    offs, idxs, psws = bags if bags is not None else make_bags(rng, rows_list, B, kind, weighted)
     bags = ops.BagBatch([to_dev(o, idx_dtype) for o in offs], [to_dev(i, idx_dtype) for i in idxs],
                         [to_dev(p) for p in psws] if weighted else None)
     CANARY = 7.5
@@ -129,10 +129,20 @@ def run_and_check(bits, D, rows_list, B, kind, idx_dtype, weighted, wide, seed, 
 
 
 @pytest.mark.parametrize("bits", [8, 4])
-@pytest.mark.parametrize("D", [8, 12, 16, 64, 128, 256])
+@pytest.mark.parametrize("D", [8, 12, 16, 64, 128, 256, 512])       # 512: 64 lanes per bag
 @pytest.mark.parametrize("weighted", [False, True])
 def test_lookup_one_table_ragged(bits, D, weighted):
     run_and_check(bits, D, [3000], 512, "ragged", torch.int64, weighted, wide=False, seed=100 + D + bits)
+
+
+def test_lookup_33_tables_cross_the_launch_group():
+    """33 8-bit tables of 7 rows, B = 5 bags of 0, 1, 5, 9 and 3 lookups: launch groups of 32 + 1; the first-row phase, one and two rounds of
+    the 4-deep loop and its tail"""
+    rng = np.random.default_rng(3308)
+    T, rows = 33, 7
+    off = np.asarray([0, 0, 1, 6, 15], dtype=np.int64)
+    bags = ([off] * T, [rng.integers(0, rows, size=18).astype(np.int64) for _ in range(T)], [None] * T)
+    run_and_check(8, 16, [rows] * T, 5, "ragged", torch.int64, False, wide=False, seed=3308, bags=bags)
 
 
 @pytest.mark.parametrize("bits", [8, 4])
