@@ -10,7 +10,7 @@ Backward runs on the autograd engine's thread: streams/devices are looked up at 
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import weakref
 
@@ -112,6 +112,15 @@ def _side_stream(device) -> "torch.cuda.Stream":
     return st
 
 
+def _wgrad_overlaps(M: int) -> bool:
+    """the weight-gradient GEMMs of an M-row backward pass go to the side stream: always with OVERLAP_WGRAD; otherwise for SMALL batches
+    — Criteo-Kaggle's 2048 rows — where every GEMM of the step occupies a fraction of the chip, so the independent weight-gradient launch runs
+    BESIDE the data-gradient launch for free; the fork / join are events a graph capture records — measured at Criteo-Kaggle shapes: graphed
+    step 0.515 -> 0.497 ms; in the EAGER step the two extra event records per layer cost the host more than the overlap saves
+    (1.51 -> 1.74 ms), so only a capturing stream forks"""
+    return OVERLAP_WGRAD or (0 < SMALL_BATCH_OVERLAP and M <= SMALL_BATCH_OVERLAP and torch.cuda.is_current_stream_capturing())
+
+
 # A parameter wrapped by ext_dist.FlatDDP carries `p._dlrm_grad_arena = (weakref to the flat fp32 gradient buffer, element offset)`:
 # the weight-gradient GEMMs of MLPFunction write such a parameter's gradient straight into the flat buffer that FlatDDP all-reduces
 # (no bucket copy in, none out).  The slot lives ON the Parameter object (not in a table keyed by its address): a tower that is
@@ -176,23 +185,159 @@ class OutSlot:
         return self._view[:]  # fresh tensor object sharing the storage (gets its own grad_fn)
 
 
-def _tower_applies(x, arith, params, L) -> bool:
+_F32, _BF16, _BF16X6 = (ops.arith_code(a) for a in ("f32", "bf16", "bf16x6"))
+
+
+def _tower_path_ok(M, in_width, dims, arith, on_gpu) -> bool:
     """the small-batch tower kernels take this MLP: native fp32, a batch of at most TOWER_ROWS rows, widths the kernels hold in LDS, and
     little enough weight traffic — every 16-row workgroup streams ALL weights, (M / 16) x parameters x 4 bytes through L2, which is what
     bounds the path to small batches x small towers (Criteo-Kaggle: 128 x 1.3 MB; the Criteo-Terabyte towers at 2048 rows would move 1.1 GB)"""
-    if TOWER_ROWS <= 0 or not x.is_cuda or arith != ops.arith_code("f32"):
+    if TOWER_ROWS <= 0 or not on_gpu or arith != _F32:
         return False
-    M = x.size(0)
-    K0 = params[0].size(1)
-    if M < 1 or M > TOWER_ROWS or x.size(1) not in (K0, _round4(K0)) or L > ops.TOWER_MAX_LAYERS:
+    L = len(dims)
+    K0 = dims[0][1]
+    if M < 1 or M > TOWER_ROWS or in_width not in (K0, _round4(K0)) or L > ops.TOWER_MAX_LAYERS:
         return False
-    widths = [x.size(1)] + [params[2 * i].size(0) for i in range(L)]
+    widths = [in_width] + [N for N, _ in dims]
     if not ops.tower_ok(M, widths):
         return False
-    if any(params[2 * i].size(1) != (K0 if i == 0 else widths[i]) for i in range(L)):
+    if any(dims[i][1] != (K0 if i == 0 else widths[i]) for i in range(L)):
         return False
     weight_bytes = 4 * sum(widths[i] * widths[i + 1] for i in range(L))
     return ((M + 15) // 16) * weight_bytes <= TOWER_L2_BYTES
+
+
+def _tower_applies(x, arith, params, L) -> bool:
+    return _tower_path_ok(x.size(0), x.size(1), [(params[2 * i].size(0), params[2 * i].size(1)) for i in range(L)], arith, x.is_cuda)
+
+
+class LayerPlan(NamedTuple):
+    """one layer of a TowerPlan: y = act(in . W^T + b), W [N, K] (K of the first layer: the padded width its GEMMs run on)"""
+    N: int
+    K: int
+    act: int
+    # forward
+    out32: bool = True          # the fp32 output is allocated (and saved for backward)
+    fwd16: bool = False         # kernel form: st.gemm on reduced-width operands (else ops.linear_fwd on fp32)
+    kb: int = 0                 # ... whose reduction length is padded to this
+    out16: bool = False         # the reduced-width output is allocated: the next layer's GEMM reads it as it is
+    bits: bool = False          # ReLU sign bits are allocated (a hidden ReLU layer of a tower that keeps bits)
+    w16_multi: bool = False     # W16 comes out of the tower's multi-cast launch
+    wT16_multi: bool = False    # ... and so does W^T16, for the data gradient
+    # backward
+    wgrad16: bool = False       # weight gradient from the reduced-width operands as stored; forward keeps its reduced-width input for it
+    need_dx: bool = True        # a data gradient is computed (the first layer's only if the tower's input wants one)
+    dgrad16: bool = False       # data gradient as a reduced-width GEMM over W^T16 (else ops.linear_bwd_data on fp32)
+    dx32: bool = True           # the data gradient is written as fp32
+    dx16: bool = False          # ... in reduced width (both may hold)
+    mask_act: int = ACT_NONE    # the derivative its epilogue applies: the activation of the layer below
+    mask_bits: bool = False     # ... read from that layer's sign bits (the fp32 form also needs its fp32 output; the reduced-width one does not)
+
+
+class TowerPlan(NamedTuple):
+    """every decision MLPFunction makes for one call, forward and backward (_plan_tower); neither pass derives any of them again"""
+    layers: tuple
+    acts: tuple
+    arith: int
+    whole_tower: bool           # backward (and with tower_fwd: forward) on the whole-tower kernels of csrc/tower.hip
+    tower_fwd: bool
+    store: Optional[type]       # None, _Bf16Store or _PlaneStore: how reduced-width copies are kept
+    in_width: int               # width of x as it arrives
+    pad_x: bool                 # x is copied into a zero-padded buffer Kp wide
+    Kp: int                     # the first weight is zero-padded to this width (0: used as it is)
+    need_bits: bool
+    multi_cast: bool            # all W16 / W^T16 of the tower in one launch
+    need_dx: bool               # the tower's input wants a gradient
+    head_fused: bool            # backward may try the one-pass N == 1 head
+    consumer_act: bool          # MLP_CONSUMER_APPLIES_LAST_ACT
+
+
+_WIDTH_ERR = "dlrm_amd: MLP input width %d does not match the first layer (%d)"
+
+
+def _plan_tower(M, in_width, dims, acts, arith, need_grad, need_dx, on_gpu, has_slot=False, slot_aligned=True, consumer_act=False) -> TowerPlan:
+    """The storage and kernel plan of one MLPFunction call, from integers and booleans alone (dims: (N_i, K_i) of every weight; slot_aligned:
+    the out_slot's rows are 16-byte aligned, ld % 4 == 0).  Allocates nothing; reads the module switches when called."""
+    L = len(dims)
+    K0 = dims[0][1]
+    f32 = arith == _F32
+    if _tower_path_ok(M, in_width, dims, arith, on_gpu):
+        # nothing has to be padded for the tower kernels: an input that arrives unpadded (13 dense features) is read with element loads; an
+        # input that arrives padded to a multiple of 4 (the interaction's 367 -> 368 columns) meets a zero-padded copy of the first weight.
+        # The per-layer forward GEMMs (no tower_fwd) pad an unaligned input as the per-layer path does
+        pad_x = in_width == K0 and in_width % 4 != 0 and not TOWER_FWD
+        Kp = in_width if in_width != K0 else _round4(K0) if pad_x else 0
+        layers = (LayerPlan(dims[0][0], Kp or K0, acts[0], need_dx=need_dx), *[LayerPlan(dims[i][0], dims[i][1], acts[i]) for i in range(1, L)])
+        return TowerPlan(layers, acts, arith, True, TOWER_FWD, None, in_width, pad_x, Kp, False, False, need_dx, False, consumer_act)
+    # first layer: an input width that is no multiple of 4 floats runs on a zero-padded weight and a zero-padded input (x may already be one)
+    Kp = _round4(K0) if K0 % 4 != 0 else 0
+    if in_width != K0 and in_width != (Kp or K0):
+        raise RuntimeError(_WIDTH_ERR % (in_width, K0))
+    pad_x = Kp != 0 and in_width != Kp
+    # sign bits: a forward that will be differentiated (Function.forward itself runs grad-free), and not a SMALL batch — there the GEMMs run
+    # on 64 x 64 tiles that neither write nor read the bits (the bits would come from a stand-alone kernel: one more launch per layer of a
+    # launch-bound step) and the data gradient reads the fp32 activation, which small batches keep in cache anyway
+    need_bits = bool(RELU_BITS and need_grad and (M > SMALL_BATCH_BITS or (BF16_STORAGE and arith == _BF16) or
+                                                  (BF16X6_PLANES and arith == _BF16X6)))
+    # arith "bf16" with bf16 STORAGE (default; DLRM_BF16_STORAGE=0 restores the in-loop rounding of rounds 1-2): every GEMM layer reads a
+    # bf16 copy of its input and of its weight (dlrm_gemm_bf16: no conversion in the k-loop).  LEAN (default, DLRM_BF16_LEAN=0 turns it
+    # off): a hidden activation is written ONLY as bf16 + ReLU sign bits when every consumer reads those — the next layer's forward
+    # GEMM, its weight gradient (dlrm_linear_bwd_weight_bf16 reads bf16 operands k-strided) and the data-gradient mask (sign bits); the
+    # fp32 copy (4 of the 6 bytes written per element) exists only where something reads it: the tower's output, the input of a
+    # matrix-vector layer, layers whose shapes the bf16 weight gradient does not take.  Same operand rounding and accumulation
+    # order as the in-loop path for every product.
+    # arith "bf16x6" with PLANES (default): the same plan with every bf16 copy replaced by the three planes of the fp32 tensor (always lean)
+    st = _Bf16Store if (BF16_STORAGE and arith == _BF16) else None
+    lean = st is not None and BF16_LEAN
+    if BF16X6_PLANES and arith == _BF16X6 and M >= 256 and RELU_BITS and ops.BF16_PHASED:
+        st, lean = _PlaneStore, True
+    Ns = [N for N, _ in dims]
+    Ks = [(Kp or K) if i == 0 else K for i, (_, K) in enumerate(dims)]
+    mask = [ACT_NONE] + list(acts[:L - 1])                          # the derivative layer i's data gradient applies
+    mbits = [i > 0 and mask[i] == ACT_RELU and need_bits for i in range(L)]
+    dx = [i > 0 or need_dx for i in range(L)]
+    if st is None:
+        layers = tuple(LayerPlan(Ns[i], Ks[i], acts[i], bits=mbits[i + 1] if i + 1 < L else False, need_dx=dx[i], mask_act=mask[i],
+                                 mask_bits=mbits[i]) for i in range(L))
+        head = bool(HEAD_FUSED and Ns[-1] == 1 and L >= 2 and f32 and not consumer_act)
+        return TowerPlan(layers, acts, arith, False, False, None, in_width, pad_x, Kp, need_bits, False, need_dx, head, consumer_act)
+    kb = [st.kround(K) for K in Ks]
+    fwd16 = [Ns[i] % 4 == 0 and Ns[i] != 1 and st.fwd_ok(M, Ns[i], kb[i]) for i in range(L)]
+    if has_slot and not slot_aligned:
+        fwd16[L - 1] = False
+    # weight gradient of layer i from reduced-width operands as stored (the input of its forward GEMM, dZ16_i).  The input width asked
+    # about is the PADDED one, where the tensor-level check at backward time (st.wgrad_ok) rounds the gradient's stored width up to 8:
+    # for first-layer widths 57-60 the two differ (60 < 64 here, 64 there) and this, the stricter answer, is the one that decides
+    wg16 = [bool(lean and need_grad and fwd16[i] and ops.linear_bwd_weight_bf16_shapes_ok(M, Ns[i], Ks[i])) for i in range(L)]
+    # data gradient of layer i (dX = dZ . W) on reduced-width operands: reduction over N_i
+    # (its epilogue applies the derivative of the activation BELOW it: none, or ReLU through that layer's sign bits)
+    dg16 = [fwd16[i] and Ns[i] % 32 == 0 and Ks[i] % 4 == 0 and st.fwd_ok(M, Ks[i], Ns[i]) and (mask[i] == ACT_NONE or mbits[i]) for i in range(L)]
+    out16 = [i + 1 < L and fwd16[i] and fwd16[i + 1] and kb[i + 1] == Ns[i] for i in range(L)]
+    reads16 = [wg16[i] or (dg16[i] and dx[i]) for i in range(L)]    # backward of layer i reads its incoming gradient in reduced width
+    # every weight copy of the tower in ONE launch (bf16 storage; the planes form keeps its per-layer splits): W16 [N, kb] for the forward
+    # GEMM of a reduced-width layer, W^T16 [K, N] for its data gradient where backward will take that path (weights do not change in between)
+    multi, w16m, wT16m = False, [False] * L, [False] * L
+    if st is _Bf16Store and MULTI_CAST:
+        wT = [need_grad and dg16[i] and dx[i] for i in range(L)]
+        if sum(fwd16[i] or wT[i] for i in range(L)) > 1:
+            multi, w16m, wT16m = True, fwd16, wT
+    layers = []
+    for i in range(L):
+        # the fp32 output: not lean, the tower's output, or the next layer's forward GEMM does not take the reduced-width one as it is ...
+        out32 = (not lean) or not out16[i]
+        if not out32 and need_grad:
+            # ... or a backward consumer reads it: the next layer's weight gradient when it is not the reduced-width one; its DATA gradient
+            # when it is not (widths the bf16 / plane GEMM refuses, e.g. 200 or 72: the fp32-storage fallback, ops.linear_bwd_data, masks
+            # with this activation, the sign bits alone would not do); the ReLU derivative when there are no sign bits; any other
+            # activation's derivative
+            out32 = (not wg16[i + 1]) or (not dg16[i + 1]) or (acts[i] == ACT_RELU and not need_bits) or acts[i] not in (ACT_RELU, ACT_NONE)
+        # what the layer below reads of this layer's data gradient: its reduced-width weight / data gradient take the reduced-width copy;
+        # fp32 is written only when something reads it (the tower's input gradient, an fp32-storage weight / data gradient below)
+        want16 = i > 0 and reads16[i - 1] and Ks[i] % 32 == 0
+        want32 = i == 0 or not want16 or not (wg16[i - 1] and (dg16[i - 1] or not dx[i - 1]))
+        layers.append(LayerPlan(Ns[i], Ks[i], acts[i], out32, fwd16[i], kb[i], out16[i], mbits[i + 1] if i + 1 < L else False, w16m[i], wT16m[i],
+                                wg16[i], dx[i], dg16[i], want32 or not dg16[i], want16 and dg16[i], mask[i], mbits[i]))    # (in field order)
+    return TowerPlan(tuple(layers), acts, arith, False, False, st, in_width, pad_x, Kp, need_bits, multi, need_dx, False, consumer_act)
 
 
 class MLPFunction(Function):
@@ -214,221 +359,150 @@ class MLPFunction(Function):
         # MLP_CONSUMER_APPLIES_LAST_ACT OR-ed into `arith`: the gradient this tower receives is already multiplied by the derivative of its
         # LAST activation (a ReLU) — the interaction backward does that to its feature-0 gradient on request (ops.INTERACT_RELU_X), so
         # backward starts from dY as it comes instead of with an act_bwd pass over [M, N_last]
-        ctx.consumer_applies_last_act = bool(int(arith) & MLP_CONSUMER_APPLIES_LAST_ACT)
+        consumer_act = bool(int(arith) & MLP_CONSUMER_APPLIES_LAST_ACT)
         arith = int(arith) & ~MLP_CONSUMER_APPLIES_LAST_ACT
-        if ctx.consumer_applies_last_act and acts[-1] != ACT_RELU:
+        if consumer_act and acts[-1] != ACT_RELU:
             raise RuntimeError("dlrm_amd: MLP_CONSUMER_APPLIES_LAST_ACT needs a tower that ends in a ReLU")
-        ctx.arith = arith
         L = len(acts)
         M = x.size(0)
-        W0 = params[0]
-        K0, Kp = W0.size(1), _round4(W0.size(1))
-        ctx.in_width = x.size(1)
-        ctx.tower = False
-        if _tower_applies(x, arith, params, L):
-            return MLPFunction._tower_forward(ctx, x, acts, out_slot, params)
-        W0p = None
-        if Kp != K0:
-            if x.size(1) != Kp:
-                if x.size(1) != K0:
-                    raise RuntimeError("dlrm_amd: MLP input width %d does not match the first layer (%d)" % (x.size(1), K0))
-                x = ops.pad_cols(x, Kp)
-            W0p = ops.pad_cols(W0, Kp)
-        elif x.size(1) != K0:
-            raise RuntimeError("dlrm_amd: MLP input width %d does not match the first layer (%d)" % (x.size(1), K0))
-        cur = x
-        need_grad = any(ctx.needs_input_grad)
-        # sign bits: a forward that will be differentiated (Function.forward itself runs grad-free), and not a SMALL batch — there the GEMMs run
-        # on 64 x 64 tiles that neither write nor read the bits (the bits would come from a stand-alone kernel: one more launch per layer of a
-        # launch-bound step) and the data gradient reads the fp32 activation, which small batches keep in cache anyway
-        need_bits = RELU_BITS and need_grad and (M > SMALL_BATCH_BITS or (BF16_STORAGE and arith == ops.arith_code("bf16")) or
-                                                 (BF16X6_PLANES and arith == ops.arith_code("bf16x6")))
-        # arith "bf16" with bf16 STORAGE (default; DLRM_BF16_STORAGE=0 restores the in-loop rounding of rounds 1-2): every GEMM layer reads a
-        # bf16 copy of its input and of its weight (dlrm_gemm_bf16: no conversion in the k-loop).  LEAN (default, DLRM_BF16_LEAN=0 turns it
-        # off): a hidden activation is written ONLY as bf16 + ReLU sign bits when every consumer reads those — the next layer's forward
-        # GEMM, its weight gradient (dlrm_linear_bwd_weight_bf16 reads bf16 operands k-strided) and the data-gradient mask (sign bits); the
-        # fp32 copy (4 of the 6 bytes written per element) exists only where something reads it: the tower's output, the input of a
-        # matrix-vector layer, layers whose shapes the bf16 weight gradient does not take.  Same operand rounding and accumulation
-        # order as the in-loop path for every product.
-        # arith "bf16x6" with PLANES (default): the same plan with every bf16 copy replaced by the three planes of the fp32 tensor (always lean)
-        st = _Bf16Store
-        store16 = BF16_STORAGE and arith == ops.arith_code("bf16")
-        lean = store16 and BF16_LEAN
-        if BF16X6_PLANES and arith == ops.arith_code("bf16x6") and M >= 256 and RELU_BITS and ops.BF16_PHASED:
-            st, store16, lean = _PlaneStore, True, True
-        ctx.st = st
-        widths = [params[2 * i].size(0) for i in range(L)]                                   # N_i
-        kin = [W0p.size(1) if (i == 0 and W0p is not None) else params[2 * i].size(1) for i in range(L)]
         out_last = out_slot.get() if out_slot is not None else None
-        kb = [st.kround(kin[i]) for i in range(L)]
-        use16 = [store16 and widths[i] % 4 == 0 and widths[i] != 1 and st.fwd_ok(M, widths[i], kb[i]) for i in range(L)]
-        if out_last is not None and use16[L - 1] and not (_ld(out_last) % 4 == 0 and out_last.data_ptr() % 16 == 0):
-            use16[L - 1] = False
-        # weight gradient of layer i from bf16 operands as stored (X16_i = the bf16 input of its forward GEMM, dZ16_i)
-        wg16 = [lean and need_grad and use16[i] and M >= 256 and M % 64 == 0 and widths[i] % 8 == 0 and widths[i] >= 64 and kin[i] >= 64
-                and ops.BF16_PHASED for i in range(L)]
-        # data gradient of layer i (dX = dZ . W) on bf16 operands: reduction over widths[i]
-        # (its epilogue applies the derivative of the activation BELOW it: none, or ReLU through that layer's sign bits)
-        dg16 = [store16 and use16[i] and widths[i] % 32 == 0 and kin[i] % 4 == 0 and st.fwd_ok(M, kin[i], widths[i]) and
-                (i == 0 or acts[i - 1] == ACT_NONE or (acts[i - 1] == ACT_RELU and need_bits)) for i in range(L)]
-        need32 = []
-        for i in range(L):
-            n32 = (not lean) or i == L - 1 or not use16[i] or not use16[i + 1] or kb[i + 1] != widths[i]
-            if not n32 and need_grad:
-                # backward consumers of the fp32 activation: the next layer's weight gradient when it is not the bf16 one; the ReLU
-                # derivative when there are no sign bits; any other activation's derivative
-                # ... and the next layer's DATA gradient when it is not the bf16 one (widths the bf16 / plane GEMM refuses, e.g. 200 or 72):
-                # the fp32-storage fallback masks with this activation (ops.linear_bwd_data), the sign bits alone would not do
-                n32 = ((not wg16[i + 1]) or (not dg16[i + 1]) or (acts[i] == ACT_RELU and not need_bits)
-                       or acts[i] not in (ACT_RELU, ACT_NONE))
-            need32.append(n32)
-        # every weight copy of the tower in ONE launch (bf16 storage; the planes form keeps its per-layer splits): W16 [N, kb] for the forward
-        # GEMM of a use16 layer, W^T16 [K, N] for its data gradient where backward will take the bf16 path (weights do not change in between)
-        pre16, preT16 = [None] * L, [None] * L
-        if store16 and st is _Bf16Store and MULTI_CAST:
-            items, where = [], []
-            for i in range(L):
-                W_i = W0p if (i == 0 and W0p is not None) else params[2 * i]
-                want = kb[i] if use16[i] else None
-                wantT = widths[i] if (need_grad and dg16[i] and (i > 0 or ctx.needs_input_grad[0])) else None
-                if want or wantT:
-                    items.append((W_i, want, wantT)); where.append(i)
-            if len(items) > 1:
-                for i, (d_, dT_) in zip(where, st.cast_multi(items, category="linear_fwd")):
-                    pre16[i], preT16[i] = d_, dT_
-        ctx.preT16 = preT16
-        cur16 = None                                                  # bf16 copy of the current activation, [M, kb of the next layer]
-        outs, in16, bits = [], [], []                                   # in16[i]: the reduced-width input of layer i's GEMM, kept for its weight gradient
-        for i in range(L):
-            W, b = params[2 * i], params[2 * i + 1]
-            if i == 0 and W0p is not None:
-                W = W0p
-            N = widths[i]
-            y = (out_last if (i == L - 1 and out_last is not None) else alloc2d(M, N, x)) if need32[i] else None
-            # hidden ReLU layers also store their sign bits (1 bit per element): the data-gradient GEMM of the NEXT layer reads
-            # those instead of this fp32 activation for its fused ReLU derivative
-            rb = ops.relu_bits_alloc(M, N, x.device) if (i < L - 1 and acts[i] == ACT_RELU and need_bits) else None
-            y16 = None
-            if use16[i]:
-                a16 = cur16 if (cur16 is not None and cur16.size(-1) == kb[i]) else st.cast(cur, kb[i], category="linear_fwd")
-                in16.append(a16 if (lean and need_grad and wg16[i]) else None)
-                w16 = pre16[i] if pre16[i] is not None else st.cast(W, kb[i], category="linear_fwd")
-                # the bf16 copy of this activation, if the NEXT layer is a GEMM that can take it as it is
-                nxt = i + 1 < L and use16[i + 1] and kb[i + 1] == N
-                y16 = st.empty(M, N, x.device) if (nxt or not need32[i]) else None
-                st.gemm(a16, w16, b, acts[i], y, y16, relu_bits_out=rb, category="linear_fwd")
-            else:
-                in16.append(None)
-                ops.linear_fwd(cur, W, b, acts[i], y, arith, relu_bits=rb)
-            cur16 = y16
-            outs.append(y)
-            bits.append(rb)
-            cur = y
-        ctx.bits = bits
-        ctx.acts = acts
-        ctx.padded = W0p is not None
-        ctx.plan = (use16, wg16, dg16, need32, kb) if store16 else None
-        ctx.in16 = in16
-        ctx.have32 = [o is not None for o in outs]
+        plan = _plan_tower(M, x.size(1), [params[2 * i].shape for i in range(L)], acts, arith,
+                           any(ctx.needs_input_grad), ctx.needs_input_grad[0], x.is_cuda, out_last is not None,
+                           out_last is None or (_ld(out_last) % 4 == 0 and out_last.data_ptr() % 16 == 0), consumer_act)
+        ctx.plan = plan
+        # first-layer padding, the one place: Ws[i] is the weight layer i's GEMMs run on, forward and backward
+        Ws = [params[2 * i] for i in range(L)]
+        W0p = None
+        if plan.Kp:
+            if plan.pad_x:
+                x = ops.pad_cols(x, plan.Kp)
+            W0p = Ws[0] = ops.pad_cols(Ws[0], plan.Kp)
+        if plan.whole_tower:
+            outs = MLPFunction._tower_forward(plan, x, out_last, Ws, params)
+        else:
+            outs = MLPFunction._layers_forward(ctx, plan, x, out_last, Ws, params)
         ctx.save_for_backward(x, *params, *[o for o in outs if o is not None], *([W0p] if W0p is not None else []))
         return outs[-1]
 
     @staticmethod
-    def _tower_forward(ctx, x, acts, out_slot, params):
+    def _saved(ctx):
+        """x as the first layer read it, the parameters, every layer's fp32 output (None: the layer kept reduced width + sign bits only) and
+        the weights the GEMMs run on"""
+        layers = ctx.plan.layers
+        L = len(layers)
+        saved = ctx.saved_tensors
+        rest = iter(saved[1 + 2 * L:])
+        outs = [next(rest) if lp.out32 else None for lp in layers]
+        Ws = [saved[1 + 2 * i] for i in range(L)]
+        if ctx.plan.Kp:
+            Ws[0] = next(rest)
+        return saved[0], saved[1:1 + 2 * L], outs, Ws
+
+    @staticmethod
+    def _layers_forward(ctx, plan, x, out_last, Ws, params):
+        st, acts, layers = plan.store, plan.acts, plan.layers
+        L = len(layers)
+        M = x.size(0)
+        pre16, preT16 = [None] * L, [None] * L
+        if plan.multi_cast:
+            where = [i for i, lp in enumerate(layers) if lp.w16_multi or lp.wT16_multi]
+            items = [(Ws[i], layers[i].kb if layers[i].w16_multi else None, layers[i].N if layers[i].wT16_multi else None) for i in where]
+            for i, (d_, dT_) in zip(where, st.cast_multi(items, category="linear_fwd")):
+                pre16[i], preT16[i] = d_, dT_
+        cur, cur16 = x, None                                            # the current activation: fp32, and its reduced-width copy [M, kb of the next layer]
+        outs, in16, bits = [], [], []                                   # in16[i]: the reduced-width input of layer i's GEMM, kept for its weight gradient
+        for i, lp in enumerate(layers):
+            b = params[2 * i + 1]
+            y = (out_last if (i == L - 1 and out_last is not None) else alloc2d(M, lp.N, x)) if lp.out32 else None
+            # hidden ReLU layers also store their sign bits (1 bit per element): the data-gradient GEMM of the NEXT layer reads
+            # those instead of this fp32 activation for its fused ReLU derivative
+            rb = ops.relu_bits_alloc(M, lp.N, x.device) if lp.bits else None
+            y16 = None
+            if lp.fwd16:
+                a16 = cur16 if cur16 is not None else st.cast(cur, lp.kb, category="linear_fwd")
+                in16.append(a16 if lp.wgrad16 else None)
+                w16 = pre16[i] if pre16[i] is not None else st.cast(Ws[i], lp.kb, category="linear_fwd")
+                y16 = st.empty(M, lp.N, x.device) if lp.out16 else None
+                st.gemm(a16, w16, b, acts[i], y, y16, relu_bits_out=rb, category="linear_fwd")
+            else:
+                in16.append(None)
+                ops.linear_fwd(cur, Ws[i], b, acts[i], y, plan.arith, relu_bits=rb)
+            cur, cur16 = y, y16
+            outs.append(y)
+            bits.append(rb)
+        ctx.in16, ctx.bits, ctx.preT16 = in16, bits, preT16
+        return outs
+
+    @staticmethod
+    def _tower_forward(plan, x, out_last, Ws, params):
         """small batches, native fp32: this tower's BACKWARD pass will run on the whole-tower kernels of csrc/tower.hip (one launch for the
         data-gradient chain, one + one for all weight / bias gradients), so every layer's fp32 output is kept.  The forward pass is the
-        per-layer GEMMs by default, or (TOWER_FWD) one tower launch — activations of 16 batch rows stay in LDS from layer to layer, nothing
-        is padded: an input that arrives unpadded (13 dense features) is read with element loads; an input that arrives padded to a
-        multiple of 4 (the interaction's 367 -> 368 columns) meets a zero-padded copy of the first weight, as in the per-layer path."""
-        L = len(acts)
+        per-layer GEMMs by default (which spread a layer over the whole chip), or (TOWER_FWD) one tower launch — activations of 16 batch
+        rows stay in LDS from layer to layer."""
+        L = len(plan.layers)
         M = x.size(0)
-        W0 = params[0]
-        K0 = W0.size(1)
-        W0p = ops.pad_cols(W0, x.size(1)) if x.size(1) != K0 else None
-        outs = [(out_slot.get() if (i == L - 1 and out_slot is not None) else alloc2d(M, params[2 * i].size(0), x)) for i in range(L)]
-        if TOWER_FWD:
-            Ws = [W0p if (i == 0 and W0p is not None) else params[2 * i] for i in range(L)]
-            ops.tower_fwd(x, Ws, [params[2 * i + 1] for i in range(L)], acts, outs)
+        outs = [(out_last if (i == L - 1 and out_last is not None) else alloc2d(M, lp.N, x)) for i, lp in enumerate(plan.layers)]
+        if plan.tower_fwd:
+            ops.tower_fwd(x, Ws, [params[2 * i + 1] for i in range(L)], plan.acts, outs)
         else:
-            # default: the forward pass on the per-layer GEMMs (which spread a layer over the whole chip), the backward pass on the tower
-            # kernels (which only need every layer's fp32 output); unaligned inputs are padded as the per-layer path does
-            if x.size(1) % 4 != 0:
-                Kp = _round4(x.size(1))
-                x, W0p = ops.pad_cols(x, Kp), ops.pad_cols(W0, Kp)
             cur = x
             for i in range(L):
-                ops.linear_fwd(cur, W0p if (i == 0 and W0p is not None) else params[2 * i], params[2 * i + 1], acts[i], outs[i],
-                               ops.arith_code("f32"), relu_bits=None)
+                ops.linear_fwd(cur, Ws[i], params[2 * i + 1], plan.acts[i], outs[i], ops.arith_code("f32"), relu_bits=None)
                 cur = outs[i]
-        ctx.tower, ctx.acts, ctx.padded = True, acts, W0p is not None
-        ctx.save_for_backward(x, *params, *outs, *([W0p] if W0p is not None else []))
-        return outs[-1]
+        return outs
 
     @staticmethod
     def _tower_backward(ctx, dY):
-        acts = ctx.acts
-        L = len(acts)
-        saved = ctx.saved_tensors
-        x, params, outs = saved[0], saved[1:1 + 2 * L], list(saved[1 + 2 * L:1 + 3 * L])
-        W0p = saved[1 + 3 * L] if ctx.padded else None
+        plan = ctx.plan
+        L = len(plan.layers)
+        x, params, outs, Ws = MLPFunction._saved(ctx)
         M = x.size(0)
         dY = _rowmajor(dY)
-        Ws = [W0p if (i == 0 and W0p is not None) else params[2 * i] for i in range(L)]
-        dZs = [alloc2d(M, params[2 * i].size(0), x) for i in range(L)]
-        dX = alloc2d(M, x.size(1), x) if ctx.needs_input_grad[0] else None
-        ops.tower_bwd(dY, Ws, acts, outs, dZs, dX, last_act_applied=ctx.consumer_applies_last_act)
+        dZs = [alloc2d(M, lp.N, x) for lp in plan.layers]
+        dX = alloc2d(M, x.size(1), x) if plan.need_dx else None
+        ops.tower_bwd(dY, Ws, plan.acts, outs, dZs, dX, last_act_applied=plan.consumer_act)
         dWs = [_grad_out(params[2 * i]) for i in range(L)]              # (the first layer's at the parameter's true width)
         dbs = [_grad_out(params[2 * i + 1]) for i in range(L)]
         ops.tower_wgrad(dZs, [x] + outs[:-1], dWs, dbs)
         grads = []
         for i in range(L):
             grads += [dWs[i], dbs[i]]
-        if dX is not None and dX.size(1) != ctx.in_width:
-            dX = dX[:, :ctx.in_width]
+        if dX is not None and dX.size(1) != plan.in_width:
+            dX = dX[:, :plan.in_width]
         return (dX, None, None, None, *grads)
 
     @staticmethod
     def backward(ctx, dY):
-        if ctx.tower:
+        plan = ctx.plan
+        if plan.whole_tower:
             return MLPFunction._tower_backward(ctx, dY)
-        acts, arith = ctx.acts, ctx.arith
-        L = len(acts)
-        saved = ctx.saved_tensors
-        x = saved[0]
-        params = saved[1:1 + 2 * L]
-        n32 = sum(ctx.have32)
-        it32 = iter(saved[1 + 2 * L:1 + 2 * L + n32])
-        outs = [next(it32) if h else None for h in ctx.have32]          # fp32 activations (None: the layer kept bf16 + sign bits only)
-        W0p = saved[1 + 2 * L + n32] if ctx.padded else None
+        st, acts, arith, layers = plan.store, plan.acts, plan.arith, plan.layers
+        L = len(layers)
+        x, params, outs, Ws = MLPFunction._saved(ctx)
         M = x.size(0)
         dY = _rowmajor(dY)
         grads: List[Optional[torch.Tensor]] = [None] * (2 * L)
-        store16 = ctx.plan is not None
-        st = ctx.st
-        use16, wg16, dg16, need32, kb = ctx.plan if store16 else ([False] * L,) * 4 + ([0] * L,)
+        overlap = _wgrad_overlaps(M)
 
         # last layer: activation backward (its dY comes from outside, e.g. the loss or the interaction)
-        N_last = params[2 * (L - 1)].size(0)
         first = L - 1                                      # the layer the loop below starts with
         dZ = None
-        if (HEAD_FUSED and N_last == 1 and L >= 2 and not store16 and not ctx.consumer_applies_last_act and arith == ops.arith_code("f32")
-                and outs[L - 1] is not None and outs[L - 2] is not None and not OVERLAP_WGRAD
-                and not (0 < SMALL_BATCH_OVERLAP and M <= SMALL_BATCH_OVERLAP and torch.cuda.is_current_stream_capturing())):
+        if plan.head_fused and not overlap:
             # the 256 -> 1 head of the top tower: act_bwd + weight gradient + data gradient of an N == 1 layer are ONE pass over its input
             # (dlrm_linear_head_bwd: X read once instead of twice, one launch + the finish instead of four: 48 -> ~29 us at B = 65536; the
             # bits of the three calls).  Outside its fast path nothing is launched and the three calls below run.
             dW_h, db_h = _grad_out(params[2 * (L - 1)]), _grad_out(params[2 * (L - 1) + 1])
-            dprev = alloc2d(M, params[2 * (L - 1)].size(1), x)
-            if ops.linear_head_bwd(dY, outs[L - 1], acts[L - 1], outs[L - 2], params[2 * (L - 1)], acts[L - 2], dprev, dW_h, db_h):
+            dprev = alloc2d(M, layers[L - 1].K, x)
+            if ops.linear_head_bwd(dY, outs[L - 1], acts[L - 1], outs[L - 2], Ws[L - 1], acts[L - 2], dprev, dW_h, db_h):
                 grads[2 * (L - 1)], grads[2 * (L - 1) + 1] = dW_h, db_h
                 dZ, first = dprev, L - 2
         if dZ is not None:
             pass
-        elif ctx.consumer_applies_last_act and _ld(dY) % 4 == 0 and dY.data_ptr() % 16 == 0:
+        elif plan.consumer_act and _ld(dY) % 4 == 0 and dY.data_ptr() % 16 == 0:
             dZ = dY                                        # already dL/dz of the last layer (see forward)
         else:
-            dZ = alloc2d(M, N_last, x)
-            if ctx.consumer_applies_last_act:
+            dZ = alloc2d(M, layers[L - 1].N, x)
+            if plan.consumer_act:
                 dZ.copy_(dY)                               # (an unaligned gradient view: the GEMMs want 16-byte rows)
             else:
                 ops.act_bwd(dY, outs[L - 1], acts[L - 1], dZ, None)
@@ -437,35 +511,29 @@ class MLPFunction(Function):
         # are independent: wgrad goes to a side HIP stream so the two kernels share the chip (their epilogue
         # store bursts and tail rounds interleave with the other's MFMA phases instead of idling the matrix cores).
         main = torch.cuda.current_stream()
-        # (small batches — Criteo-Kaggle's 2048 rows — are the opposite regime: every GEMM of the step occupies a fraction of the chip, so the
-        # independent weight-gradient launch runs BESIDE the data-gradient launch for free; the fork / join are events a graph capture records)
-        # — measured at Criteo-Kaggle shapes: graphed step 0.515 -> 0.497 ms; in the EAGER step the two extra event records per layer cost the
-        # host more than the overlap saves (1.51 -> 1.74 ms), so only a capturing stream forks
-        side = _side_stream(x.device) if (OVERLAP_WGRAD or (0 < SMALL_BATCH_OVERLAP and M <= SMALL_BATCH_OVERLAP
-                                                          and torch.cuda.is_current_stream_capturing())) else None
+        side = _side_stream(x.device) if overlap else None
         keep = []                                          # tensors the side stream reads stay alive until the join
-        dZ16 = None                                        # bf16 copy of dZ when the previous data-gradient GEMM produced one
+        dZ16 = None                                        # reduced-width copy of dZ when the previous data-gradient GEMM produced one
         for i in range(first, -1, -1):
-            W = params[2 * i] if not (i == 0 and W0p is not None) else W0p
+            lp, W = layers[i], Ws[i]
             X_i = x if i == 0 else outs[i - 1]
-            X16_i = ctx.in16[i] if wg16[i] else None
+            X16_i = ctx.in16[i]
             # first layer on a zero-padded input: the gradient is written at the parameter's true width (the padding
             # columns of X are dropped inside the kernel) — contiguous, no slicing / re-packing afterwards
             dW = _grad_out(params[2 * i])
             db = _grad_out(params[2 * i + 1])
-            N_i, K_i = W.size(0), W.size(1)
-            do16 = wg16[i] and X16_i is not None
-            if do16 and not st.wgrad_ok(M, N_i, dW.size(1), dZ16 if dZ16 is not None else X16_i, X16_i):
+            # the one check of the plan that needs the real gradient slot (it may be a view into a flat all-reduce buffer)
+            if lp.wgrad16 and not st.wgrad_ok(M, lp.N, dW.size(1), dZ16 if dZ16 is not None else X16_i, X16_i):
                 # forward already dropped the fp32 operands on the strength of this plan: a run-time disagreement (DLRM_BF16_PHASED changed
                 # between forward and backward, an unaligned gradient slot) must not fall into the fp32 branch with operands that no longer exist
                 raise RuntimeError("dlrm_amd: the bf16 weight gradient planned at forward time for layer %d (M=%d, N=%d, K=%d) is refused at "
                                    "backward time (environment switched between forward and backward, or unaligned gradient storage)"
-                                   % (i, M, N_i, dW.size(1)))
-            if do16 and dZ16 is None:
-                dZ16 = st.cast(dZ, N_i, category="linear_bwd_weight")                # (the tower's last layer: its dZ comes from act_bwd in fp32)
+                                   % (i, M, lp.N, dW.size(1)))
+            if lp.wgrad16 and dZ16 is None:
+                dZ16 = st.cast(dZ, lp.N, category="linear_bwd_weight")               # (the tower's last layer: its dZ comes from act_bwd in fp32)
 
             def wgrad():
-                if do16:
+                if lp.wgrad16:
                     st.wgrad(dZ16, X16_i, dW, db)                                 # bf16 operands (or planes) as stored, k-strided reads
                 else:
                     ops.linear_bwd_weight(dZ, X_i, dW, db, arith=arith)           # dW and db (row sums of dZ^T) in one GEMM
@@ -477,38 +545,29 @@ class MLPFunction(Function):
             else:
                 wgrad()
             grads[2 * i], grads[2 * i + 1] = dW, db
-            need_dx = i > 0 or ctx.needs_input_grad[0]
-            if not need_dx:
+            if not lp.need_dx:
                 continue
-            mask_act = acts[i - 1] if i > 0 else ACT_NONE
             rbits = ctx.bits[i - 1] if i > 0 else None
-            # what the layer below reads of this gradient: its bf16 weight / data gradient take the bf16 copy; fp32 is written only when
-            # something reads it (the tower's input gradient, an fp32-storage weight / data gradient below)
-            want16 = i > 0 and store16 and (wg16[i - 1] or (dg16[i - 1] and (i - 1 > 0 or ctx.needs_input_grad[0]))) and K_i % 32 == 0
-            want32 = i == 0 or not store16 or not (wg16[i - 1] and (dg16[i - 1] or not (i - 1 > 0 or ctx.needs_input_grad[0]))) or not want16
-            ok16 = (store16 and dg16[i] and (mask_act == ACT_NONE or (mask_act == ACT_RELU and rbits is not None)))
-            dprev = alloc2d(M, K_i, x) if (want32 or not ok16) else None
-            if ok16 and dprev is not None and _ld(dprev) % 4 != 0:
-                ok16 = False
-            if ok16:
-                # bf16 storage: dX = dZ . W as a <k-contiguous, k-contiguous> GEMM over a transposed bf16 copy of W
-                a16 = dZ16 if dZ16 is not None else st.cast(dZ, N_i, category="linear_bwd_data")
-                wT16 = ctx.preT16[i] if ctx.preT16[i] is not None else st.cast_t(W, N_i, category="linear_bwd_data")
-                d16 = st.empty(M, K_i, x.device) if want16 else None
+            dprev = alloc2d(M, lp.K, x) if lp.dx32 else None
+            if lp.dgrad16:
+                # reduced-width storage: dX = dZ . W as a <k-contiguous, k-contiguous> GEMM over a transposed reduced-width copy of W
+                a16 = dZ16 if dZ16 is not None else st.cast(dZ, lp.N, category="linear_bwd_data")
+                wT16 = ctx.preT16[i] if ctx.preT16[i] is not None else st.cast_t(W, lp.N, category="linear_bwd_data")
+                d16 = st.empty(M, lp.K, x.device) if lp.dx16 else None
                 st.gemm(a16, wT16, None, ACT_NONE, dprev, d16, relu_bits_in=rbits, category="linear_bwd_data")
                 dZ16 = d16
             else:
                 # dgrad GEMM with the previous layer's activation derivative fused into the epilogue
                 if dZ is None:
                     raise RuntimeError("dlrm_amd: internal: fp32 gradient missing for an fp32-storage data gradient")
-                ops.linear_bwd_data(dZ, W, X_i if i > 0 else None, mask_act, dprev, arith, relu_bits=rbits)
+                ops.linear_bwd_data(dZ, W, X_i if i > 0 else None, lp.mask_act, dprev, arith, relu_bits=rbits)
                 dZ16 = None
             if i > 0:
                 dZ = dprev
             else:
                 dX = dprev
-                if dX.size(1) != ctx.in_width:
-                    dX = dX[:, :ctx.in_width]
+                if dX.size(1) != plan.in_width:
+                    dX = dX[:, :plan.in_width]
         if side is not None:
             main.wait_stream(side)
             del keep
@@ -903,8 +962,8 @@ class LowRankCrossNetFunction(Function):
         kernels write beside (or instead of) their fp32 results, v and dv as bf16-only GEMM outputs; weight gradients from the stored
         operands (dlrm_linear_bwd_weight_bf16); the gradient sum g + dv.V inside the GEMM epilogue (addend).  Needs the shapes of the
         bf16-shaped kernels."""
-        return (BF16_STORAGE and BF16_LEAN and arith == ops.arith_code("bf16") and M >= 256 and M % 64 == 0 and n_in % 64 == 0 and r % 64 == 0
-                and n_in >= 192 and r >= 192 and ops.BF16_PHASED)
+        return (BF16_STORAGE and BF16_LEAN and arith == ops.arith_code("bf16") and n_in % 64 == 0 and r % 64 == 0 and n_in >= 192 and r >= 192
+                and ops.linear_bwd_weight_bf16_shapes_ok(M, r, n_in) and ops.linear_bwd_weight_bf16_shapes_ok(M, n_in, r))   # dV [r, in], dW [in, r]
 
     @staticmethod
     def forward(ctx, arith, x0, *params):

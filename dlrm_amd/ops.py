@@ -1865,11 +1865,18 @@ def linear_head_bwd(dY: torch.Tensor, Y: Optional[torch.Tensor], act: int, X: to
     return True
 
 
+def linear_bwd_weight_bf16_shapes_ok(M: int, N: int, K: int) -> bool:
+    """the shapes dlrm_linear_bwd_weight_bf16 takes (csrc/gemm_bf16.hip, weight-gradient form): dW [N, K] from M rows.  The one statement of
+    them: the tensor-level check below, MLPFunction's plan and LowRankCrossNetFunction all ask here."""
+    return M >= 256 and M % 64 == 0 and N % 8 == 0 and N >= 64 and K >= 64 and BF16_PHASED
+
+
 def linear_bwd_weight_bf16_ok(M: int, N: int, K: int, dZ16: torch.Tensor, X16: torch.Tensor) -> bool:
-    """preconditions of dlrm_linear_bwd_weight_bf16 (csrc/gemm_bf16.hip, weight-gradient form)"""
+    """preconditions of dlrm_linear_bwd_weight_bf16: its shapes (K, the stored width of dW, rounded up to the product's 8), and operands
+    that are wide enough, 16-byte aligned and of a pitch that keeps every row so"""
     K = (K + 7) & ~7
-    return (M >= 256 and M % 64 == 0 and N % 8 == 0 and N >= 64 and K >= 64 and X16.size(1) >= K and dZ16.stride(0) % 8 == 0 and X16.stride(0) % 8 == 0
-            and dZ16.data_ptr() % 16 == 0 and X16.data_ptr() % 16 == 0 and BF16_PHASED)
+    return (linear_bwd_weight_bf16_shapes_ok(M, N, K) and X16.size(1) >= K and dZ16.stride(0) % 8 == 0 and X16.stride(0) % 8 == 0
+            and dZ16.data_ptr() % 16 == 0 and X16.data_ptr() % 16 == 0)
 
 
 def linear_bwd_weight_bf16(dZ16: torch.Tensor, X16: torch.Tensor, dW: torch.Tensor, dbias: Optional[torch.Tensor] = None,

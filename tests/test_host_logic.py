@@ -474,22 +474,52 @@ def test_product_library_has_no_work_skipping_switches():
     assert "DLRM_TUNING" in mk and "TUNING" in mk
 
 
-@pytest.mark.parametrize("ln,B,arith", [([13, 512, 256, 128], 4096, "bf16x6"), ([479, 1024, 1024, 512, 256, 1], 4096, "bf16x6"),
-                                        ([480, 1024, 512, 256], 2048, "bf16x6"), ([96, 64, 32], 512, "bf16x6"), ([256, 320, 192, 64], 1000, "bf16x6"),
-                                        ([13, 512, 256, 128], 4096, "bf16"), ([479, 1024, 1024, 512, 256, 1], 4096, "bf16")])
-def test_mlp_storage_plan_hands_every_consumer_what_it_reads(monkeypatch, ln, B, arith):
-    """MLPFunction's storage plan (functional.py: which layer keeps fp32, which keeps only the reduced-width copy — bf16, or the three planes
-    of arith "bf16x6" — and which kernel form every forward / data-gradient / weight-gradient product takes) with the device operators
-    replaced by plain torch on the CPU: every operator asserts that the operands it is handed exist in the form it reads, and the tower's
-    output and all gradients must equal torch autograd's.  The kernels themselves are tested on the GPU; this is the HOST logic around
-    them — the towers of the Terabyte model (13 -> 16 padded first layer, a 128-wide and a 1-wide layer between reduced-width layers), a
-    tower the planes kernel refuses entirely, and a batch that is not a multiple of 64 (fp32 weight gradients beside planes)."""
-    from dlrm_amd import functional, ops
-    from dlrm_amd.functional import MLPFunction
-    masks = {}
+class _MLPTrace:
+    """Recorder around the stand-ins of _mlp_standins: one line per call — the operator's name, every tensor argument as dtype, shape
+    and an identity number (the order of the buffer's first appearance, so a wrong buffer shows up), every scalar argument, and what the
+    call returned.  Every tensor seen stays alive until the trace is dropped: no address is handed out twice within a case."""
 
-    def act(v, a):
-        return torch.relu(v) if a == ops.ACT_RELU else torch.sigmoid(v) if a == ops.ACT_SIGMOID else v
+    def __init__(self):
+        self.lines, self.calls, self._ids, self._keep = [], 0, {}, []
+
+    def desc(self, v):
+        if isinstance(v, torch.Tensor):
+            key = (v.untyped_storage().data_ptr(), v.storage_offset(), tuple(v.shape), tuple(v.stride()), v.dtype)
+            if key not in self._ids:
+                self._ids[key] = len(self._ids)
+                self._keep.append(v)
+            return "%s[%s]#%d" % (str(v.dtype).replace("torch.", ""), "x".join(map(str, v.shape)), self._ids[key])
+        if isinstance(v, (list, tuple)):
+            return "(" + ", ".join(self.desc(e) for e in v) + ")"
+        return str(v)
+
+    def wrap(self, name, fn):
+        def logged(*args, **kwargs):
+            head = "%s(%s)" % (name, ", ".join([self.desc(a) for a in args] + ["%s=%s" % (k, self.desc(kwargs[k])) for k in sorted(kwargs)]))
+            out = fn(*args, **kwargs)
+            self.lines.append(head if out is None else head + " -> " + self.desc(out))
+            self.calls += 1
+            return out
+        return logged
+
+    def note(self, text):
+        self.lines.append(text)
+
+    def text(self):
+        return "\n".join(self.lines) + "\n"
+
+
+def _mlp_act(v, a):
+    from dlrm_amd import ops
+    return torch.relu(v) if a == ops.ACT_RELU else torch.sigmoid(v) if a == ops.ACT_SIGMOID else v
+
+
+def _mlp_standins(monkeypatch, rec=None):
+    """Every device operator MLPFunction calls, replaced by plain torch on the CPU; each asserts that the operands it is handed exist in
+    the form it reads.  With `rec` (an _MLPTrace) every call — the allocations included — is also logged."""
+    from dlrm_amd import functional, ops
+    masks = {}
+    act = _mlp_act
 
     def linear_fwd(X, W, b, a, Y, arith_, relu_bits=None):
         assert Y is not None and X is not None and X.dtype == torch.float32
@@ -557,8 +587,15 @@ def test_mlp_storage_plan_hands_every_consumer_what_it_reads(monkeypatch, ln, B,
         t = torch.zeros((src.size(0), Kp)); t[:, :src.size(1)] = src
         return t
 
+    def linear_head_bwd(dY, Y, a, X, W, xact_kind, dX, dW, db, accumulate=False):      # the N == 1 head in one pass: always takes it
+        dz = torch.empty_like(dY)
+        act_bwd(dY, Y, a, dz, None)
+        linear_bwd_weight(dz, X, dW, db)
+        linear_bwd_data(dz, W, X, xact_kind, dX, None)
+        return True
+
     for name, fn in (("linear_fwd", linear_fwd), ("act_bwd", act_bwd), ("linear_bwd_weight", linear_bwd_weight), ("linear_bwd_data", linear_bwd_data),
-                     ("pad_cols", pad_cols)):
+                     ("linear_head_bwd", linear_head_bwd), ("pad_cols", pad_cols)):
         monkeypatch.setattr(ops, name, fn)
     def cast_multi_like(items, category=None):           # (round 5: all weight copies of a bf16 tower in one launch)
         return [(cast_like(False)(s_, cp) if cp else None, cast_t_like(False)(s_, rp) if rp else None) for s_, cp, rp in items]
@@ -570,7 +607,20 @@ def test_mlp_storage_plan_hands_every_consumer_what_it_reads(monkeypatch, ln, B,
         monkeypatch.setattr(store, "wgrad", staticmethod(wgrad_like))
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: None)
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    if rec is not None:
+        for owner, names in ((ops, ("linear_fwd", "act_bwd", "linear_bwd_weight", "linear_bwd_data", "linear_head_bwd", "pad_cols", "relu_bits_alloc")),
+                             (functional, ("alloc2d",)),
+                             (functional._Bf16Store, ("cast", "cast_t", "cast_multi", "gemm", "wgrad", "empty")),
+                             (functional._PlaneStore, ("cast", "cast_t", "gemm", "wgrad", "empty"))):
+            for n in names:
+                label = n if owner in (ops, functional) else "%s.%s" % (owner.__name__, n)
+                fn = rec.wrap(label, getattr(owner, n))
+                monkeypatch.setattr(owner, n, fn if owner in (ops, functional) else staticmethod(fn))
 
+
+def _mlp_tower(ln, B, requires_grad=True):
+    """seeded parameters, activations, input and incoming gradient of the tower ln[0] -> ... -> ln[-1] at B rows"""
+    from dlrm_amd import ops
     rng = np.random.default_rng(0)
     L = len(ln) - 1
     params = []
@@ -578,8 +628,27 @@ def test_mlp_storage_plan_hands_every_consumer_what_it_reads(monkeypatch, ln, B,
         params += [torch.tensor((rng.standard_normal((ln[i + 1], ln[i])) * np.sqrt(2 / (ln[i] + ln[i + 1]))).astype(np.float32), requires_grad=True),
                    torch.tensor((rng.standard_normal(ln[i + 1]) * 0.1).astype(np.float32), requires_grad=True)]
     acts = tuple([ops.ACT_RELU] * (L - 1) + [ops.ACT_SIGMOID if ln[-1] == 1 else ops.ACT_RELU])
-    x = torch.tensor(rng.random((B, ln[0])).astype(np.float32), requires_grad=True)
+    x = torch.tensor(rng.random((B, ln[0])).astype(np.float32), requires_grad=requires_grad)
     dy = torch.tensor(rng.standard_normal((B, ln[-1])).astype(np.float32))
+    return params, acts, x, dy
+
+
+@pytest.mark.parametrize("ln,B,arith", [([13, 512, 256, 128], 4096, "bf16x6"), ([479, 1024, 1024, 512, 256, 1], 4096, "bf16x6"),
+                                        ([480, 1024, 512, 256], 2048, "bf16x6"), ([96, 64, 32], 512, "bf16x6"), ([256, 320, 192, 64], 1000, "bf16x6"),
+                                        ([13, 512, 256, 128], 4096, "bf16"), ([479, 1024, 1024, 512, 256, 1], 4096, "bf16")])
+def test_mlp_storage_plan_hands_every_consumer_what_it_reads(monkeypatch, ln, B, arith):
+    """MLPFunction's storage plan (functional.py: which layer keeps fp32, which keeps only the reduced-width copy — bf16, or the three planes
+    of arith "bf16x6" — and which kernel form every forward / data-gradient / weight-gradient product takes) with the device operators
+    replaced by plain torch on the CPU: every operator asserts that the operands it is handed exist in the form it reads, and the tower's
+    output and all gradients must equal torch autograd's.  The kernels themselves are tested on the GPU; this is the HOST logic around
+    them — the towers of the Terabyte model (13 -> 16 padded first layer, a 128-wide and a 1-wide layer between reduced-width layers), a
+    tower the planes kernel refuses entirely, and a batch that is not a multiple of 64 (fp32 weight gradients beside planes)."""
+    from dlrm_amd import ops
+    from dlrm_amd.functional import MLPFunction
+    _mlp_standins(monkeypatch)
+    act = _mlp_act
+    L = len(ln) - 1
+    params, acts, x, dy = _mlp_tower(ln, B)
     y = MLPFunction.apply(x, acts, None, ops.arith_code(arith), *params)
     y.backward(dy)
     got = [y.detach(), x.grad] + [p.grad for p in params]
@@ -592,6 +661,202 @@ def test_mlp_storage_plan_hands_every_consumer_what_it_reads(monkeypatch, ln, B,
     ref = [h.detach(), xr.grad] + [p.grad for p in ps]
     for k, (a, b) in enumerate(zip(got, ref)):
         np.testing.assert_allclose(a.numpy(), b.numpy(), rtol=2e-3, atol=2e-3 * float(b.abs().max()), err_msg=str((ln, k)))
+
+
+# ---- MLPFunction's call trace, case by case, against tests/fixtures/mlp_tower_trace.json -----------------------------------------------
+# The fixture holds the SHA-256 and the call count of every case's trace AS RECORDED FROM THE COMMIT BEFORE the tower plan (_plan_tower)
+# was introduced: `python tests/test_host_logic.py --record FILE` in a checkout of that commit with this file copied in.  It is never
+# regenerated from newer code: a refactor of MLPFunction must reproduce it.
+_TRACE_FIXTURE = os.path.join(ROOT, "tests", "fixtures", "mlp_tower_trace.json")
+_TB_TOWERS = ([13, 512, 256, 128], [479, 1024, 1024, 512, 256, 1])
+_TRACE_TOWERS = _TB_TOWERS + ([480, 1024, 512, 256], [96, 64, 32], [256, 320, 192, 64], [256, 200, 72, 64], [58, 128, 64], [256, 256])
+_TRACE_SWITCHES = ("BF16_STORAGE", "BF16_LEAN", "MULTI_CAST", "RELU_BITS", "BF16X6_PLANES", "BF16_PHASED", "SMALL_BATCH_BITS")
+_TRACE_ROWS = tuple(s + "=0" for s in _TRACE_SWITCHES) + ("x_without_grad", "no_grad", "out_slot_aligned", "out_slot_one_float_in",
+                                                           "consumer_act_aligned", "consumer_act_unaligned", "head_accepts", "head_declines")
+
+
+def _trace_cases():
+    """default switches: towers x batches (256: the least the bf16 forms take; 300: no multiple of 64; 128: below 256) x arithmetic; then
+    one thing changed at a time on the two Terabyte towers at 256 rows"""
+    cases = [(ln, B, arith, None) for ln in _TRACE_TOWERS for B in (256, 300, 128) for arith in ("f32", "bf16", "bf16x6")]
+    cases += [(ln, 256, arith, row) for ln in _TB_TOWERS for arith in ("f32", "bf16", "bf16x6") for row in _TRACE_ROWS]
+    return cases
+
+
+def _trace_id(case):
+    ln, B, arith, row = case
+    return "%s|%d|%s|%s" % ("-".join(map(str, ln)), B, arith, row or "default")
+
+
+def _record_mlp_trace(monkeypatch, ln, B, arith, row):
+    from dlrm_amd import functional, ops
+    from dlrm_amd.functional import MLPFunction, OutSlot
+    rec = _MLPTrace()
+    _mlp_standins(monkeypatch, rec)
+    if row is not None and row.endswith("=0"):
+        name = row[:-2]
+        if name == "SMALL_BATCH_BITS":
+            monkeypatch.setattr(functional, name, 0)
+        else:
+            monkeypatch.setattr(ops if name == "BF16_PHASED" else functional, name, False)
+    if row == "head_declines":
+        monkeypatch.setattr(ops, "linear_head_bwd", rec.wrap("linear_head_bwd", lambda *a, **k: False))
+    bwd = MLPFunction.backward
+
+    def backward(ctx, dY):
+        out = bwd(ctx, dY)
+        rec.note("backward returns " + ", ".join("None" if g is None else "%s%s" % (rec.desc(g), tuple(g.stride())) for g in out))
+        return out
+    monkeypatch.setattr(MLPFunction, "backward", staticmethod(backward))
+
+    params, acts, x, dy = _mlp_tower(ln, B, requires_grad=row != "x_without_grad")
+    N = ln[-1]
+    code = ops.arith_code(arith)
+    slot = None
+    if row in ("out_slot_aligned", "out_slot_one_float_in"):
+        c0 = 0 if row == "out_slot_aligned" else 1
+        slot = OutSlot(torch.zeros((B, 2 * functional._round4(N) + 4))[:, c0:c0 + N])
+    if row in ("consumer_act_aligned", "consumer_act_unaligned"):
+        code |= functional.MLP_CONSUMER_APPLIES_LAST_ACT
+        c0 = 0 if row == "consumer_act_aligned" else 1
+        wide = torch.zeros((B, 2 * functional._round4(N) + 4))
+        wide[:, c0:c0 + N] = dy
+        dy = wide[:, c0:c0 + N]
+    for t in [x, dy] + params:
+        rec.desc(t)                                                     # identity numbers of the inputs, in a fixed order
+    try:
+        if row == "no_grad":
+            with torch.no_grad():
+                y = MLPFunction.apply(x, acts, slot, code, *params)
+        else:
+            y = MLPFunction.apply(x, acts, slot, code, *params)
+        saved = y.grad_fn.saved_tensors if y.grad_fn is not None else None
+        rec.note("forward returns %s%s, saved %s" % (rec.desc(y), tuple(y.stride()), "nothing" if saved is None else rec.desc(saved)))
+        if y.grad_fn is not None:
+            y.backward(dy)
+    except RuntimeError as e:
+        rec.note("RuntimeError: %s" % e)
+    return rec
+
+
+@pytest.mark.parametrize("case", _trace_cases(), ids=_trace_id)
+def test_mlp_call_trace_equals_the_recorded_one(monkeypatch, tmp_path, case):
+    """Every operator call and allocation MLPFunction makes, forward and backward — names, shapes, dtypes, which buffer goes where, every
+    scalar — equals, case by case, the trace recorded before the storage plan moved into _plan_tower (see _TRACE_FIXTURE above)."""
+    want = json.load(open(_TRACE_FIXTURE))[_trace_id(case)]
+    rec = _record_mlp_trace(monkeypatch, *case)
+    import hashlib
+    got = {"sha256": hashlib.sha256(rec.text().encode()).hexdigest(), "calls": rec.calls}
+    if got != want:
+        f = tmp_path / "trace.txt"
+        f.write_text(rec.text())
+        assert got == want, "the call trace of %s changed; the new one is in %s" % (_trace_id(case), f)
+
+
+def test_tower_plan_hands_every_consumer_what_it_reads(monkeypatch):
+    """functional._plan_tower with no tensor anywhere: at the workloads' real batches, on and off the GPU, every product of the plan finds
+    its operands in the form it reads; the bf16 Terabyte towers keep fp32 after exactly the layers they kept before the plan was one
+    object (read off the recorded traces at 256 rows: the bf16 plan depends on M only through M >= 256 and M % 64 == 0); and the
+    whole-tower path is taken only on the GPU and within TOWER_ROWS / TOWER_L2_BYTES."""
+    from dlrm_amd import functional, ops
+    from dlrm_amd.functional import _plan_tower
+    RELU, NONE = ops.ACT_RELU, ops.ACT_NONE
+    monkeypatch.setattr(functional, "TOWER_ROWS", 4096)
+    monkeypatch.setattr(functional, "TOWER_L2_BYTES", 384 << 20)
+
+    def plan(ln, M, arith, gpu=True, need_grad=True, need_dx=True, in_width=None, **kw):
+        L = len(ln) - 1
+        acts = tuple([RELU] * (L - 1) + [ops.ACT_SIGMOID if ln[-1] == 1 else RELU])
+        return _plan_tower(M, in_width or ln[0], [(ln[i + 1], ln[i]) for i in range(L)], acts, ops.arith_code(arith), need_grad,
+                           need_grad and need_dx, gpu, **kw)
+
+    def check(p, M, why):
+        ls = p.layers
+        L = len(ls)
+        assert ls[-1].out32, why
+        assert p.store is not None or not any(lp.fwd16 or lp.wgrad16 or lp.dgrad16 or lp.out16 or lp.dx16 for lp in ls), why
+        for i, lp in enumerate(ls):
+            below, above = (ls[i - 1] if i > 0 else None), (ls[i + 1] if i + 1 < L else None)
+            in32 = below is None or below.out32                     # the layer's input exists as fp32 (the tower's input always does)
+            dz32 = above is None or above.dx32                      # its incoming gradient exists as fp32 (the last layer's comes from act_bwd)
+            dz_any = dz32 or above.dx16
+            assert lp.out32 or lp.out16, (why, i)
+            # forward: a reduced-width GEMM reads the reduced-width output below, or casts the fp32 one; an fp32 GEMM needs fp32
+            assert (in32 or below.out16) if lp.fwd16 else in32, (why, i)
+            assert not lp.out16 or (lp.fwd16 and above.fwd16 and above.kb == lp.N), (why, i)
+            assert lp.bits == (above is not None and lp.act == RELU and p.need_bits), (why, i)
+            if p.store is functional._PlaneStore:
+                assert not lp.fwd16 or ops.gemm_bf16x6_ok(M, lp.N, lp.kb), (why, i)
+                assert not lp.dgrad16 or ops.gemm_bf16x6_ok(M, lp.K, lp.N), (why, i)
+            # weight gradient: reduced width from the kept reduced-width input and a gradient in either form; fp32 from fp32 operands
+            assert (lp.fwd16 and dz_any and ops.linear_bwd_weight_bf16_shapes_ok(M, lp.N, lp.K)) if lp.wgrad16 else (in32 and dz32), (why, i)
+            if not lp.need_dx:
+                assert i == 0 and not p.need_dx, (why, i)
+                continue
+            assert lp.dx32 or lp.dx16, (why, i)
+            assert lp.mask_act == (below.act if below is not None else NONE) and (not lp.mask_bits or below.bits), (why, i)
+            if lp.dgrad16:
+                assert dz_any and (lp.mask_act == NONE or (lp.mask_act == RELU and lp.mask_bits)), (why, i)
+            else:
+                assert dz32 and not lp.dx16 and lp.dx32, (why, i)
+                assert lp.mask_act == NONE or in32, (why, i)           # ops.linear_bwd_data masks with the fp32 activation, bits or not
+            if lp.mask_act not in (NONE, RELU):
+                assert in32, (why, i)
+
+    kag_bot, kag_top = [13, 512, 256, 64, 16], [367, 512, 256, 1]
+    # (+ two towers in which a layer takes the reduced-width weight gradient but not the reduced-width data gradient — 200 and 72 are
+    # multiples of 8, not of 32 — below a layer whose output the next GEMM reads as it is: the fp32 copy is kept for the mask alone)
+    for ln in list(_TRACE_TOWERS) + [kag_bot, kag_top, [256, 256, 200, 64], [256, 128, 72, 64]]:
+        for M in (65536, 2048):
+            for arith in ("f32", "bf16", "bf16x6"):
+                for gpu in (True, False):
+                    for need_dx in (True, False):
+                        for switch in (None, "BF16_LEAN", "RELU_BITS", "BF16_STORAGE", "BF16X6_PLANES"):
+                            with monkeypatch.context() as mp:
+                                if switch:
+                                    mp.setattr(functional, switch, False)
+                                p = plan(ln, M, arith, gpu=gpu, need_dx=need_dx)
+                                assert not p.whole_tower or (gpu and arith == "f32" and M <= 4096), (ln, M, arith, gpu)
+                                if not p.whole_tower:
+                                    check(p, M, (ln, M, arith, gpu, need_dx, switch))
+        p = plan(ln, 65536, "bf16", need_grad=False)                 # a forward that will not be differentiated plans no backward form
+        assert not p.need_bits and not any(lp.bits or lp.wgrad16 or lp.wT16_multi for lp in p.layers)
+
+    # the Terabyte towers, arith "bf16": fp32 is kept after the tower's output only (bottom), and after the 256-wide input of the
+    # matrix-vector head and the head itself (top); every other activation is bf16 + sign bits
+    for M in (65536, 2048):
+        assert [lp.out32 for lp in plan(_TB_TOWERS[0], M, "bf16").layers] == [False, False, True]
+        assert [lp.out32 for lp in plan(_TB_TOWERS[1], M, "bf16").layers] == [False, False, False, True, True]
+        assert [lp.out32 for lp in plan(_TB_TOWERS[1], M, "bf16", in_width=480).layers] == [False, False, False, True, True]
+    # first-layer width 58 -> 60: the plan asks for the padded width >= 64 and refuses, where the tensor-level check alone would round 58 up to 64
+    p = plan([58, 128, 64], 65536, "bf16")
+    assert p.Kp == 60 and p.pad_x and not p.layers[0].wgrad16 and p.layers[1].wgrad16
+
+    # whole-tower kernels: Criteo-Kaggle's towers at 2048 rows on the GPU, never off it, never a tower with a 1024-wide layer, never the big batch
+    for ln, w in ((kag_bot, None), (kag_top, 368)):
+        p = plan(ln, 2048, "f32", in_width=w)
+        assert p.whole_tower and p.store is None and all(lp.out32 for lp in p.layers) and not p.head_fused
+        assert not plan(ln, 2048, "f32", gpu=False, in_width=w).whole_tower and not plan(ln, 65536, "f32", in_width=w).whole_tower
+        assert not plan(ln, 2048, "bf16", in_width=w).whole_tower
+    p = plan(kag_bot, 2048, "f32")
+    assert (p.pad_x, p.Kp, p.layers[0].K, p.in_width) == (True, 16, 16, 13)       # per-layer forward GEMMs: the 13 columns are padded
+    p = plan(kag_top, 2048, "f32", in_width=368)
+    assert (p.pad_x, p.Kp, p.layers[0].K, p.in_width) == (False, 368, 368, 368)  # an input that arrives padded meets a padded weight
+    assert not plan(_TB_TOWERS[1], 2048, "f32", in_width=480).whole_tower and plan(_TB_TOWERS[1], 2048, "f32", in_width=480).head_fused
+    assert not plan(_TB_TOWERS[1], 2048, "f32", in_width=480, consumer_act=True).head_fused
+    assert not plan([256, 1], 2048, "f32", gpu=False).head_fused              # a single layer has no layer below the head
+    with monkeypatch.context() as mp:
+        mp.setattr(functional, "TOWER_FWD", True)
+        p = plan(kag_bot, 2048, "f32")
+        assert p.whole_tower and p.tower_fwd and (p.pad_x, p.Kp, p.layers[0].K) == (False, 0, 13)
+    with monkeypatch.context() as mp:
+        mp.setattr(functional, "TOWER_L2_BYTES", 64 << 20)               # 128 workgroups x 0.6 MB of weights no longer fit
+        assert not plan(kag_bot, 2048, "f32").whole_tower
+    with monkeypatch.context() as mp:
+        mp.setattr(functional, "TOWER_ROWS", 1024)
+        assert not plan(kag_bot, 2048, "f32").whole_tower
+    with pytest.raises(RuntimeError, match="MLP input width 14 does not match the first layer"):
+        plan(kag_bot, 2048, "f32", in_width=14)
 
 
 def test_bench_node_state_never_raises_and_reads_the_sysfs_format(tmp_path, monkeypatch):
@@ -830,3 +1095,25 @@ def test_scratch_cache_is_grow_only_per_kind_and_stream(monkeypatch):
     assert ops._scratch("tower", 0, cpu, stream=3).numel() == 0
     assert set(ops._scratch_ws) == {("emb", cpu, 1), ("emb", cpu, 2), ("wgrad", cpu, 1), ("tower", cpu, 1), ("tower", cpu, 3)}
     assert [w_ for (_, d_, _), w_ in ops._scratch_ws.items() if d_ == cpu and w_ is big] == [big]     # what GraphedTrainStep pins
+
+
+if __name__ == "__main__":
+    # python tests/test_host_logic.py --record FILE [--traces DIR]: write the fixture of test_mlp_call_trace_equals_the_recorded_one from
+    # the dlrm_amd package of THIS checkout (and, with --traces, every case's full trace as text)
+    import argparse
+    import hashlib
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--record", required=True)
+    ap.add_argument("--traces")
+    args = ap.parse_args()
+    fixture = {}
+    for case in _trace_cases():
+        with pytest.MonkeyPatch.context() as mp:
+            rec = _record_mlp_trace(mp, *case)
+        fixture[_trace_id(case)] = {"sha256": hashlib.sha256(rec.text().encode()).hexdigest(), "calls": rec.calls}
+        if args.traces:
+            os.makedirs(args.traces, exist_ok=True)
+            open(os.path.join(args.traces, _trace_id(case).replace("|", "_") + ".txt"), "w").write(rec.text())
+    with open(args.record, "w") as f:
+        json.dump(fixture, f, indent=0, sort_keys=True)
+        f.write("\n")
