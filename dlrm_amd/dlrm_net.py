@@ -20,7 +20,7 @@ from __future__ import annotations
 import os
 import sys
 import weakref
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
                          BF16EmbeddingBagsFunction, EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
-                         MDEmbeddingBagsFunction, NarrowGatherInteractFunction, OutSlot, QREmbeddingBagsFunction, QRGatherInteractFunction)
+                         MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
 
@@ -71,6 +71,68 @@ def set_embedding_dtype(dtype=None, rounding: str = "stochastic", seed: int = 0)
     if rounding not in ops.BF16_ROUNDINGS:
         sys.exit("ERROR: bfloat16 embedding tables round 'stochastic' or 'nearest', got " + repr(rounding))
     _EMB_DTYPE = (torch.bfloat16, rounding, int(seed))
+
+
+class FusedRoute(NamedTuple):
+    """one row of fused_route's table"""
+    kind: str               # a key of ops.ROW_KINDS and functional.GATHER_KINDS; "fp32": dlrm_interact_*_gather
+    none_fused: bool        # undecided offsets (a HIP graph is being captured) run the fused kernels alone; False: the two-kernel form
+    host_proof: bool        # DLRM_DEVICE_PREDICATE=0 makes the host wait for the offsets' verdict; False: always the device-side state
+    align: int              # bytes every table's base address must be a multiple of (one lane's load of a row)
+    presort: bool           # the backward may take the SGD step of single-lookup rows itself (bags.presort)
+    autograd: bool          # False: a forward-only kernel, no autograd node (packed tables)
+
+
+# tables -> (route of D = 16 / 32 / 64, its ops.*_ok; route of D = 128, its ops.*_ok).  Given (tables, D) at most one of the two *_ok answers
+# is true — every D = 128 one requires D == 128, every narrow one is dlrm_interact_gather_narrow_ok — and every table kind has its own row:
+# the routes exclude each other.
+_ROUTES = {
+    "quant": ("narrow_quant", "gather_narrow_quant_ok", "quant", "gather_quant_ok"),
+    "qr": ("narrow_qr", "gather_narrow_qr_ok", "qr", "gather_qr_ok"),
+    "bf16": ("narrow_bf16", "gather_narrow_bf16_ok", "bf16", "gather_bf16_ok"),
+    "fp32": ("narrow", "gather_narrow_ok", "fp32", "gather_ok"),
+}
+
+
+def fused_route(tables: str, F: int, D: int, bits: int = 0, *, fuse_emb_interact: bool, fuse_quant_interact: bool, fuse_qr_interact: bool,
+                fuse_bf16_interact: bool, fuse_narrow_interact: bool, update_in_backward: bool, interaction_op: str = "dot",
+                on_gpu: bool = True, pooling_weights: bool = False, grad_wanted: bool = False, bf16_rows: bool = False) -> Optional[FusedRoute]:
+    """Which fused lookup + interaction kernels a model runs, decided once and from plain values: None = the two-kernel form.
+    tables: "fp32" | "bf16" | "qr" | "md" | "quant" (packed; `bits` 4 | 8); F = 1 + T features of width D; the model's fuse_* attributes and
+    update_in_backward; grad_wanted (packed tables only): the forward wants a gradient through the bottom tower, which only InteractFunction
+    carries; bf16_rows: a QR list stored as bfloat16 (no kernel).  Touches no device and allocates nothing: the ops.gather_*_ok asked only
+    load the library.  What a batch has to add at run time — B lookups per table, aligned tables, the offsets' state — is asked by
+    DLRM_Net._fused_forward, after the route.
+
+    Common to every route: fuse_emb_interact, the dot interaction, a GPU batch, no mixed-dimension table, no pooling weights.  Then
+      tables   admitted by                              D = 16 / 32 / 64 with fuse_narrow_interact   else D = 128
+      quant    fuse_quant_interact, no grad_wanted      narrow_quant                                 quant
+      qr       fuse_qr_interact, no bf16_rows           narrow_qr                                    qr
+      bf16     fuse_bf16_interact                       narrow_bf16                                  bf16
+      fp32     (always)                                 narrow                                       fp32, presort iff update_in_backward
+    The narrow routes of trained tables keep the two-kernel form for undecided offsets (none_fused False); the packed routes have no autograd
+    node and never wait for a host-side proof; align is ops.RowKind.align of the kind, ops.packed_align(bits), or ops.GATHER_ALIGN."""
+    if not (fuse_emb_interact and interaction_op == "dot" and on_gpu) or tables == "md" or pooling_weights:
+        return None
+    packed = tables == "quant"
+    shape = (F, D, bits) if packed else (F, D)
+    if packed:
+        own = fuse_quant_interact and not grad_wanted
+    elif tables == "qr":
+        own = fuse_qr_interact and not bf16_rows
+    else:
+        own = fuse_bf16_interact if tables == "bf16" else True
+    if not own:
+        return None
+    narrow, narrow_ok, wide, wide_ok = _ROUTES[tables]
+    if fuse_narrow_interact and getattr(ops, narrow_ok)(*shape):
+        kind = narrow
+    elif getattr(ops, wide_ok)(*shape):
+        kind = wide
+    else:
+        return None
+    align = ops.packed_align(bits) if packed else ops.GATHER_ALIGN if kind == "fp32" else ops.ROW_KINDS[kind].align
+    return FusedRoute(kind, packed or kind == wide, not packed, align, kind == "fp32" and bool(update_in_backward), not packed)
 
 
 def _mix_seed(seed: int, call_no: int, stream_id: int = 0) -> int:
@@ -346,7 +408,7 @@ class DLRM_Net(nn.Module):
     # of sequential_forward under the fp32 branch's conditions and runs csrc/interact_narrow.hip (forward and backward) instead of dlrm_emb_fwd
     # + the generic interaction kernels through the pooled [B, T*D] buffer — the same bits.  Off: such a model runs exactly the two-kernel form.
     # Together with fuse_bf16_interact a bfloat16 model of those widths enters too (csrc/interact_narrow_rows.hip, forward and backward), and
-    # together with fuse_quant_interact a quantised model of those widths takes the narrow fused forward of that file (_quant_fused_forward),
+    # together with fuse_quant_interact a quantised model of those widths takes the narrow fused forward of that file (fused_route),
     # and together with fuse_qr_interact a model with QR tables of those widths enters too (csrc/interact_narrow_qr.hip, forward and backward).
     fuse_narrow_interact = False
     # opt-in (launcher: --fused-adagrad): a stock torch.optim.Adagrad that owns the tables (the reference's --optimizer=adagrad) gets the fused
@@ -1024,14 +1086,18 @@ class DLRM_Net(nn.Module):
         return p
 
     def sequential_forward(self, dense_x, lS_o, lS_i):
-        """bottom MLP -> embeddings -> interaction -> top MLP (dlrm_s_pytorch.py:587-612), with the
-        bottom tower and the embedding kernel writing directly into the [B, (1+T)*D] feature buffer."""
+        """bottom MLP -> embeddings -> interaction -> top MLP (dlrm_s_pytorch.py:587-612): the fused lookup + interaction form where a route
+        and the batch admit it (_fused_forward), else the two-kernel form, with the bottom tower and the embedding kernel writing directly
+        into the [B, (1+T)*D] feature buffer."""
         if self.arch_interaction_op not in ("dot", "cat"):
             sys.exit("ERROR: --arch-interaction-op=" + str(self.arch_interaction_op) + " is not supported")
         ops.check_index_errors()          # host memory read, no synchronisation: bad indices of earlier steps surface here
         B = dense_x.size(0)
-        if self.quantize_emb:
+        quant = self.quantize_emb
+        if quant:
             T, D = len(self.emb_l_q), self.emb_q_dim
+            if self.update_in_backward:
+                sys.exit("ERROR: update_in_backward trains the embedding tables; quantized tables are constants (inference only)")
         else:
             T = len(self.emb_l)
             D = self._emb_dim(self.emb_l)
@@ -1040,50 +1106,12 @@ class DLRM_Net(nn.Module):
             sys.exit("ERROR: bottom MLP output (%d) and embedding dimension (%d) differ" % (n_out, D))
         # the last ReLU of the bottom tower is differentiated inside the interaction backward (which has x staged): see _relu_x
         rx = self._relu_x() if dense_x.is_cuda else 0
-        if self.quantize_emb:
-            # the fused form where it applies (_quant_fused_forward), else the two-kernel form: the bottom tower writes its slot of the feature
-            # buffer, dlrm_emb_fwd_quant the rest; interaction and top tower as below.
-            if self.update_in_backward:
-                sys.exit("ERROR: update_in_backward trains the embedding tables; quantized tables are constants (inference only)")
-            z = self._quant_fused_forward(dense_x, lS_o, lS_i, B, T, D)
-            if z is not None:
-                return self._clamp(self.apply_mlp(z, self.top_l))
-            feat = torch.empty((B, n_out + T * D), dtype=torch.float32, device=dense_x.device)
-            x = self.apply_mlp(dense_x, self.bot_l, out_slot=OutSlot(feat[:, :n_out]), consumer_applies_last_act=bool(rx))
-            E = self._emb_quant_into(lS_o, lS_i, self.v_W_l, feat[:, n_out:])
-            if self.arch_interaction_op == "cat":
-                z = CatFunction.apply(OutSlot(feat), x, E)
-            else:
-                z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)
+        z = self._fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
+        if z is not None:
             return self._clamp(self.apply_mlp(z, self.top_l))
-        # (a model with a mixed-dimension table takes the two-kernel form: the fused lookup + interaction kernels fetch plain fp32 rows — and with it
-        # the step-time update, update_in_backward included.  So does a model with a QR table unless fuse_qr_interact is set: _qr_fused_forward)
-        if self.fuse_qr_interact and self._has_qr(self.emb_l):
-            z = self._qr_fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
-            if z is not None:
-                return self._clamp(self.apply_mlp(z, self.top_l))
-        if self.fuse_narrow_interact:
-            z = self._narrow_fused_forward(dense_x, lS_o, lS_i, B, T, D, rx)
-            if z is not None:
-                return self._clamp(self.apply_mlp(z, self.top_l))
-        # fp32 tables of D = 128 — or bfloat16 ones, only with fuse_bf16_interact set, through csrc/interact_bf16.hip: ops.interact_*_gather
-        # dispatch on the tables' dtype.  Undecided offsets (a HIP graph is being captured) run the fused kernels alone: GraphedTrainStep
-        # proves every incoming batch.
-        bf16 = self.emb_bf16 is not None
-        gate = self._fused_gate(dense_x, lS_o, lS_i, B,
-                                lambda: ((self.fuse_bf16_interact and ops.gather_bf16_ok(1 + T, D)) if bf16 else ops.gather_ok(1 + T, D))
-                                and not self._has_qr(self.emb_l),
-                                ops.ROW_KINDS["bf16"].align if bf16 else ops.GATHER_ALIGN)
-        if gate is not None:
-            bags, ws = gate
-            x = self._fused_bottom(dense_x, lS_o, bags, rx, none_fused=True)
-            if x is not None:
-                # (bfloat16 tables: no update inside the backward — update_in_backward falls back to the step-time update)
-                bags.presort = self._presort_for_backward if (self.update_in_backward and not bf16) else None
-                z = GatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x, *ws)
-                return self._clamp(self.apply_mlp(z, self.top_l))
+        # the two-kernel form: the bottom tower writes its slot of the feature buffer, the lookup (dlrm_emb_fwd_quant for packed tables) the rest
         feat = torch.empty((B, n_out + T * D), dtype=torch.float32, device=dense_x.device)
-        if self.overlap_streams and dense_x.is_cuda:
+        if self.overlap_streams and dense_x.is_cuda and not quant:
             # pooled lookups (HBM-bound) on the side stream beside the bottom-MLP GEMMs (MFMA-bound): they only meet at the
             # interaction.  The side stream first waits for everything already enqueued (inputs, the previous update).
             main, side = torch.cuda.current_stream(dense_x.device), _side_stream(dense_x.device)
@@ -1096,26 +1124,64 @@ class DLRM_Net(nn.Module):
             main.wait_stream(side)
         else:
             x = self.apply_mlp(dense_x, self.bot_l, out_slot=OutSlot(feat[:, :n_out]), consumer_applies_last_act=bool(rx))
-            E = self._emb_packed(lS_o, lS_i, self.emb_l, self.v_W_l, out_slot=OutSlot(feat[:, n_out:]))
+            if quant:
+                E = self._emb_quant_into(lS_o, lS_i, self.v_W_l, feat[:, n_out:])
+            else:
+                E = self._emb_packed(lS_o, lS_i, self.emb_l, self.v_W_l, out_slot=OutSlot(feat[:, n_out:]))
         if self.arch_interaction_op == "cat":
             z = CatFunction.apply(OutSlot(feat), x, E)      # the feature buffer IS cat([x] + ly, 1): nothing is copied
         else:
             z = InteractFunction.apply(D, self._interaction_mode() | rx, True, x, E)   # [B, round4(width)], zero padded
         return self._clamp(self.apply_mlp(z, self.top_l))
 
-    def _fused_gate(self, dense_x, lS_o, lS_i, B, shape_ok, align):
-        """What every fused lookup + interaction path asks first: fuse_emb_interact, the dot interaction, a GPU batch, shape_ok() (the caller's
-        own rule: a kernel for this F, D and table kind, and the flags that admit it), no mixed-dimension table, no pooling weights, B lookups
-        per table, and every table's base address a multiple of `align` bytes (one lane's load: ops.RowKind.align).
-        -> (bags, the tables as the kernels see them), or None: the two-kernel form."""
-        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda and shape_ok()
-                and not self._has_md(self.emb_l) and not any(w is not None for w in (self.v_W_l or []))):
+    def _table_kind(self) -> str:
+        """the `tables` argument of fused_route (a QR list stored as bfloat16 — refused at construction — stays "qr": see its bf16_rows)"""
+        if self.quantize_emb:
+            return "quant"
+        kind = "fp32" if self.emb_bf16 is None else "bf16"
+        for e in self.emb_l:
+            if isinstance(e, (PrEmbeddingBagHolder, QREmbeddingBagHolder)):       # (one test per plain table: this runs at every step)
+                if isinstance(e, PrEmbeddingBagHolder):
+                    return "md"
+                kind = "qr"
+        return kind
+
+    def _fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
+        """The interaction output through the fused lookup + interaction kernels of the route fused_route picks, or None: the two-kernel form.
+        What the route cannot know is asked here: B lookups per table, every table's base address a multiple of route.align bytes (one lane's
+        load: ops.RowKind.align), and the offsets' state (_fused_bottom).  Undecided offsets (a HIP graph is being captured) run the fused
+        kernels alone where route.none_fused says so: GraphedTrainStep proves every incoming batch, for the shapes of ops.gather_ok.
+        Packed tables (route.autograd False) are constants: no autograd node, the bottom tower keeps its own last activation, and a forward
+        whose bottom tower is being trained is no route at all (InteractFunction carries the gradient of x)."""
+        if not (self.fuse_emb_interact and self.arch_interaction_op == "dot" and dense_x.is_cuda):
+            return None                     # (fused_route's first three conditions, asked before anything is looked at)
+        tables = self._table_kind()
+        packed = tables == "quant"
+        route = fused_route(
+            tables, 1 + T, D, self.quantize_bits if packed else 0, fuse_emb_interact=True, fuse_quant_interact=self.fuse_quant_interact,
+            fuse_qr_interact=self.fuse_qr_interact, fuse_bf16_interact=self.fuse_bf16_interact, fuse_narrow_interact=self.fuse_narrow_interact,
+            update_in_backward=self.update_in_backward, pooling_weights=any(w is not None for w in (self.v_W_l or [])),
+            grad_wanted=packed and torch.is_grad_enabled() and (dense_x.requires_grad or (
+                getattr(self.bot_l, "quant_bits", 32) == 32 and any(p_.requires_grad for p_ in self.bot_l.parameters()))),
+            bf16_rows=self.emb_bf16 is not None)
+        if route is None:
             return None
         bags = self._bags(lS_o, lS_i, None)
-        tables = self.emb_l_q if self.quantize_emb else self._emb_weights(self.emb_l)
-        if not (all(n == B for n in bags.nnz) and ops.tables_aligned(tables, align)):
+        ws = self.emb_l_q if packed else self._emb_weights(self.emb_l)
+        if not (all(n == B for n in bags.nnz) and ops.tables_aligned(ws, route.align)):
             return None
-        return bags, tables
+        if not route.autograd:
+            rx = 0
+        x = self._fused_bottom(dense_x, lS_o, bags, rx, route.none_fused, route.host_proof)
+        if x is None:
+            return None
+        if not route.autograd:
+            return _functional.gather_interact_fwd(None, None, route.kind, (self.emb_q_rows, D, self.quantize_bits), D,
+                                                   self._interaction_mode(), bags, x, ws)
+        # (the update inside the backward exists for fp32 tables of D = 128 only: everywhere else update_in_backward falls back to the step-time update)
+        bags.presort = self._presort_for_backward if route.presort else None
+        spec = self._qr_spec(self.emb_l) if tables == "qr" else None
+        return GatherInteractFunction.apply(self._stash_embedding_grad, route.kind, spec, D, self._interaction_mode() | rx, bags, x, *ws)
 
     def _fused_bottom(self, dense_x, lS_o, bags, rx, none_fused, host_proof=True):
         """The offsets decision of the fused paths, with the bottom tower in its middle -> the tower's output x with bags.iota_flag set, or None:
@@ -1143,66 +1209,6 @@ class DLRM_Net(nn.Module):
                 return None
         bags.iota_flag = state if isinstance(state, torch.Tensor) else None
         return x
-
-    def _qr_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
-        """The interaction output of a model with QR tables through csrc/interact_qr.hip (QRGatherInteractFunction), or None when the two-kernel
-        form has to run.  D = 16 / 32 / 64 run csrc/interact_narrow_qr.hip, only with fuse_narrow_interact set as well, and then undecided offsets
-        take the two-kernel form (_narrow_fused_forward's rule).  The update stays the step-time one, update_in_backward included."""
-        narrow = self.fuse_narrow_interact and ops.gather_narrow_qr_ok(1 + T, D)
-        gate = self._fused_gate(dense_x, lS_o, lS_i, B, lambda: self.emb_bf16 is None and (narrow or ops.gather_qr_ok(1 + T, D)),
-                                ops.ROW_KINDS["narrow_qr" if narrow else "qr"].align)
-        x = None if gate is None else self._fused_bottom(dense_x, lS_o, gate[0], rx, none_fused=not narrow)
-        if x is None:
-            return None
-        bags, ws = gate
-        bags.presort = None
-        return QRGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, self._qr_spec(self.emb_l), x, *ws)
-
-    def _narrow_fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
-        """The interaction output of a model with plain fp32 tables of D = 16 / 32 / 64 through csrc/interact_narrow.hip, or — only with
-        fuse_bf16_interact set as well — of a model with bfloat16 tables of those widths through csrc/interact_narrow_rows.hip
-        (NarrowGatherInteractFunction dispatches on the tables' dtype), or None when the two-kernel form has to run.  Undecided offsets take
-        the two-kernel form: GraphedTrainStep proves the offsets of every incoming batch only for the shapes of ops.gather_ok.  The update
-        stays the step-time one, update_in_backward included: the update inside the backward exists at D = 128 only."""
-        bf16 = self.emb_bf16 is not None
-        gate = self._fused_gate(dense_x, lS_o, lS_i, B,
-                                lambda: ((self.fuse_bf16_interact and ops.gather_narrow_bf16_ok(1 + T, D)) if bf16
-                                         else ops.gather_narrow_ok(1 + T, D)) and not self._has_qr(self.emb_l),
-                                ops.ROW_KINDS["narrow_bf16" if bf16 else "narrow"].align)
-        x = None if gate is None else self._fused_bottom(dense_x, lS_o, gate[0], rx, none_fused=False)
-        if x is None:
-            return None
-        bags, ws = gate
-        bags.presort = None
-        return NarrowGatherInteractFunction.apply(self._stash_embedding_grad, D, self._interaction_mode() | rx, bags, x, *ws)
-
-    def _quant_fused_forward(self, dense_x, lS_o, lS_i, B, T, D):
-        """The interaction output of a quantised model through dlrm_interact_fwd_gather_quant, or None when the two-kernel form has to run;
-        besides the common gate: fuse_quant_interact off, or a forward that wants gradients (the fused kernel is forward only).  D = 128 runs
-        csrc/interact_quant.hip; D = 16 / 32 / 64 run dlrm_interact_fwd_gather_narrow_quant (csrc/interact_narrow_rows.hip), only with
-        fuse_narrow_interact set as well — same rules.  The offsets' state is always the device-side one; undecided offsets run the fused
-        kernel alone.  No autograd node: the tables are constants, the bottom tower keeps its own last activation."""
-        bits = self.quantize_bits
-        narrow = self.fuse_narrow_interact and ops.gather_narrow_quant_ok(1 + T, D, bits)
-
-        def shape_ok():
-            if not (self.fuse_quant_interact and (narrow or ops.gather_quant_ok(1 + T, D, bits))):
-                return False
-            # (a forward whose bottom tower is being trained: InteractFunction carries the gradient of x)
-            return not (torch.is_grad_enabled() and (dense_x.requires_grad or (getattr(self.bot_l, "quant_bits", 32) == 32
-                                                                               and any(p_.requires_grad for p_ in self.bot_l.parameters()))))
-
-        gate = self._fused_gate(dense_x, lS_o, lS_i, B, shape_ok, ops.packed_align(bits))
-        x = None if gate is None else self._fused_bottom(dense_x, lS_o, gate[0], 0, none_fused=True, host_proof=False)
-        if x is None:
-            return None
-        bags, qws = gate
-        fused = ops.interact_fwd_gather_narrow_quant if narrow else ops.interact_fwd_gather_quant
-        x = _functional._rowmajor(x)
-        return _functional.gather_interact_fwd(
-            None, None, D, self._interaction_mode(), bags, x, T,
-            lambda mode, R, pred: fused(x, qws, self.emb_q_rows, D, bits, bags, mode, R, pred=pred),
-            lambda ly, pred: ops.emb_fwd_quant(qws, self.emb_q_rows, D, bits, bags, ly, pred=pred))
 
     def distributed_forward(self, dense_x, lS_o, lS_i):
         """Table-wise sharded embeddings + batch-split MLPs (dlrm_s_pytorch.py:528-585): every rank pools

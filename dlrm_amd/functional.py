@@ -574,6 +574,20 @@ class MLPFunction(Function):
         return (dX, None, None, None, *grads)
 
 
+_NO_SINK = "dlrm_amd: embedding backward needs a gradient sink (fused update)"
+_NO_QR_SUMS = "dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept"
+
+
+def _qr_tables(vweights, collisions):
+    """the VIRTUAL table list (weight_q then weight_r of a QR table, the weight of a plain one) -> (weights, weights_r), None for a plain table's r"""
+    it = iter(vweights)
+    weights, weights_r = [], []
+    for c in collisions:
+        weights.append(next(it))
+        weights_r.append(next(it) if c else None)
+    return weights, weights_r
+
+
 class EmbeddingBagsFunction(Function):
     """All T EmbeddingBag(sum) lookups in one kernel launch; the backward pass does NOT materialise a
     gradient: it hands (bags, d_out) to `sink`, which applies the fused sparse update when the
@@ -600,7 +614,7 @@ class EmbeddingBagsFunction(Function):
     @staticmethod
     def backward(ctx, dout):
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         dout = _rowmajor(dout)
         dvw = (None,) * len(ctx.vws)
         if ctx.vws and any(ctx.needs_input_grad[3 + len(ctx.weights):]):
@@ -635,7 +649,7 @@ class BF16EmbeddingBagsFunction(Function):
     @staticmethod
     def backward(ctx, dout):
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         ctx.sink(ctx.weights, ctx.bags, _rowmajor(dout))
         return (None, None, None) + (None,) * (len(ctx.weights) + ctx.n_vws)
 
@@ -650,11 +664,7 @@ class QREmbeddingBagsFunction(Function):
     @staticmethod
     def forward(ctx, sink, bags, out_slot, spec, *vweights):
         rows, collisions, op, keep_sums = spec
-        weights, weights_r = [], []
-        it = iter(vweights)
-        for c in collisions:
-            weights.append(next(it))
-            weights_r.append(next(it) if c else None)
+        weights, weights_r = _qr_tables(vweights, collisions)
         D = weights[0].size(1)
         out = out_slot.get() if out_slot is not None else alloc2d(bags.B, bags.T * D, weights[0])
         saved = None
@@ -669,10 +679,10 @@ class QREmbeddingBagsFunction(Function):
     @staticmethod
     def backward(ctx, dout):
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         rows, collisions, op, _ = ctx.spec
         if op == "mult" and ctx.saved is None:
-            raise RuntimeError("dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept")
+            raise RuntimeError(_NO_QR_SUMS)
         gout = ops.emb_qr_bwd_split(collisions, op, ctx.D, _rowmajor(dout), ctx.saved)     # (the sums stay with the node: a retained graph may run again)
         ctx.sink(ctx.vweights, ops.qr_virtual_bags(rows, collisions, ctx.bags), gout)
         return (None, None, None, None) + (None,) * len(ctx.vweights)
@@ -705,7 +715,7 @@ class MDEmbeddingBagsFunction(Function):
     @staticmethod
     def backward(ctx, dout):
         if ctx.sink is None:
-            raise RuntimeError("dlrm_amd: embedding backward needs a gradient sink (fused update)")
+            raise RuntimeError(_NO_SINK)
         T, layout = len(ctx.weights), ctx.layout
         need = iter(ctx.needs_input_grad[4 + T:])
         want = [p_ is not None and next(need) for p_ in ctx.projs]
@@ -765,42 +775,74 @@ class InteractFunction(Function):
         return (None, None, None, *dblocks) if ctx.order is None else (None, None, None, None, *dblocks)
 
 
-def gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, T, fused, lookup):
-    """The forward every fused lookup + interaction Function shares (and, with ctx = None, DLRM_Net._quant_fused_forward, which needs no autograd
-    node): R [B, round4(width)] = interaction of [x | one row per bag of T tables].
+class GatherKind(NamedTuple):
+    """What the fused lookup + interaction path needs to know of a route's kind (dlrm_net.fused_route): a key of ops.ROW_KINDS, or "fp32".
+    The wrappers are NAMES of `ops` attributes, looked up when they are called."""
+    fwd: str
+    bwd: Optional[str]          # None: forward only (packed tables are constants; their table description holds D)
+    lookup: str                 # the lookup of the two-kernel form behind (flag, 1)
+    virtual: bool = False       # QR: the sink takes the VIRTUAL table list, its [B, Tv*D] buffer (emb_qr_bwd_split behind (flag, 1)) and qr_virtual_bags
+    presort: bool = False       # `bags.presort` is read: the update inside the backward
+
+
+# (fp32 and bf16 at D = 128 name the same wrappers: ops.interact_*_gather dispatch on the tables' dtype themselves)
+GATHER_KINDS = {
+    "fp32": GatherKind("interact_fwd_gather", "interact_bwd_gather", "emb_fwd", presort=True),
+    "bf16": GatherKind("interact_fwd_gather", "interact_bwd_gather", "emb_fwd_bf16"),
+    "narrow": GatherKind("interact_fwd_gather_narrow", "interact_bwd_gather_narrow", "emb_fwd"),
+    "narrow_bf16": GatherKind("interact_fwd_gather_narrow_bf16", "interact_bwd_gather_narrow_bf16", "emb_fwd_bf16"),
+    "qr": GatherKind("interact_fwd_gather_qr", "interact_bwd_gather_qr", "emb_fwd_qr", virtual=True),
+    "narrow_qr": GatherKind("interact_fwd_gather_narrow_qr", "interact_bwd_gather_narrow_qr", "emb_fwd_qr", virtual=True),
+    "quant": GatherKind("interact_fwd_gather_quant", None, "emb_fwd_quant"),
+    "narrow_quant": GatherKind("interact_fwd_gather_narrow_quant", None, "emb_fwd_quant"),
+}
+
+
+def gather_interact_fwd(ctx, sink, kind, spec, D, self_interaction, bags, x, tables):
+    """The forward of the fused lookup + interaction path, for GatherInteractFunction and, with ctx = None, for the packed routes, which need no
+    autograd node: R [B, round4(width)] = interaction of [x | one row per bag of the tables of `kind`].
+    spec: None for plain tables; (rows, collisions, operation, keep_sums) with `tables` the VIRTUAL list for QR ones, as QREmbeddingBagsFunction
+    takes them; (rows, D, bits) for packed ones.
     `bags.iota_flag` (a device int32, ops.offsets_iota_state in dlrm_amd/iota.py): whether the batch really has ONE lookup per bag is known on the
-    device only — nnz == B does not prove it.  Absent: fused(mode, R, None) runs alone.  Present: both implementations are enqueued with that launch
-    predicate (ABI 16) — fused(mode, R, (flag, 0)) runs if the flag is zero; lookup(ly, (flag, 1)) + the plain interaction (the reference's
-    apply_emb + interact_features as two kernels, through a pooled buffer ly that then has to live until backward) run if it is not.  The launches
-    that do not run return at once; the host never waits.  `lookup` also allocates whatever else its kind keeps for the backward."""
-    mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
-    R = torch.empty((x.size(0), _round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
-    flag = getattr(bags, "iota_flag", None)
-    ly = None
-    if flag is None:
-        fused(mode, R, None)
+    device only — nnz == B does not prove it.  Absent: the fused call runs alone.  Present: both implementations are enqueued with that launch
+    predicate (ABI 16) — the fused call runs if the flag is zero; the lookup + the plain interaction (the reference's apply_emb +
+    interact_features as two kernels, through a pooled buffer ly that then has to live until backward; QR: and the two pooled sums) run if it is
+    not.  The launches that do not run return at once; the host never waits."""
+    k = GATHER_KINDS[kind]
+    x = _rowmajor(x)
+    B, sums = x.size(0), 0
+    if k.virtual:
+        rows, collisions, op, keep_sums = spec
+        t = (*_qr_tables(tables, collisions), rows, collisions, op)
+        T = len(collisions)
+        if keep_sums and op == "mult":
+            sums = 2 * D * sum(1 for c in collisions if c)
     else:
-        fused(mode, R, (flag, 0))
-        ly = alloc2d(x.size(0), T * D, x)
-        lookup(ly, (flag, 1))
+        t, T = (tables,) if spec is None else (tables, *spec), len(tables)
+    mode = int(self_interaction) & 3                      # (| ops.INTERACT_RELU_X: see InteractFunction.forward)
+    R = torch.empty((B, _round4(ops.interact_out_width(1 + T, D, mode))), dtype=torch.float32, device=x.device)
+    flag = getattr(bags, "iota_flag", None)
+    fwd = getattr(ops, k.fwd)
+    out = (bags, mode, R) if k.bwd is None else (bags, D, mode, R)
+    ly = saved = None
+    if flag is None:
+        fwd(x, *t, *out, pred=None)
+    else:
+        fwd(x, *t, *out, pred=(flag, 0))
+        ly = alloc2d(B, T * D, x)
+        if k.virtual:
+            if sums:
+                saved = torch.empty((B, sums), dtype=torch.float32, device=x.device)
+            getattr(ops, k.lookup)(*t, bags, ly, saved, pred=(flag, 1))
+        else:
+            getattr(ops, k.lookup)(*t, bags, ly, pred=(flag, 1))
         ops.interact_fwd((x, ly), D, mode, R, pred=(flag, 1))
     if ctx is not None:
-        ctx.sink, ctx.bags, ctx.flag = sink, bags, flag
-        ctx.D, ctx.self_interaction = D, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
+        ctx.sink, ctx.bags, ctx.flag, ctx.kind = sink, bags, flag, kind
+        ctx.D, ctx.T, ctx.self_interaction = D, T, int(self_interaction) & (3 | ops.INTERACT_RELU_X)
+        ctx.tables, ctx.t, ctx.saved = tables, t, saved      # parameters (leaves) — kept by reference, not via save_for_backward
         ctx.save_for_backward(*((x,) if ly is None else (x, ly)))
     return R                                   # zero padding columns (what MLPFunction takes as is)
-
-
-def _gather_interact_bwd(ctx, x, dR, dx, fused, pooled_grad, split=None):
-    """... and the backward: fused(pred) writes dx and the gradient of the gathered rows; with a flag it runs behind (flag, 0), and behind
-    (flag, 1) the plain interaction backward over (x, the saved pooled buffer) writes dx and dE = pooled_grad(), which split(dE), if any, turns
-    into what the sink takes"""
-    fused(None if ctx.flag is None else (ctx.flag, 0))
-    if ctx.flag is not None:
-        dE = pooled_grad()
-        ops.interact_bwd((x, ctx.saved_tensors[1]), ctx.D, ctx.self_interaction, dR, (dx, dE), pred=(ctx.flag, 1))
-        if split is not None:
-            split(dE)
 
 
 def _flat_dx_dE(B, D, T, device):
@@ -809,143 +851,53 @@ def _flat_dx_dE(B, D, T, device):
     return flat[:B * D].view(B, D), flat[B * D:].view(B, T * D)
 
 
-_NO_SINK = "dlrm_amd: embedding backward needs a gradient sink (fused update)"
-
-
 class GatherInteractFunction(Function):
-    """apply_emb + interact_features fused for one-lookup-per-bag batches (dlrm_s_pytorch.py:407-462 + 483-504):
-    R = [x | lower-triangular dots of (x, E_1[idx_1], ..., E_T[idx_T])], the embedding rows fetched by the interaction kernel
-    itself — the [B, T*D] pooled-embedding buffer is neither written nor read back.  Backward recomputes nothing: it gathers
-    the same rows again, writes dx and the [B, T*D] gradient of the gathered rows, and hands the latter to `sink` (the fused
-    sparse update), exactly like EmbeddingBagsFunction.backward."""
+    """apply_emb + interact_features fused for one-lookup-per-bag batches (dlrm_s_pytorch.py:407-462 + 483-504), for every kind of
+    GATHER_KINDS with a backward: R = [x | lower-triangular dots of (x, the row of table 1, ..., the row of table T)], the rows fetched (QR:
+    and composed) by the interaction kernel itself — the bits of the kind's *EmbeddingBagsFunction + InteractFunction, without the [B, T*D]
+    pooled-embedding buffer (QR: its gradient and the [B, 2*Tq*D] pooled sums).  apply(sink, kind, spec, D, mode, bags, x, *tables): see
+    gather_interact_fwd.  Backward recomputes nothing: it gathers the same rows again, writes dx and the gradient of the gathered rows, and
+    hands the latter to `sink` (the fused sparse update) exactly as the kind's *EmbeddingBagsFunction.backward does: one update call per step,
+    with or without a flag."""
 
     @staticmethod
-    def forward(ctx, sink, D, self_interaction, bags, x, *weights):
-        x = _rowmajor(x)
-        ctx.weights = weights
-        # (bfloat16 tables: ops.interact_fwd_gather dispatches on the dtype; so does the lookup of the two-kernel form)
-        return gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, len(weights),
-                                   lambda mode, R, pred: ops.interact_fwd_gather(x, weights, bags, D, mode, R, pred=pred),
-                                   lambda ly, pred: (ops.emb_fwd_bf16 if weights[0].dtype == torch.bfloat16 else ops.emb_fwd)(
-                                       weights, bags, ly, pred=pred))
+    def forward(ctx, sink, kind, spec, D, self_interaction, bags, x, *tables):
+        return gather_interact_fwd(ctx, sink, kind, spec, D, self_interaction, bags, x, tables)
 
     @staticmethod
     def backward(ctx, dR):
-        x = ctx.saved_tensors[0]
-        dR = _rowmajor(dR)
-        T = len(ctx.weights)
-        dx, dE = _flat_dx_dE(x.size(0), ctx.D, T, dR.device)
         if ctx.sink is None:
             raise RuntimeError(_NO_SINK)
+        k = GATHER_KINDS[ctx.kind]
+        x = ctx.saved_tensors[0]
+        dR = _rowmajor(dR)
+        B, D, T, t, bags, flag = x.size(0), ctx.D, ctx.T, ctx.t, ctx.bags, ctx.flag
+        if k.virtual:
+            collisions, op = t[3], t[4]
+            dx = torch.empty((B, D), dtype=torch.float32, device=dR.device)
+            dE = torch.empty((B, len(ctx.tables) * D), dtype=torch.float32, device=dR.device)       # `gout`, the buffer of the virtual list
+        else:
+            dx, dE = _flat_dx_dE(B, D, T, dR.device)
+        pred = None if flag is None else (flag, 0)
         # `bags.presort` (DLRM_Net._presort_for_backward; None unless the model was told to update in backward and knows its SGD optimizer): the
         # sort of the sparse update runs NOW and the fused kernel takes the SGD step of every row a single lookup of the batch names (its table
         # row is staged in LDS anyway) — ops.Presorted travels to the sink, which applies the rest from the same sorted workspace
-        presort = getattr(ctx.bags, "presort", None)
-        pre = None
-
-        def fused(pred):
-            nonlocal pre
-            pre = presort(ctx.weights, ctx.bags, pred) if presort is not None else None
-            ops.interact_bwd_gather(x, ctx.weights, ctx.bags, ctx.D, ctx.self_interaction, dR, dx, dE, pred=pred, presorted=pre)
-
-        _gather_interact_bwd(ctx, x, dR, dx, fused, lambda: dE)
-        if pre is None:
-            ctx.sink(ctx.weights, ctx.bags, dE)
-        else:
-            ctx.sink(ctx.weights, ctx.bags, dE, presorted=pre)
-        return (None, None, None, None, dx) + (None,) * T
-
-
-class NarrowGatherInteractFunction(Function):
-    """GatherInteractFunction for plain fp32 tables of D = 16 / 32 / 64 (csrc/interact_narrow.hip), or bfloat16 tables of those widths
-    (csrc/interact_narrow_rows.hip; the calls dispatch on the tables' dtype): the bits of EmbeddingBagsFunction / BF16EmbeddingBagsFunction +
-    InteractFunction without the [B, T*D] pooled buffer.  dE goes to `sink` with or without a flag: one update call per step.  There is no update
-    inside the backward at these widths (`bags.presort` is not read)."""
-
-    @staticmethod
-    def forward(ctx, sink, D, self_interaction, bags, x, *weights):
-        x = _rowmajor(x)
-        ctx.weights = weights
-        ctx.bf16 = bf16 = ops._gather_tables_bf16(weights, "NarrowGatherInteractFunction")
-        fwd = ops.interact_fwd_gather_narrow_bf16 if bf16 else ops.interact_fwd_gather_narrow
-        lookup = ops.emb_fwd_bf16 if bf16 else ops.emb_fwd
-        return gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, len(weights),
-                                   lambda mode, R, pred: fwd(x, weights, bags, D, mode, R, pred=pred),
-                                   lambda ly, pred: lookup(weights, bags, ly, pred=pred))
-
-    @staticmethod
-    def backward(ctx, dR):
-        if ctx.sink is None:
-            raise RuntimeError(_NO_SINK)
-        x = ctx.saved_tensors[0]
-        dR = _rowmajor(dR)
-        T = len(ctx.weights)
-        dx, dE = _flat_dx_dE(x.size(0), ctx.D, T, dR.device)
-        bwd = ops.interact_bwd_gather_narrow_bf16 if ctx.bf16 else ops.interact_bwd_gather_narrow
-        _gather_interact_bwd(ctx, x, dR, dx,
-                             lambda pred: bwd(x, ctx.weights, ctx.bags, ctx.D, ctx.self_interaction, dR, dx, dE, pred=pred), lambda: dE)
-        ctx.sink(ctx.weights, ctx.bags, dE)
-        return (None, None, None, None, dx) + (None,) * T
-
-
-class QRGatherInteractFunction(Function):
-    """GatherInteractFunction for a table list with quotient-remainder tables (csrc/interact_qr.hip at D = 128, csrc/interact_narrow_qr.hip at
-    D = 16 / 32 / 64: the calls dispatch on the width): R = [x | lower-triangular dots of (x, the composed rows Wq[q] o Wr[r], plain rows)], the
-    rows fetched and composed by the interaction kernel itself — the bits of QREmbeddingBagsFunction + InteractFunction without the [B, T*D]
-    pooled buffer, its gradient or the [B, 2*Tq*D] pooled sums.
-    spec = (rows, collisions, operation, keep_sums) and `vweights` = the VIRTUAL table list, as QREmbeddingBagsFunction takes them.  Backward
-    gathers the rows again, writes dx and the gradient buffer of the virtual list and hands (virtual weights, virtual bags, buffer) to `sink`:
-    exactly what QREmbeddingBagsFunction.backward hands over."""
-
-    @staticmethod
-    def forward(ctx, sink, D, self_interaction, bags, spec, x, *vweights):
-        rows, collisions, op, keep_sums = spec
-        weights, weights_r = [], []
-        it = iter(vweights)
-        for c in collisions:
-            weights.append(next(it))
-            weights_r.append(next(it) if c else None)
-        x = _rowmajor(x)
-        T = len(weights)
-        ctx.spec, ctx.tables = spec, (weights, weights_r)
-        ctx.vweights = vweights      # parameters (leaves) — kept by reference, not via save_for_backward
-        ctx.saved = None
-        ctx.narrow = narrow = ops.gather_narrow_qr_ok(1 + T, D)
-        fwd = ops.interact_fwd_gather_narrow_qr if narrow else ops.interact_fwd_gather_qr
-
-        def lookup(ly, pred):
-            if keep_sums and op == "mult":
-                ctx.saved = torch.empty((x.size(0), 2 * D * sum(1 for c in collisions if c)), dtype=torch.float32, device=x.device)
-            ops.emb_fwd_qr(weights, weights_r, rows, collisions, op, bags, ly, ctx.saved, pred=pred)
-
-        return gather_interact_fwd(ctx, sink, D, self_interaction, bags, x, T,
-                                   lambda mode, R, pred: fwd(x, weights, weights_r, rows, collisions, op, bags, D, mode, R, pred=pred), lookup)
-
-    @staticmethod
-    def backward(ctx, dR):
-        if ctx.sink is None:
-            raise RuntimeError(_NO_SINK)
-        x = ctx.saved_tensors[0]
-        dR = _rowmajor(dR)
-        rows, collisions, op, _ = ctx.spec
-        weights, weights_r = ctx.tables
-        B, D, T = x.size(0), ctx.D, len(weights)
-        Tv = T + sum(1 for c in collisions if c)
-        dx = torch.empty((B, D), dtype=torch.float32, device=dR.device)
-        gout = torch.empty((B, Tv * D), dtype=torch.float32, device=dR.device)
-        bwd = ops.interact_bwd_gather_narrow_qr if ctx.narrow else ops.interact_bwd_gather_qr
-
-        def pooled_grad():
-            if op == "mult" and ctx.saved is None:
-                raise RuntimeError("dlrm_amd: this QR lookup ran without gradients enabled; its pooled sums were not kept")
-            return torch.empty((B, T * D), dtype=torch.float32, device=dR.device)
-
-        _gather_interact_bwd(ctx, x, dR, dx,
-                             lambda pred: bwd(x, weights, weights_r, rows, collisions, op, ctx.bags, D, ctx.self_interaction, dR, dx, gout,
-                                              pred=pred),
-                             pooled_grad, lambda dE: ops.emb_qr_bwd_split(collisions, op, D, dE, ctx.saved, gout, pred=(ctx.flag, 1)))
-        ctx.sink(ctx.vweights, ops.qr_virtual_bags(rows, collisions, ctx.bags), gout)
-        return (None, None, None, None, None, dx) + (None,) * len(ctx.vweights)
+        presort = getattr(bags, "presort", None) if k.presort else None
+        pre = presort(ctx.tables, bags, pred) if presort is not None else None
+        more = {} if pre is None else {"presorted": pre}
+        getattr(ops, k.bwd)(x, *t, bags, D, ctx.self_interaction, dR, dx, dE, pred=pred, **more)
+        if flag is not None:
+            # ... and behind (flag, 1) the plain interaction backward over (x, the saved pooled buffer)
+            pooled = dE
+            if k.virtual:
+                if op == "mult" and ctx.saved is None:
+                    raise RuntimeError(_NO_QR_SUMS)
+                pooled = torch.empty((B, T * D), dtype=torch.float32, device=dR.device)
+            ops.interact_bwd((x, ctx.saved_tensors[1]), D, ctx.self_interaction, dR, (dx, pooled), pred=(flag, 1))
+            if k.virtual:
+                ops.emb_qr_bwd_split(collisions, op, D, pooled, ctx.saved, dE, pred=(flag, 1))
+        ctx.sink(ctx.tables, ops.qr_virtual_bags(t[2], collisions, bags) if k.virtual else bags, dE, **more)
+        return (None, None, None, None, None, None, dx) + (None,) * len(ctx.tables)
 
 
 class LowRankCrossNetFunction(Function):

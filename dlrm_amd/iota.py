@@ -208,7 +208,7 @@ def offsets_iota_state(lS_o):
       True / False    the verdict is known (producer tag, or this tensor object was proven earlier);
       None            a HIP graph is being captured (undecided: GraphedTrainStep proves every incoming batch before the replay);
       a device int32  the proof was enqueued on the CURRENT stream (dlrm_offsets_iota_flags: number of bags whose start differs from their
-                      number) — the caller enqueues both implementations with that launch predicate (GatherInteractFunction) and never
+                      number) — the caller enqueues both implementations with that launch predicate (functional.gather_interact_fwd) and never
                       waits; the host-visible copy of the verdict is looked at whenever a later call finds its event complete."""
     for st in _states.values():
         _drain(st.pending)

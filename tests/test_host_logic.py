@@ -1097,6 +1097,101 @@ def test_scratch_cache_is_grow_only_per_kind_and_stream(monkeypatch):
     assert [w_ for (_, d_, _), w_ in ops._scratch_ws.items() if d_ == cpu and w_ is big] == [big]     # what GraphedTrainStep pins
 
 
+# ---- dlrm_net.fused_route against the table of routes as it stood before the selection became one function ----------------------------------
+# kind -> (none_fused, host_proof, align at 8 bits / for unpacked rows, align at 4 bits, autograd); presort: "fp32" with update_in_backward only
+_ROUTE_ROWS = {
+    "narrow_quant": (True, False, 8, 4, False), "quant": (True, False, 8, 4, False),
+    "narrow_qr": (False, True, 16, 16, True), "qr": (True, True, 16, 16, True),
+    "narrow": (False, True, 16, 16, True), "fp32": (True, True, 16, 16, True),
+    "narrow_bf16": (False, True, 8, 8, True), "bf16": (True, True, 16, 16, True),
+}
+_ROUTE_FLAGS = ("fuse_emb_interact", "fuse_quant_interact", "fuse_qr_interact", "fuse_bf16_interact", "fuse_narrow_interact")
+_NARROW_MAXF, _WIDE_MAXF = 32, 27          # dlrm_interact_gather_narrow_ok: F <= GC_MAXF; dlrm_interact_gather_ok at D = 128: F <= 27
+
+
+def _route_wanted(tables, F, D, bits, flags, uib=False, op="dot", gpu=True, pool=False, grad=False, bf16_rows=False):
+    """the kind the table of routes names, or None"""
+    if not (flags["fuse_emb_interact"] and op == "dot" and gpu) or tables == "md" or pool:
+        return None
+    narrow = flags["fuse_narrow_interact"] and D in (16, 32, 64) and F <= _NARROW_MAXF
+    wide = D == 128 and F <= _WIDE_MAXF
+    if tables == "quant":
+        if not flags["fuse_quant_interact"] or grad:
+            return None
+        return "narrow_quant" if narrow else "quant" if wide else None
+    if tables == "qr":
+        if not flags["fuse_qr_interact"] or bf16_rows:
+            return None
+        return "narrow_qr" if narrow else "qr" if wide else None
+    if tables == "bf16":
+        if not flags["fuse_bf16_interact"]:
+            return None
+        return "narrow_bf16" if narrow else "bf16" if wide else None
+    return "narrow" if narrow else "fp32" if wide else None
+
+
+def test_fused_route_reproduces_the_table_of_routes():
+    from dlrm_amd import ops
+    from dlrm_amd.dlrm_net import FusedRoute, fused_route
+    all_on = dict.fromkeys(_ROUTE_FLAGS, True)
+    states = [all_on] + [dict(all_on, **{f: False}) for f in _ROUTE_FLAGS]
+    others = [{}, {"uib": True}, {"op": "cat"}, {"gpu": False}, {"pool": True}, {"grad": True}, {"bf16_rows": True}]
+    names = {"uib": "update_in_backward", "op": "interaction_op", "gpu": "on_gpu", "pool": "pooling_weights", "grad": "grad_wanted",
+             "bf16_rows": "bf16_rows"}
+    seen = set()
+    for tables in ("fp32", "bf16", "qr", "md", "quant"):
+        for D in (16, 32, 64, 128, 48):
+            for F in (2, 27, 28, 33):
+                for bits in ((4, 8) if tables == "quant" else (0,)):
+                    for flags in states:
+                        for other in others:
+                            if other and flags is not all_on:
+                                continue
+                            why = (tables, D, F, bits, flags, other)
+                            got = fused_route(tables, F, D, bits, **flags, **{"update_in_backward": False, **{names[k]: v for k, v in other.items()}})
+                            kind = _route_wanted(tables, F, D, bits, flags, **other)
+                            if kind is None:
+                                assert got is None, why
+                                continue
+                            none_fused, host_proof, align8, align4, autograd = _ROUTE_ROWS[kind]
+                            want = FusedRoute(kind, none_fused, host_proof, align4 if bits == 4 else align8,
+                                              kind == "fp32" and bool(other.get("uib")), autograd)
+                            assert got == want, why
+                            seen.add(kind)
+    assert seen == set(_ROUTE_ROWS) and set(_ROUTE_ROWS) == set(ops.ROW_KINDS) | {"fp32"}
+    # a few rows of the table spelt out
+    on = dict(all_on, update_in_backward=True)
+    assert fused_route("fp32", 27, 128, **on) == FusedRoute("fp32", True, True, ops.GATHER_ALIGN, True, True)
+    assert fused_route("fp32", 27, 16, **on) == FusedRoute("narrow", False, True, 16, False, True)
+    assert fused_route("fp32", 27, 16, **dict(on, fuse_narrow_interact=False)) is None              # (the default model of the Kaggle step)
+    assert fused_route("bf16", 27, 64, **on) == FusedRoute("narrow_bf16", False, True, 8, False, True)
+    assert fused_route("qr", 4, 128, **on) == FusedRoute("qr", True, True, 16, False, True)
+    assert fused_route("qr", 4, 128, bf16_rows=True, **on) is None and fused_route("md", 4, 16, **on) is None
+    assert fused_route("quant", 27, 32, 4, **dict(on, update_in_backward=False)) == FusedRoute("narrow_quant", True, False, 4, False, False)
+    assert fused_route("quant", 27, 128, 8, **dict(on, update_in_backward=False)) == FusedRoute("quant", True, False, 8, False, False)
+    assert fused_route("quant", 27, 128, 8, grad_wanted=True, **on) is None
+    assert isinstance(fused_route("fp32", 2, 128, **on), tuple)                                      # an immutable record
+    with pytest.raises(AttributeError):
+        fused_route("fp32", 2, 128, **on).kind = "qr"
+
+
+def test_at_most_one_gather_ok_answers_for_a_table_kind_and_shape():
+    """what one decision per (table kind, D, F) rests on: the D = 128 kernels and the narrow ones never both take a shape — and the limits
+    _route_wanted states are the library's"""
+    from dlrm_amd import ops
+    pairs = {"fp32": (ops.gather_ok, ops.gather_narrow_ok), "bf16": (ops.gather_bf16_ok, ops.gather_narrow_bf16_ok),
+             "qr": (ops.gather_qr_ok, ops.gather_narrow_qr_ok),
+             "quant4": (lambda F, D: ops.gather_quant_ok(F, D, 4), lambda F, D: ops.gather_narrow_quant_ok(F, D, 4)),
+             "quant8": (lambda F, D: ops.gather_quant_ok(F, D, 8), lambda F, D: ops.gather_narrow_quant_ok(F, D, 8))}
+    for kind, (wide, narrow) in pairs.items():
+        for D in (8, 16, 32, 48, 64, 96, 128, 256):
+            for F in range(1, 40):
+                w, n = wide(F, D), narrow(F, D)
+                assert not (w and n), (kind, D, F)
+                assert w == (D == 128 and F <= _WIDE_MAXF), (kind, D, F)
+                assert n == (D in (16, 32, 64) and F <= _NARROW_MAXF), (kind, D, F)
+
+
 if __name__ == "__main__":
     # python tests/test_host_logic.py --record FILE [--traces DIR]: write the fixture of test_mlp_call_trace_equals_the_recorded_one from
     # the dlrm_amd package of THIS checkout (and, with --traces, every case's full trace as text)
