@@ -17,6 +17,7 @@ of the reference (nnz x D floats per table) is never written to HBM.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import sys
 import weakref
@@ -28,7 +29,7 @@ import torch.nn as nn
 
 from . import ext_dist, ops
 from .functional import (BCEElementwiseFunction, BCELossFunction, CatFunction, ChunkPackFunction, ClampFunction,
-                         BF16EmbeddingBagsFunction, EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
+                         EmbeddingBagsFunction, GatherInteractFunction, InteractFunction, MLPFunction, MSELossFunction,
                          MDEmbeddingBagsFunction, OutSlot, QREmbeddingBagsFunction)
 from . import functional as _functional
 from .functional import MLP_CONSUMER_APPLIES_LAST_ACT, _side_stream
@@ -380,12 +381,32 @@ class EmbeddingUpdateHook:
             model._join_side_stream()
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
+class ParkedGrad(NamedTuple):
+    """one backward pass of the embedding lookups, parked in DLRM_Net._pending_emb until an optimizer that owns the tables steps"""
+    weights: Sequence[torch.Tensor]
+    bags: BagBatch
+    dout: torch.Tensor                          # the [B, >= T*D] gradient buffer of the pooled lookups
+    presorted: Optional["ops.Presorted"] = None        # the backward pass already took the single-lookup rows (update_in_backward)
 
-    def __exit__(self, *exc):
-        return False
+
+# (update, tables) -> why that update is not built for those tables; every other pair runs.  update: the head of an _embedding_update_plan
+# result — "sgd", "rwsadagrad", "adagrad", "coo" — or "unfused" (fused_emb_update = False: the COO gradient whatever the optimizer);
+# tables: DLRM_Net._table_kind().  Read by DLRM_Net._refuse_update alone.
+UPDATE_REFUSALS = {
+    ("adagrad", "bf16"): "ERROR: the fused exact Adagrad update is not built for bfloat16 embedding tables; use SGD or row-wise Adagrad",
+    ("adagrad", "qr"): "ERROR: the fused exact Adagrad update is not built for QR embedding tables; use SGD, or set "
+                       "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("adagrad", "md"): "ERROR: the fused exact Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
+                       "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("rwsadagrad", "qr"): "ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
+                          "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("rwsadagrad", "md"): "ERROR: the fused row-wise Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
+                          "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("coo", "bf16"): "ERROR: bfloat16 embedding tables are updated by the fused kernels only: plain SGD (no momentum, no weight "
+                     "decay) or row-wise Adagrad; this optimizer needs the sparse COO gradient",
+    ("unfused", "bf16"): "ERROR: bfloat16 embedding tables need the fused embedding update (fused_emb_update = False materialises sparse "
+                         "fp32 COO gradients for a torch optimizer, which would round on every add)",
+}
 
 
 class DLRM_Net(nn.Module):
@@ -730,11 +751,9 @@ class DLRM_Net(nn.Module):
             projs = [e.proj_weight() if isinstance(e, PrEmbeddingBagHolder) else None for e in emb_l]
             spec = (self._md_base(emb_l), [p is not None for p in projs], torch.is_grad_enabled())
             return MDEmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, spec, *ws, *[p for p in projs if p is not None])
-        if self.emb_bf16 is not None:
-            if isinstance(v_W_l, nn.ParameterList) or any(isinstance(w, nn.Parameter) for w in (v_W_l or []) if w is not None):
-                sys.exit("ERROR: bfloat16 embedding tables with learned pooling weights are not supported (the pooling-weight gradient "
-                         "kernel reads fp32 rows); use --weighted-pooling=fixed")
-            return BF16EmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, *ws, *self._pool_weights(v_W_l, ws[0].device))
+        if self.emb_bf16 is not None and (isinstance(v_W_l, nn.ParameterList) or any(isinstance(w, nn.Parameter) for w in (v_W_l or []) if w is not None)):
+            sys.exit("ERROR: bfloat16 embedding tables with learned pooling weights are not supported (the pooling-weight gradient "
+                     "kernel reads fp32 rows); use --weighted-pooling=fixed")
         return EmbeddingBagsFunction.apply(self._stash_embedding_grad, bags, out_slot, *ws, *self._pool_weights(v_W_l, ws[0].device))
 
     def apply_emb(self, lS_o, lS_i, emb_l, v_W_l):
@@ -823,8 +842,7 @@ class DLRM_Net(nn.Module):
             sys.exit("ERROR: bfloat16 embedding tables with learned pooling weights are not supported (the pooling-weight gradient "
                      "kernel reads fp32 rows); use --weighted-pooling=fixed")
         if not self.fused_emb_update:
-            sys.exit("ERROR: bfloat16 embedding tables need the fused embedding update (fused_emb_update = False materialises sparse "
-                     "fp32 COO gradients for a torch optimizer, which would round on every add)")
+            sys.exit(UPDATE_REFUSALS["unfused", "bf16"])
         if ext_dist.is_distributed():
             sys.exit("ERROR: bfloat16 embedding tables are single-process only (the table-sharded distributed forward is not built for them)")
 
@@ -860,12 +878,29 @@ class DLRM_Net(nn.Module):
         self._bf16_update_calls = n + 1
         return _mix_seed(self.emb_bf16[1], n)
 
-    def _sgd_update(self, weights, bags, dout, lr) -> None:
-        """the fused backward + SGD step of one parked backward pass: the fp32 kernels, or the bf16 ones for bfloat16 tables"""
+    def _run_update(self, plan, weights, bags, dout) -> None:
+        """The ONE place that maps an update plan — ("sgd", lr), ("rwsadagrad", clr, eps, states) or ("adagrad", clr, eps, sums), as
+        _embedding_update_plan builds them — to the fused backward + update kernel of one backward pass: the fp32 kernels, or the bf16 ones
+        (this model's rounding, one seed of its counter per call) for bfloat16 tables.  What no kernel is built for was refused before
+        (UPDATE_REFUSALS)."""
+        kind = plan[0]
         if self.emb_bf16 is not None:
-            ops.emb_bwd_sgd_bf16(weights, bags, dout, lr, self.emb_bf16[0], self._bf16_next_seed())
+            if kind == "sgd":
+                ops.emb_bwd_sgd_bf16(weights, bags, dout, plan[1], self.emb_bf16[0], self._bf16_next_seed())
+            else:
+                ops.emb_bwd_rowwise_adagrad_bf16(weights, plan[3], bags, dout, plan[1], plan[2], self.emb_bf16[0], self._bf16_next_seed())
+        elif kind == "sgd":
+            ops.emb_bwd_sgd(weights, bags, dout, plan[1], self.emb_update_mode)
+        elif kind == "rwsadagrad":
+            ops.emb_bwd_rowwise_adagrad(weights, plan[3], bags, dout, plan[1], plan[2])
         else:
-            ops.emb_bwd_sgd(weights, bags, dout, lr, self.emb_update_mode)
+            ops.emb_bwd_adagrad(weights, plan[3], bags, dout, plan[1], plan[2])
+
+    def _refuse_update(self, update: str) -> None:
+        """exit with the message of UPDATE_REFUSALS if `update` is not built for this model's tables"""
+        msg = UPDATE_REFUSALS.get((update, self._table_kind()))
+        if msg is not None:
+            sys.exit(msg)
 
     def quantize_mlp(self, bits):
         """The reference's `torch.quantization.quantize_dynamic(dlrm, {torch.nn.Linear}, qint8 | float16)` of --quantize-mlp-with-bit 8 | 16
@@ -949,44 +984,46 @@ class DLRM_Net(nn.Module):
             return None
         return ops.emb_presort(weights, bags, plan[1], pred)
 
+    @contextlib.contextmanager
+    def _on_side_stream(self, device, keep, always_wait=False):
+        """What is launched inside runs on the device's side stream, after everything the current stream holds now; `keep`, the tensors those
+        launches read, stay alive until the join (_join_side_stream).  A backward node whose forward ran on the side stream is on it already
+        and waits for nothing (always_wait: the caller is never on it)."""
+        cur, side = torch.cuda.current_stream(device), _side_stream(device)
+        if always_wait or cur != side:           # (cur != side in a backward node: distributed forward, the lookups ran on the main stream)
+            ops.timer_mark()
+            side.wait_stream(cur)
+        self._side_keep += keep
+        with torch.cuda.stream(side):
+            yield
+
     def _stash_embedding_grad(self, weights, bags, dout, presorted=None):
+        # (overlap mode: the optimizer that owns the tables, once known from its earlier steps)
+        bound = self._bound_optimizer() if (self.overlap_streams and self._bound_optimizer is not None) else None
         if presorted is not None:
             # the fused backward already applied the single-lookup rows with presorted.lr; the rest follows from the same sorted workspace —
             # on the side stream now (overlap mode) or when the optimizer steps
-            if self.overlap_streams and self._bound_optimizer is not None and self._bound_optimizer() is not None:
-                cur, side = torch.cuda.current_stream(dout.device), _side_stream(dout.device)
-                if cur != side:
-                    ops.timer_mark()
-                    side.wait_stream(cur)
-                with torch.cuda.stream(side):
+            if bound is not None:
+                with self._on_side_stream(dout.device, [dout, presorted.ws, presorted.mask] + bags.keep):
                     ops.emb_bwd_sgd_presorted(weights, bags, dout, presorted)
-                self._side_keep += [dout, presorted.ws, presorted.mask] + bags.keep
-                return
-            self._pending_emb.append((weights, bags, dout, presorted))
+            else:
+                self._pending_emb.append(ParkedGrad(weights, bags, dout, presorted))
             return
         if not self.fused_emb_update:
-            if self.emb_bf16 is not None:
-                sys.exit("ERROR: bfloat16 embedding tables need the fused embedding update (fused_emb_update = False materialises sparse "
-                         "fp32 COO gradients for a torch optimizer, which would round on every add)")
+            self._refuse_update("unfused")
             self._materialize_coo_grads(weights, bags, dout)
             return
-        opt = self._bound_optimizer() if (self.overlap_streams and self._bound_optimizer is not None) else None
-        if opt is not None and not self._pending_emb:
-            # overlap mode, optimizer known from its earlier steps: the sparse SGD update is launched NOW — this backward
-            # node runs on the side stream its forward ran on, so the update overlaps the bottom-MLP backward that autograd
-            # runs next on the main stream — with the learning rate the optimizer holds at this moment (the reference reads
-            # it at step(), a few microseconds later in the same loop body: dlrm_s_pytorch.py:1611-1621)
-            plan = _embedding_update_plan(opt, weights) if _is_plain_sgd(opt) else None     # (the Adagrad plan advances state["step"]: only built where it is applied)
+        if bound is not None and not self._pending_emb:
+            # the sparse SGD update is launched NOW — this backward node runs on the side stream its forward ran on, so the update
+            # overlaps the bottom-MLP backward that autograd runs next on the main stream — with the learning rate the optimizer
+            # holds at this moment (the reference reads it at step(), a few microseconds later in the same loop body:
+            # dlrm_s_pytorch.py:1611-1621)
+            plan = _embedding_update_plan(bound, weights) if _is_plain_sgd(bound) else None     # (the Adagrad plan advances state["step"]: only built where it is applied)
             if plan is not None and plan[0] == "sgd":
-                cur, side = torch.cuda.current_stream(dout.device), _side_stream(dout.device)
-                if cur != side:                      # (distributed forward: the lookups ran on the main stream)
-                    ops.timer_mark()
-                    side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    self._sgd_update(weights, bags, dout, plan[1])
-                self._side_keep += [dout] + bags.keep
+                with self._on_side_stream(dout.device, [dout] + bags.keep):
+                    self._run_update(plan, weights, bags, dout)
                 return
-        self._pending_emb.append((weights, bags, dout, None))
+        self._pending_emb.append(ParkedGrad(weights, bags, dout))
         if len(self._pending_emb) == 65:
             print("WARNING: dlrm_amd: 65 embedding gradients are parked and no optimizer that owns the tables has stepped; "
                   "every backward() keeps its [B, T*D] gradient buffer alive until then", file=sys.stderr)
@@ -1010,69 +1047,42 @@ class DLRM_Net(nn.Module):
         """Launch the fused backward+update for every stashed embedding gradient: sparse SGD for torch.optim.SGD,
         row-wise sparse Adagrad for RWSAdagrad (the reference's optim/rwsadagrad.py or dlrm_amd.optim.FusedRWSAdagrad)."""
         pending, self._pending_emb = self._pending_emb, []
-        side = None
-        if self.overlap_streams and pending and pending[0][2].is_cuda:
+        if self.overlap_streams and pending and pending[0].dout.is_cuda:
             # launched from the step pre-hook: on the side stream, beside the dense optimizer step (joined in the post-hook)
-            dev = pending[0][2].device
-            side = _side_stream(dev)
-            ops.timer_mark()
-            side.wait_stream(torch.cuda.current_stream(dev))
-            self._side_keep += [p_[2] for p_ in pending] + [t for p_ in pending for t in p_[1].keep]
-            self._side_keep += [t for p_ in pending if len(p_) > 3 and p_[3] is not None for t in (p_[3].ws, p_[3].mask)]
-            if optimizer is not None and self._bound_optimizer is None and self._owned_by(optimizer):
-                self._bound_optimizer = weakref.ref(optimizer)
-        with torch.cuda.stream(side) if side is not None else _NullCtx():
+            keep = [p_.dout for p_ in pending] + [t for p_ in pending for t in p_.bags.keep]
+            keep += [t for p_ in pending if p_.presorted is not None for t in (p_.presorted.ws, p_.presorted.mask)]
+            with self._on_side_stream(pending[0].dout.device, keep, always_wait=True):
+                if optimizer is not None and self._bound_optimizer is None and self._owned_by(optimizer):
+                    self._bound_optimizer = weakref.ref(optimizer)
+                self._apply_pending(pending, optimizer, lr)
+        else:
             self._apply_pending(pending, optimizer, lr)
 
     def _apply_pending(self, pending, optimizer, lr):
-        for entry in pending:
-            weights, bags, dout = entry[:3]
-            pre = entry[3] if len(entry) > 3 else None        # ops.Presorted: the backward pass already took the single-lookup rows
+        pending = [ParkedGrad(*entry) for entry in pending]
+        for weights, bags, dout, pre in pending:
             if pre is not None:
-                # (the single-lookup rows were updated in backward with pre.lr — the optimizer's lr then; the rest takes the same step size)
+                # (the backward pass already took the single-lookup rows with pre.lr — the optimizer's lr then; the rest takes the same step size)
                 ops.emb_bwd_sgd_presorted(weights, bags, dout, pre)
                 continue
             if lr is not None:
-                self._sgd_update(weights, bags, dout, lr)
+                self._run_update(("sgd", lr), weights, bags, dout)
                 continue
             # parked backward passes over THESE tables (`weights` is a fresh tuple per forward call: compare the tables themselves)
             key = tuple(id(w) for w in weights)
             if _is_exact_adagrad(optimizer, self.fused_adagrad) and self._owned_by(optimizer):
-                # (asked in front of the plan, which advances state["step"])
-                if self.emb_bf16 is not None:
-                    sys.exit("ERROR: the fused exact Adagrad update is not built for bfloat16 embedding tables; use SGD or row-wise Adagrad")
-                if self._has_qr(self.emb_l):
-                    sys.exit("ERROR: the fused exact Adagrad update is not built for QR embedding tables; use SGD, or set "
-                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
-                if self._has_md(self.emb_l):
-                    sys.exit("ERROR: the fused exact Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
-                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
-            plan = _embedding_update_plan(optimizer, weights, count=sum(1 for p_ in pending if tuple(id(w) for w in p_[0]) == key),
+                self._refuse_update("adagrad")                    # (asked in front of the plan, which advances state["step"])
+            plan = _embedding_update_plan(optimizer, weights, count=sum(1 for p_ in pending if tuple(id(w) for w in p_.weights) == key),
                                           fused_adagrad=self.fused_adagrad)
             if plan is None:
-                self._pending_emb.append((weights, bags, dout, None))   # another optimizer owns these tables
-            elif plan[0] == "coo":
-                if self.emb_bf16 is not None:
-                    sys.exit("ERROR: bfloat16 embedding tables are updated by the fused kernels only: plain SGD (no momentum, no weight "
-                             "decay) or row-wise Adagrad; this optimizer needs the sparse COO gradient")
+                self._pending_emb.append(ParkedGrad(weights, bags, dout))   # another optimizer owns these tables
+                continue
+            if plan[0] != "sgd":                                  # (nothing refuses plain SGD: the per-step path does not ask)
+                self._refuse_update(plan[0])
+            if plan[0] == "coo":
                 self._materialize_coo_grads(weights, bags, dout)  # the optimizer's own step consumes .grad right after this hook
-            elif plan[0] == "sgd":
-                self._sgd_update(weights, bags, dout, plan[1])
-            elif plan[0] == "adagrad":
-                _, clr, eps, sums = plan
-                ops.emb_bwd_adagrad(weights, sums, bags, dout, clr, eps)
             else:
-                if self._has_qr(self.emb_l):
-                    sys.exit("ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
-                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
-                if self._has_md(self.emb_l):
-                    sys.exit("ERROR: the fused row-wise Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
-                             "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer")
-                _, clr, eps, states = plan
-                if self.emb_bf16 is not None:
-                    ops.emb_bwd_rowwise_adagrad_bf16(weights, states, bags, dout, clr, eps, self.emb_bf16[0], self._bf16_next_seed())
-                else:
-                    ops.emb_bwd_rowwise_adagrad(weights, states, bags, dout, clr, eps)
+                self._run_update(plan, weights, bags, dout)
 
     # ---------------------------------------------------------------- forward paths
     def forward(self, dense_x, lS_o, lS_i):

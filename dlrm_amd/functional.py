@@ -591,7 +591,9 @@ def _qr_tables(vweights, collisions):
 class EmbeddingBagsFunction(Function):
     """All T EmbeddingBag(sum) lookups in one kernel launch; the backward pass does NOT materialise a
     gradient: it hands (bags, d_out) to `sink`, which applies the fused sparse update when the
-    optimizer steps.  Reference: DLRM_Net.apply_emb (dlrm_s_pytorch.py:407-462)."""
+    optimizer steps.  Reference: DLRM_Net.apply_emb (dlrm_s_pytorch.py:407-462).
+    Tables all fp32, or all torch.bfloat16 (DLRM_Net.embedding_bfloat16: dlrm_emb_fwd_bf16 pools them into the fp32 feature buffer — the bits
+    of the fp32 lookup on the upcast tables; the model routes what backward hands to `sink` to the bf16 update kernels)."""
 
     @staticmethod
     def forward(ctx, sink, bags, out_slot, *tensors):
@@ -601,10 +603,14 @@ class EmbeddingBagsFunction(Function):
         T = bags.T
         weights, vws = tensors[:T], tensors[T:]
         D = weights[0].size(1)
+        bf16 = weights[0].dtype == torch.bfloat16          # (a mixture is refused by the lookup's table description)
         if vws:
+            if bf16 and any(v.requires_grad for v in vws):
+                # (the gradient kernel of learned vectors reads fp32 rows; the model refuses them before it gets here)
+                raise RuntimeError("dlrm_amd: learned pooling weights are not built for bfloat16 embedding tables")
             ops.pool_weights_gather(vws, bags)
-        out = out_slot.get() if out_slot is not None else alloc2d(bags.B, T * D, weights[0])
-        ops.emb_fwd(weights, bags, out)
+        out = out_slot.get() if out_slot is not None else alloc2d(bags.B, T * D, weights[0])        # (fp32, on the tables' device)
+        (ops.emb_fwd_bf16 if bf16 else ops.emb_fwd)(weights, bags, out)
         ctx.sink = sink
         ctx.bags = bags
         ctx.weights = weights  # parameters (leaves) — kept by reference, not via save_for_backward
@@ -621,37 +627,6 @@ class EmbeddingBagsFunction(Function):
             dvw = tuple(ops.emb_psw_grad(ctx.weights, ctx.bags, dout, ctx.vws))    # before the update touches the tables
         ctx.sink(ctx.weights, ctx.bags, dout)
         return (None, None, None) + (None,) * len(ctx.weights) + dvw
-
-
-class BF16EmbeddingBagsFunction(Function):
-    """EmbeddingBagsFunction over torch.bfloat16 tables (DLRM_Net.embedding_bfloat16): one dlrm_emb_fwd_bf16 launch pools every table into
-    the fp32 feature buffer — the bits of EmbeddingBagsFunction on the tables upcast to fp32.  Backward hands (weights, bags, d_out) to the
-    same `sink`; the model routes them to the bf16 update kernels when the optimizer steps.  Pooling weights: fixed vectors only (the
-    gradient kernel of learned ones reads fp32 rows; the model refuses them before it gets here)."""
-
-    @staticmethod
-    def forward(ctx, sink, bags, out_slot, *tensors):
-        T = bags.T
-        weights, vws = tensors[:T], tensors[T:]
-        D = weights[0].size(1)
-        if vws:
-            if any(v.requires_grad for v in vws):
-                raise RuntimeError("dlrm_amd: learned pooling weights are not built for bfloat16 embedding tables")
-            ops.pool_weights_gather(vws, bags)
-        out = out_slot.get() if out_slot is not None else alloc2d(bags.B, T * D, weights[0])        # (fp32, on the tables' device)
-        ops.emb_fwd_bf16(weights, bags, out)
-        ctx.sink = sink
-        ctx.bags = bags
-        ctx.weights = weights  # parameters (leaves) — kept by reference, not via save_for_backward
-        ctx.n_vws = len(vws)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.sink is None:
-            raise RuntimeError(_NO_SINK)
-        ctx.sink(ctx.weights, ctx.bags, _rowmajor(dout))
-        return (None, None, None) + (None,) * (len(ctx.weights) + ctx.n_vws)
 
 
 class QREmbeddingBagsFunction(Function):

@@ -332,23 +332,7 @@ def _pred_args(pred, stream: C.c_void_p):
 
 def emb_fwd(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor, pred=None) -> torch.Tensor:
     """out[b, t*D:(t+1)*D] = sum-pooled bag (t, b).  `out` is a [B, >= T*D] view (row stride free).  pred: see _pred_args."""
-    lib = _lib.load()
-    D, wp, rows = _weights_desc(weights)
-    _req(out, "out", ndim=2)
-    if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_fwd shape mismatch")
-    err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
-    st = _stream(out)
-    # (a predicated launch belongs to the step's fused lookup + interaction: same timing category, so the three launches are ONE run)
-    with _timed("emb_fwd" if pred is None else "emb_interact_fwd"):
-        if pred is None:
-            rc = lib.dlrm_emb_fwd(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                  bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, st)
-        else:
-            rc = lib.dlrm_emb_fwd_pred(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                       bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred, st), st)
-    _lib.check(rc, "dlrm_emb_fwd")
-    return out
+    return _pooled_lookup("fp32", (weights,), bags, out, pred)
 
 
 def quant_row_bytes(D: int, bits: int) -> int:
@@ -391,27 +375,15 @@ def _packed_tables_desc(qweights: Sequence[torch.Tensor], rows: Sequence[int], D
     return _lib.ptr_array([q.data_ptr() for q in qweights]), _lib.i64_array(rows)
 
 
+def _packed_rows_desc(qweights, rows, D, bits, T, what):
+    return (D,) + _packed_tables_desc(qweights, rows, D, bits, T, what)
+
+
 def emb_fwd_quant(qweights: Sequence[torch.Tensor], rows: Sequence[int], D: int, bits: int, bags: BagBatch, out: torch.Tensor,
                   pred=None) -> torch.Tensor:
     """emb_fwd over packed tables (emb_quantize): out[b, t*D:(t+1)*D] = sum_i psw_i * (scale_r * q_r + bias_r).  qweights[t] is the
     uint8 [rows[t], quant_row_bytes(D, bits)] tensor of table t; `out` is a [B, >= T*D] view (row stride free).  pred: see _pred_args."""
-    lib = _lib.load()
-    wp, rp = _packed_tables_desc(qweights, rows, D, bits, bags.T, "emb_fwd_quant")
-    _req(out, "out", ndim=2)
-    if out.size(0) != bags.B or out.size(1) < bags.T * D:
-        raise RuntimeError("dlrm_amd: emb_fwd_quant shape mismatch")
-    err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
-    st = _stream(out)
-    # (a predicated launch belongs to the forward's fused lookup + interaction, as in emb_fwd: one timing category for the three launches)
-    with _timed("emb_fwd_quant" if pred is None else "emb_interact_fwd_quant"):
-        if pred is None:
-            rc = lib.dlrm_emb_fwd_quant(bags.T, bags.B, D, bits, wp, rp, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
-                                        C.c_void_p(out.data_ptr()), _ld(out), err, st)
-        else:
-            rc = lib.dlrm_emb_fwd_quant_pred(bags.T, bags.B, D, bits, wp, rp, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
-                                             C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred, st), st)
-    _lib.check(rc, "dlrm_emb_fwd_quant")
-    return out
+    return _pooled_lookup("quant", (qweights, rows, D, bits, bags.T, "emb_fwd_quant"), bags, out, pred, (bits,))
 
 
 # ---- quotient-remainder (QR) tables: csrc/emb_qr.hip.  A table list is described by three parallel lists: `weights` (weight_q of a QR table,
@@ -789,24 +761,11 @@ def _lr_args(lr: LrLike):
     return float(lr), None
 
 
-def emb_bwd_sgd(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor, lr: LrLike,
-                mode: int = UPD_SORTED) -> None:
-    """Fused EmbeddingBag backward + sparse SGD: W_t[idx] -= lr * dout[bag, t*D:(t+1)*D] (in place)."""
-    lib = _lib.load()
-    D, wp, rows = _weights_desc(weights)
+def _check_dout(name: str, dout: torch.Tensor, bags: BagBatch, D: int, *per_table) -> None:
+    """what every sparse update refuses first: `dout` is a [B, >= T*D] buffer, and every list of `per_table` has one entry per table"""
     _req(dout, "dout", ndim=2)
-    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_bwd_sgd shape mismatch")
-    ws_ptr, ws_bytes = None, 0
-    if mode == UPD_SORTED:
-        ws = _scratch("emb", _emb_sort_bytes(lib, bags, rows), dout.device)
-        ws_ptr, ws_bytes = C.c_void_p(ws.data_ptr()), ws.numel()
-    lr_v, lr_p = _lr_args(lr)
-    with _timed("emb_bwd_sgd"):
-        rc = lib.dlrm_emb_bwd_sgd(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                  bags.idx_bits, C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, int(mode),
-                                  ws_ptr, ws_bytes, None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
-    _lib.check(rc, "dlrm_emb_bwd_sgd")
+    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or any(len(l) != bags.T for l in per_table):
+        raise RuntimeError("dlrm_amd: %s shape mismatch" % name)
 
 
 class Presorted:
@@ -846,9 +805,7 @@ def emb_bwd_sgd_presorted(weights: Sequence[torch.Tensor], bags: BagBatch, dout:
     (interact_bwd_gather(..., presorted=pre)) are left out — when the launch predicate it ran under holds."""
     lib = _lib.load()
     D, wp, rows = _weights_desc(weights)
-    _req(dout, "dout", ndim=2)
-    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_bwd_sgd_presorted shape mismatch")
+    _check_dout("emb_bwd_sgd_presorted", dout, bags, D, weights)
     lr_v, lr_p = _lr_args(pre.lr)
     st = _stream(dout)
     flag, nz = _pred_args(pre.pred, st) if pre.pred is not None else (None, 0)
@@ -856,64 +813,6 @@ def emb_bwd_sgd_presorted(weights: Sequence[torch.Tensor], bags: BagBatch, dout:
         rc = lib.dlrm_emb_bwd_sgd_presorted(bags.T, bags.B, D, wp, rows, bags._nnz, C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p,
                                             C.c_void_p(pre.ws.data_ptr()), pre.ws.numel(), int(bool(skip_singles)), flag, nz, st)
     _lib.check(rc, "dlrm_emb_bwd_sgd_presorted")
-
-
-def emb_bwd_rowwise_adagrad(weights: Sequence[torch.Tensor], states: Sequence[torch.Tensor], bags: BagBatch,
-                            dout: torch.Tensor, lr: LrLike, eps: float) -> None:
-    """Fused EmbeddingBag backward + row-wise sparse Adagrad (optim/rwsadagrad.py:117-143), in place:
-    per touched row r:  g_r = sum of its lookups' gradients;  states[t][r] += mean(g_r^2);
-    W_t[r] -= lr * g_r / (sqrt(states[t][r]) + eps).  `lr` is the decayed clr of rwsadagrad.py:115."""
-    lib = _lib.load()
-    D, wp, rows = _weights_desc(weights)
-    _req(dout, "dout", ndim=2)
-    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T or len(states) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_bwd_rowwise_adagrad shape mismatch")
-    for s_, w in zip(states, weights):
-        _req(s_, "adagrad state", ndim=1)
-        if s_.numel() != w.size(0) or not s_.is_contiguous():
-            raise RuntimeError("dlrm_amd: row-wise adagrad state must be a contiguous [rows] tensor")
-    sp = _lib.ptr_array([s_.data_ptr() for s_ in states])
-    need = lib.dlrm_emb_adagrad_workspace_bytes(bags.T, D, bags._nnz, rows)
-    if need < 0:
-        raise RuntimeError("dlrm_amd: dlrm_emb_adagrad_workspace_bytes failed")
-    ws = _scratch("emb", need, dout.device)
-    lr_v, lr_p = _lr_args(lr)
-    with _timed("emb_bwd_adagrad"):
-        rc = lib.dlrm_emb_bwd_rowwise_adagrad(bags.T, bags.B, D, wp, sp, rows, bags._idx, bags._off, bags._nnz,
-                                              bags._psw, bags.idx_bits, C.c_void_p(dout.data_ptr()), _ld(dout),
-                                              lr_v, lr_p, float(eps), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                              None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
-    _lib.check(rc, "dlrm_emb_bwd_rowwise_adagrad")
-
-
-def emb_bwd_adagrad(weights: Sequence[torch.Tensor], sums: Sequence[torch.Tensor], bags: BagBatch,
-                    dout: torch.Tensor, lr: LrLike, eps: float) -> None:
-    """Fused EmbeddingBag backward + exact sparse Adagrad (torch.optim.Adagrad's sparse branch, the reference's --optimizer=adagrad), in
-    place: per touched row r:  g_r = sum of its lookups' gradients (the order and bits of emb_bwd_rowwise_adagrad);
-    sums[t][r] += g_r^2;  W_t[r] -= lr * g_r / (sqrt(sums[t][r]) + eps), per element.  `sums[t]` is torch's state["sum"] of table t:
-    fp32, contiguous, the shape of the table.  `lr` is the decayed clr."""
-    lib = _lib.load()
-    D, wp, rows = _weights_desc(weights)
-    _req(dout, "dout", ndim=2)
-    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T or len(sums) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_bwd_adagrad shape mismatch")
-    for s_, w in zip(sums, weights):
-        # (the kernel writes sums[t][row, 0:D] for every looked-up row: any other layout is an out-of-bounds device write)
-        _req(s_, "adagrad sum", ndim=2)
-        if tuple(s_.shape) != tuple(w.shape) or not s_.is_contiguous() or s_.device != w.device:
-            raise RuntimeError("dlrm_amd: adagrad sum must be a contiguous [rows, D] tensor on its table's device")
-    sp = _lib.ptr_array([s_.data_ptr() for s_ in sums])
-    need = lib.dlrm_emb_adagrad_workspace_bytes(bags.T, D, bags._nnz, rows)
-    if need < 0:
-        raise RuntimeError("dlrm_amd: dlrm_emb_adagrad_workspace_bytes failed")
-    ws = _scratch("emb", need, dout.device)
-    lr_v, lr_p = _lr_args(lr)
-    with _timed("emb_bwd_adagrad"):
-        rc = lib.dlrm_emb_bwd_adagrad(bags.T, bags.B, D, wp, sp, rows, bags._idx, bags._off, bags._nnz,
-                                      bags._psw, bags.idx_bits, C.c_void_p(dout.data_ptr()), _ld(dout),
-                                      lr_v, lr_p, float(eps), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                      None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
-    _lib.check(rc, "dlrm_emb_bwd_adagrad")
 
 
 # ---- bfloat16 embedding tables: csrc/emb_bf16.hip.  Tables are torch.bfloat16 [rows, D]; the feature buffer, the gradient, the Adagrad
@@ -944,30 +843,141 @@ def _bf16_weights_desc(weights: Sequence[torch.Tensor]):
 def emb_fwd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, out: torch.Tensor, pred=None) -> torch.Tensor:
     """emb_fwd over torch.bfloat16 tables: out[b, t*D:(t+1)*D] = sum-pooled bag (t, b) in fp32, bit-identical to emb_fwd on the tables
     upcast to fp32.  `out` is an fp32 [B, >= T*D] view (row stride free).  pred: see _pred_args."""
+    return _pooled_lookup("bf16", (weights,), bags, out, pred)
+
+
+# ---- the pooled lookup of the two-kernel form.  The C calls of the plain tables of either dtype and of the packed ones share ONE argument list
+#     (T, B, D, [bits,] <the tables>, idx, off, nnz, psw, idx_bits, out, ld, err, [flag, nonzero,] stream)
+# so there is one wrapper (_pooled_lookup) over LOOKUP_KINDS, in the form of ROW_KINDS below: `tables` is the argument list of the kind's
+# descriptor, the entries hold finished strings, the descriptor is called without a frame in between.  emb_fwd_qr and emb_fwd_md are NOT kinds
+# of it: each has a `saved` buffer, a second table list (weight_r, the projections) and refusals of its own — folding them in would add
+# parameters to the wrapper, not remove code.
+class LookupKind(NamedTuple):
+    fwd: str                # the C symbols: unconditional, and behind a launch predicate (_pred_args)
+    fwd_pred: str
+    timer: str              # the timer categories: a predicated launch belongs to the step's fused lookup + interaction (one run with it)
+    timer_pred: str
+    desc: Callable          # desc(*tables) -> (D, then the ctypes arguments between `D, [bits]` and `idx`)
+
+
+LOOKUP_KINDS = {
+    "fp32": LookupKind("dlrm_emb_fwd", "dlrm_emb_fwd_pred", "emb_fwd", "emb_interact_fwd", _weights_desc),
+    "bf16": LookupKind("dlrm_emb_fwd_bf16", "dlrm_emb_fwd_bf16_pred", "emb_fwd_bf16", "emb_interact_fwd_bf16", _bf16_weights_desc),
+    "quant": LookupKind("dlrm_emb_fwd_quant", "dlrm_emb_fwd_quant_pred", "emb_fwd_quant", "emb_interact_fwd_quant", _packed_rows_desc),
+}
+
+
+def _pooled_lookup(kind: str, tables, bags: BagBatch, out: torch.Tensor, pred, lead=()) -> torch.Tensor:
+    """out[b, t*D:(t+1)*D] = sum-pooled bag (t, b) of the tables of `kind`.  lead: the scalars behind D (packed: bits)."""
+    k = LOOKUP_KINDS[kind]
     lib = _lib.load()
-    D, wp, rows = _bf16_weights_desc(weights)
+    d = k.desc(*tables)
+    D = d[0]
     _req(out, "out", ndim=2)
-    if out.size(0) != bags.B or out.size(1) < bags.T * D or len(weights) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_fwd_bf16 shape mismatch")
+    if out.size(0) != bags.B or out.size(1) < bags.T * D or len(tables[0]) != bags.T:
+        raise RuntimeError("dlrm_amd: %s shape mismatch" % k.fwd[5:])
     err = None if bags.ignore_oob else C.c_void_p(_err_block(out.device).data_ptr())
     st = _stream(out)
-    # (a predicated launch belongs to the step's fused lookup + interaction: same timing category, as emb_fwd)
-    with _timed("emb_fwd_bf16" if pred is None else "emb_interact_fwd_bf16"):
-        if pred is None:
-            rc = lib.dlrm_emb_fwd_bf16(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                       bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, st)
-        else:
-            rc = lib.dlrm_emb_fwd_bf16_pred(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                            bags.idx_bits, C.c_void_p(out.data_ptr()), _ld(out), err, *_pred_args(pred, st), st)
-    _lib.check(rc, "dlrm_emb_fwd_bf16")
+    fn, timer, tail = (k.fwd, k.timer, (st,)) if pred is None else (k.fwd_pred, k.timer_pred, (*_pred_args(pred, st), st))
+    with _timed(timer):
+        rc = getattr(lib, fn)(bags.T, bags.B, D, *lead, *d[1:], bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
+                              C.c_void_p(out.data_ptr()), _ld(out), err, *tail)
+    _lib.check(rc, k.fwd)
     return out
 
 
-def _bf16_update_ws(lib, bags: BagBatch, D: int, rows, device):
-    need = lib.dlrm_emb_bwd_bf16_workspace_bytes(bags.T, D, bags._nnz, rows)
-    if need < 0:
-        raise RuntimeError("dlrm_amd: dlrm_emb_bwd_bf16_workspace_bytes failed")
-    return _scratch("emb", need, device)
+# ---- the sparse updates: fused EmbeddingBag backward + optimizer step, in place.  Below them is one device body (walk_update in
+# csrc/sorted_walk.h, which takes a row-update policy); their C calls share ONE argument list
+#     (T, B, D, tables, [states,] rows, idx, off, nnz, psw, idx_bits, dout, ld, lr, lr_dev, [eps,] [mode | rounding, seed, table0,] ws, ws_bytes, err, stream)
+# so there is one wrapper (_sparse_update) over UPDATE_KINDS, which holds what differs.  dlrm_emb_presort and dlrm_emb_bwd_sgd_presorted above
+# take other lists and keep their own calls.
+class UpdateKind(NamedTuple):
+    fn: str                 # the C symbol; without "dlrm_", the public wrapper's name in "<name> shape mismatch"
+    timer: str              # the timer category
+    desc: Callable          # _weights_desc | _bf16_weights_desc
+    ws: str                 # the C symbol that sizes the workspace
+    acc: Optional[str]      # the accumulators in `states`: None, "rows" ([rows] per table) or "table" (the table's shape)
+    eps: bool               # the extra scalars, in the order of the list above: eps;
+    mode: bool              # the UPD_* mode (only UPD_SORTED takes a workspace: that of the sort alone, sized without D);
+    rounding: bool          # rounding, seed, table0
+
+
+UPDATE_KINDS = {
+    "sgd": UpdateKind("dlrm_emb_bwd_sgd", "emb_bwd_sgd", _weights_desc, "dlrm_emb_bwd_workspace_bytes", None, False, True, False),
+    "rwsadagrad": UpdateKind("dlrm_emb_bwd_rowwise_adagrad", "emb_bwd_adagrad", _weights_desc, "dlrm_emb_adagrad_workspace_bytes", "rows",
+                             True, False, False),
+    "adagrad": UpdateKind("dlrm_emb_bwd_adagrad", "emb_bwd_adagrad", _weights_desc, "dlrm_emb_adagrad_workspace_bytes", "table",
+                          True, False, False),
+    "sgd_bf16": UpdateKind("dlrm_emb_bwd_sgd_bf16", "emb_bwd_sgd_bf16", _bf16_weights_desc, "dlrm_emb_bwd_bf16_workspace_bytes", None,
+                           False, False, True),
+    "rwsadagrad_bf16": UpdateKind("dlrm_emb_bwd_rowwise_adagrad_bf16", "emb_bwd_adagrad_bf16", _bf16_weights_desc,
+                                  "dlrm_emb_bwd_bf16_workspace_bytes", "rows", True, False, True),
+}
+
+
+def _sparse_update(kind: str, weights, bags: BagBatch, dout: torch.Tensor, lr: LrLike, states=None, eps=None, mode=None, rounding=None,
+                   seed: int = 0, table0: int = 0) -> None:
+    """the update of `kind` over one backward pass (the public wrappers below say what each computes); states: the accumulators, one per table"""
+    k = UPDATE_KINDS[kind]
+    lib = _lib.load()
+    D, wp, rows = k.desc(weights)
+    if k.acc is None:
+        _check_dout(k.fn[5:], dout, bags, D, weights)
+        tables = (wp,)
+    else:
+        _check_dout(k.fn[5:], dout, bags, D, weights, states)
+        for s_, w in zip(states, weights):
+            if k.acc == "rows":
+                _req(s_, "adagrad state", ndim=1)
+                if s_.numel() != w.size(0) or not s_.is_contiguous():
+                    raise RuntimeError("dlrm_amd: row-wise adagrad state must be a contiguous [rows] tensor")
+            else:
+                # (the kernel writes sums[t][row, 0:D] for every looked-up row: any other layout is an out-of-bounds device write)
+                _req(s_, "adagrad sum", ndim=2)
+                if tuple(s_.shape) != tuple(w.shape) or not s_.is_contiguous() or s_.device != w.device:
+                    raise RuntimeError("dlrm_amd: adagrad sum must be a contiguous [rows, D] tensor on its table's device")
+        tables = (wp, _lib.ptr_array([s_.data_ptr() for s_ in states]))
+    extra = (float(eps),) if k.eps else ()
+    if k.mode:
+        extra += (int(mode),)
+    if k.rounding:
+        extra += (_bf16_rounding(rounding), int(seed) & (2 ** 64 - 1), int(table0))
+    ws_ptr, ws_bytes = None, 0
+    if not k.mode or mode == UPD_SORTED:
+        need = getattr(lib, k.ws)(bags.T, bags._nnz, rows) if k.mode else getattr(lib, k.ws)(bags.T, D, bags._nnz, rows)
+        if need < 0:
+            raise RuntimeError("dlrm_amd: %s failed" % k.ws)
+        ws = _scratch("emb", need, dout.device)
+        ws_ptr, ws_bytes = C.c_void_p(ws.data_ptr()), ws.numel()
+    lr_v, lr_p = _lr_args(lr)
+    err = None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr())
+    with _timed(k.timer):
+        rc = getattr(lib, k.fn)(bags.T, bags.B, D, *tables, rows, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
+                                C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, *extra, ws_ptr, ws_bytes, err, _stream(dout))
+    _lib.check(rc, k.fn)
+
+
+def emb_bwd_sgd(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor, lr: LrLike,
+                mode: int = UPD_SORTED) -> None:
+    """Fused EmbeddingBag backward + sparse SGD: W_t[idx] -= lr * dout[bag, t*D:(t+1)*D] (in place)."""
+    _sparse_update("sgd", weights, bags, dout, lr, mode=mode)
+
+
+def emb_bwd_rowwise_adagrad(weights: Sequence[torch.Tensor], states: Sequence[torch.Tensor], bags: BagBatch,
+                            dout: torch.Tensor, lr: LrLike, eps: float) -> None:
+    """Fused EmbeddingBag backward + row-wise sparse Adagrad (optim/rwsadagrad.py:117-143), in place:
+    per touched row r:  g_r = sum of its lookups' gradients;  states[t][r] += mean(g_r^2);
+    W_t[r] -= lr * g_r / (sqrt(states[t][r]) + eps).  `lr` is the decayed clr of rwsadagrad.py:115."""
+    _sparse_update("rwsadagrad", weights, bags, dout, lr, states, eps)
+
+
+def emb_bwd_adagrad(weights: Sequence[torch.Tensor], sums: Sequence[torch.Tensor], bags: BagBatch,
+                    dout: torch.Tensor, lr: LrLike, eps: float) -> None:
+    """Fused EmbeddingBag backward + exact sparse Adagrad (torch.optim.Adagrad's sparse branch, the reference's --optimizer=adagrad), in
+    place: per touched row r:  g_r = sum of its lookups' gradients (the order and bits of emb_bwd_rowwise_adagrad);
+    sums[t][r] += g_r^2;  W_t[r] -= lr * g_r / (sqrt(sums[t][r]) + eps), per element.  `sums[t]` is torch's state["sum"] of table t:
+    fp32, contiguous, the shape of the table.  `lr` is the decayed clr."""
+    _sparse_update("adagrad", weights, bags, dout, lr, sums, eps)
 
 
 def emb_bwd_sgd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor, lr: LrLike, rounding: str = "stochastic",
@@ -975,45 +985,14 @@ def emb_bwd_sgd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torc
     """Fused EmbeddingBag backward + sparse SGD over torch.bfloat16 tables, in place: per touched row r, g_r = the fp32 sum of its lookups'
     gradients (sorted walk, deterministic), W[r] = round(fmaf(-lr, g_r, float(W[r]))) — one rounding per row per call.  table0: index of
     weights[0] in the caller's full table list (the random stream of a table does not depend on how the list is cut into calls)."""
-    lib = _lib.load()
-    D, wp, rows = _bf16_weights_desc(weights)
-    _req(dout, "dout", ndim=2)
-    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_bwd_sgd_bf16 shape mismatch")
-    mode = _bf16_rounding(rounding)
-    ws = _bf16_update_ws(lib, bags, D, rows, dout.device)
-    lr_v, lr_p = _lr_args(lr)
-    with _timed("emb_bwd_sgd_bf16"):
-        rc = lib.dlrm_emb_bwd_sgd_bf16(bags.T, bags.B, D, wp, rows, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
-                                       C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, mode, int(seed) & (2 ** 64 - 1), int(table0),
-                                       C.c_void_p(ws.data_ptr()), ws.numel(),
-                                       None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
-    _lib.check(rc, "dlrm_emb_bwd_sgd_bf16")
+    _sparse_update("sgd_bf16", weights, bags, dout, lr, rounding=rounding, seed=seed, table0=table0)
 
 
 def emb_bwd_rowwise_adagrad_bf16(weights: Sequence[torch.Tensor], states: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor,
                                  lr: LrLike, eps: float, rounding: str = "stochastic", seed: int = 0, table0: int = 0) -> None:
     """emb_bwd_rowwise_adagrad over torch.bfloat16 tables, in place.  `states` stay fp32 and receive the bits emb_bwd_rowwise_adagrad gives
     them on the upcast tables; W[r] = round(fmaf(-lr, g_r / (sqrt(states[t][r]) + eps), float(W[r]))), one rounding per row per call."""
-    lib = _lib.load()
-    D, wp, rows = _bf16_weights_desc(weights)
-    _req(dout, "dout", ndim=2)
-    if dout.size(0) != bags.B or dout.size(1) < bags.T * D or len(weights) != bags.T or len(states) != bags.T:
-        raise RuntimeError("dlrm_amd: emb_bwd_rowwise_adagrad_bf16 shape mismatch")
-    for s_, w in zip(states, weights):
-        _req(s_, "adagrad state", ndim=1)
-        if s_.numel() != w.size(0) or not s_.is_contiguous():
-            raise RuntimeError("dlrm_amd: row-wise adagrad state must be a contiguous [rows] tensor")
-    mode = _bf16_rounding(rounding)
-    sp = _lib.ptr_array([s_.data_ptr() for s_ in states])
-    ws = _bf16_update_ws(lib, bags, D, rows, dout.device)
-    lr_v, lr_p = _lr_args(lr)
-    with _timed("emb_bwd_adagrad_bf16"):
-        rc = lib.dlrm_emb_bwd_rowwise_adagrad_bf16(bags.T, bags.B, D, wp, sp, rows, bags._idx, bags._off, bags._nnz, bags._psw,
-                                                   bags.idx_bits, C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, float(eps), mode,
-                                                   int(seed) & (2 ** 64 - 1), int(table0), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                   None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr()), _stream(dout))
-    _lib.check(rc, "dlrm_emb_bwd_rowwise_adagrad_bf16")
+    _sparse_update("rwsadagrad_bf16", weights, bags, dout, lr, states, eps, None, rounding, seed, table0)
 
 
 def emb_bwd_coo(bags: BagBatch, dout: torch.Tensor, D: int) -> List[torch.Tensor]:
@@ -1144,10 +1123,6 @@ def _gather_tables_bf16(weights: Sequence[torch.Tensor], what: str) -> bool:
 # path: the entries hold finished strings and the descriptors are called without a frame in between.
 def _qr_rows_desc(weights, weights_r, rows, collisions, op):
     return _qr_desc(weights, weights_r, rows, collisions) + (_qr_op(op),)
-
-
-def _packed_rows_desc(qweights, rows, D, bits, T, what):
-    return (D,) + _packed_tables_desc(qweights, rows, D, bits, T, what)
 
 
 class RowKind(NamedTuple):

@@ -1192,6 +1192,65 @@ def test_at_most_one_gather_ok_answers_for_a_table_kind_and_shape():
                 assert n == (D in (16, 32, 64) and F <= _NARROW_MAXF), (kind, D, F)
 
 
+# the seven refusals of the sparse embedding update, as the source held them (seven separate sys.exit blocks) before they became one table
+_UPDATE_REFUSALS = {
+    ("adagrad", "bf16"): "ERROR: the fused exact Adagrad update is not built for bfloat16 embedding tables; use SGD or row-wise Adagrad",
+    ("adagrad", "qr"): "ERROR: the fused exact Adagrad update is not built for QR embedding tables; use SGD, or set "
+                       "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("adagrad", "md"): "ERROR: the fused exact Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
+                       "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("rwsadagrad", "qr"): "ERROR: the fused row-wise Adagrad update is not built for QR embedding tables; use SGD, or set "
+                          "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("rwsadagrad", "md"): "ERROR: the fused row-wise Adagrad update is not built for mixed-dimension embedding tables; use SGD, or set "
+                          "model.fused_emb_update = False (DLRM_FUSED_EMB_UPDATE=0) with a torch optimizer",
+    ("coo", "bf16"): "ERROR: bfloat16 embedding tables are updated by the fused kernels only: plain SGD (no momentum, no weight "
+                     "decay) or row-wise Adagrad; this optimizer needs the sparse COO gradient",
+    ("unfused", "bf16"): "ERROR: bfloat16 embedding tables need the fused embedding update (fused_emb_update = False materialises sparse "
+                         "fp32 COO gradients for a torch optimizer, which would round on every add)",
+}
+
+
+def test_update_refusal_table_answers_every_pair_with_the_recorded_strings():
+    """(update kind, table kind) -> the exact message, or no refusal: every pair, through the one function that reads the table"""
+    import dlrm_amd
+    from dlrm_amd import dlrm_net
+    assert dlrm_net.UPDATE_REFUSALS == _UPDATE_REFUSALS
+    shell = dlrm_amd.DLRM_Net()
+    for update in ("sgd", "rwsadagrad", "adagrad", "coo", "unfused"):
+        for tables in ("fp32", "bf16", "qr", "md", "quant"):
+            shell._table_kind = lambda tables=tables: tables
+            want = _UPDATE_REFUSALS.get((update, tables))
+            if want is None:
+                shell._refuse_update(update)
+            else:
+                with pytest.raises(SystemExit) as e:
+                    shell._refuse_update(update)
+                assert e.value.code == want, (update, tables)
+
+
+def test_table_kind_names_the_tables_the_refusals_are_keyed_by():
+    import dlrm_amd
+    np.random.seed(5)
+    args = (np.asarray([300, 3, 40]), np.asarray([13, 8]), np.asarray([8 + 6, 1]), "dot")
+    kw = dict(sigmoid_top=0, loss_function="bce")
+    assert dlrm_amd.DLRM_Net(8, *args, **kw)._table_kind() == "fp32"
+    assert dlrm_amd.DLRM_Net(8, *args, qr_flag=True, qr_operation="mult", qr_collisions=4, qr_threshold=200, **kw)._table_kind() == "qr"
+    assert dlrm_amd.DLRM_Net([2, 8, 4], *args, md_flag=True, md_threshold=2, **kw)._table_kind() == "md"
+    bf16 = dlrm_amd.DLRM_Net(8, *args, **kw)
+    bf16.embedding_bfloat16("nearest")
+    assert bf16._table_kind() == "bf16"
+
+
+def test_parked_grad_accepts_the_three_and_the_four_element_form():
+    from dlrm_amd.dlrm_net import ParkedGrad
+    w, bags, dout, pre = (object(),), object(), object(), object()
+    assert ParkedGrad(*(w, bags, dout)) == (w, bags, dout, None) and ParkedGrad(*(w, bags, dout)).presorted is None
+    p = ParkedGrad(*(w, bags, dout, pre))
+    assert (p.weights, p.bags, p.dout, p.presorted) == (w, bags, dout, pre) and len(p) == 4
+    with pytest.raises(TypeError):
+        ParkedGrad(*(w, bags))
+
+
 if __name__ == "__main__":
     # python tests/test_host_logic.py --record FILE [--traces DIR]: write the fixture of test_mlp_call_trace_equals_the_recorded_one from
     # the dlrm_amd package of THIS checkout (and, with --traces, every case's full trace as text)
