@@ -146,12 +146,18 @@ int dlrm_gemv_bwd_weight(int64_t M, int K, const float* dY, int64_t lddy, const 
 int dlrm_gemv_bwd_fused(int64_t M, int K, const float* dY, int64_t lddy, const float* Yout, int64_t ldy, int act_out, const float* X,
                         int64_t ldx, const float* w, int xact_kind, float* dX, int64_t lddx, float* dW, float* dbias, int accumulate,
                         void* workspace, int64_t workspace_bytes, hipStream_t st);
+// "would the call above handle it": the calls' own pre-checks, pure host code (no launch, pointers inspected for alignment only)
+bool dlrm_gemv_fwd_handles(int K, const float* X, int64_t ldx, const float* w);
+bool dlrm_gemv_bwd_data_handles(int K, const float* w, const float* Xact, int64_t ldxa, const float* dX, int64_t lddx);
+bool dlrm_gemv_bwd_weight_handles(int64_t M, int K, const float* X, int64_t ldx, const void* workspace, int64_t workspace_bytes);
 
 // smallk.hip: weight gradient of layers with K <= 16 (the first bottom-MLP layer: 13 dense features padded to 16)
 int64_t dlrm_smallk_bwd_weight_workspace_bytes(int64_t M, int N, int K);
 int dlrm_smallk_bwd_weight(int64_t M, int N, int K, int K_store, const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW,
                            int64_t lddw, float* dbias, int accumulate, void* workspace, int64_t workspace_bytes,
                            hipStream_t st);
+bool dlrm_smallk_bwd_weight_handles(int64_t M, int N, int K, const float* dY, int64_t lddy, const float* X, int64_t ldx,
+                                    const void* workspace, int64_t workspace_bytes);
 
 // gemm_bf16.hip: the bf16-shaped (256 x 256 x 64, four phases per k-tile) GEMM; 0 = handled, DLRM_GEMV_NOT_HANDLED = outside its preconditions
 int dlrm_gemm_bf16_phased(int64_t M, int N, int K, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const float* bias, int act,

@@ -1272,9 +1272,22 @@ static int gemm_path() {   // tuning builds, env DLRM_GEMM_PATH: 0 = auto (defau
     return v;
 }
 
+// THE DISPATCH, in two halves.  gemm_route decides which kernel instantiation a prepared GemmArgs runs — pure host arithmetic on sizes, pitches
+// and pointer ALIGNMENT (nothing is dereferenced, no HIP call, no device query) — and launch_route switches on that decision.  The entry
+// points run one after the other; the exported route queries (dlrm_linear_*_route, include/dlrm_hip.h) stop after the first half, so what a
+// query reports is what the call launches.  Fields a path does not have are 0.
+struct GemmRoute {
+    int path;                      // DLRM_PATH_* (dlrm_hip.h): gemm_f32_kernel, gemm3_kernel, gemv.hip, smallk.hip
+    int tm, tn, frag, epi, nst, arith, sched;      // gemm3_kernel's template arguments TM, TN, FRAG, EPI, NST, ARITH, SCHED
+    int splits; long long kchunk;  // k-slices (grid z) and the reduction length of each
+    int bits;                      // the GEMM kernel itself writes (forward) / reads (data gradient) the ReLU sign bits
+    int workspace, atomic;         // weight gradient: k-slices store slabs in the workspace / add into dW with fp32 atomics
+};
+
 template <bool A_KC, bool B_KC>
-static int launch_gemm(GemmArgs& g, int splits, hipStream_t st, int arith, bool* fast = nullptr) {
-    if (fast) *fast = false;
+static GemmRoute gemm_route(const GemmArgs& g, int splits, int arith) {
+    GemmRoute r = {};
+    r.path = DLRM_PATH_FALLBACK; r.splits = splits; r.kchunk = g.kchunk;
     // fast path preconditions: 16-byte vector access to both operands, every k-slice a multiple of 16
     const bool k16 = (g.K % BK3 == 0) && (g.kchunk % BK3 == 0);
     if (gemm_path() != 2 && g.vecA && g.vecB && k16 && g.lda % 4 == 0 && g.ldb % 4 == 0) {
@@ -1299,7 +1312,6 @@ static int launch_gemm(GemmArgs& g, int splits, hipStream_t st, int arith, bool*
         // DLRM_WGRAD_TM=2 -> 128-row weight-gradient tiles (three workgroups per CU; lost 20 % with scalar fragments).
         static const int frag = DLRM_TUNE_ENV("DLRM_GEMM_FRAG", 1), wgrad_tm = DLRM_TUNE_ENV("DLRM_WGRAD_TM", 0);
         if (splits > 1 && wgrad_tm == 2) big = false;
-        if (fast) *fast = true;
         // SMALL launches (Criteo-Kaggle: batch 2048): a 128 x 128 tiling leaves most CUs idle and every wave walks its k-loop alone at one
         // SIMD's MFMA rate (29 / 25 / 44 us per forward / data- / weight-gradient GEMM of ~0.5 GFLOP, profiles/round4/kaggle_kernels.md).
         // 64-row tiles (TM = 1) double the workgroups and halve each wave's MFMA chain.  fp32 MFMA only.
@@ -1307,10 +1319,9 @@ static int launch_gemm(GemmArgs& g, int splits, hipStream_t st, int arith, bool*
         const long long wg128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * splits;
         const bool small = small_tm && !big && arith == DLRM_ARITH_F32 && wg128 < 128 && force_tm == 0;
         // ... and 64 x 64 tiles (TN = 1 too) while even the 64 x 128 tiling has fewer workgroups than 3/4 of the CUs; that kernel neither writes
-        // nor reads sign bits: `fast` stays false so that dlrm_linear_fwd runs the stand-alone bit kernel, the data gradient takes its fp32 mask
+        // nor reads sign bits: the route's `bits` stays 0 so that dlrm_linear_fwd runs the stand-alone bit kernel, the data gradient takes its fp32 mask
         const long long wg64 = ((g.M + 63) / 64) * ((g.N + 127) / 128) * splits;
         const bool tiny = small && small_tm >= 2 && wg64 < 192 && (g.bits_in == nullptr || g.mask != nullptr);
-        if (tiny && fast) *fast = false;
         // fragment-read schedule (gemm3_kernel SCHED) of the native fp32 loop per kernel form: compile-time (-DDLRM_SCHED_FWD=.. etc., tools/build_variant_lib.sh)
         constexpr int FORM = (A_KC && B_KC) ? 0 : (A_KC ? 1 : 2);
         constexpr int SCHED_DEFAULT[3] = {DLRM_SCHED_FWD, DLRM_SCHED_DGRAD, DLRM_SCHED_WGRAD};
@@ -1327,19 +1338,49 @@ static int launch_gemm(GemmArgs& g, int splits, hipStream_t st, int arith, bool*
 #ifdef DLRM_TUNING
         static const int nst_all = DLRM_TUNE_ENV("DLRM_GEMM_NST", -1);
         const int nst = nst_all < 0 ? NST_DEFAULT[FORM] : (FORM == 0 ? nst_all / 100 : FORM == 1 ? (nst_all / 10) % 10 : nst_all % 10);
-#define GEMM3_LAUNCH2(FR, EP) (nst == 2 ? launch_gemm3<A_KC, B_KC, 2, 0, FR, 2, SD, EP, 2>(g, splits, st) : launch_gemm3<A_KC, B_KC, 2, 0, FR, 2, SD, EP, 3>(g, splits, st))
+#else
+        const int nst = NST_DEFAULT[FORM];
+#endif
+        // the template arguments launch_route instantiates, in its order: the k-strided forms' vector fragments first, then 64-row tiles, the
+        // two bf16 arithmetics (128- / 256-row tiles, general epilogue, three stages, SCHED 0), the native fp32 loop
+        r.path = DLRM_PATH_GEMM3; r.tn = 2; r.nst = 3;
+        r.frag = ((!A_KC || !B_KC) && arith == DLRM_ARITH_F32 && frag) ? 1 : 0;
+        if (tiny) { r.tm = 1; r.tn = 1; }
+        else if (small) r.tm = 1;
+        else if (arith == DLRM_ARITH_BF16X6 || arith == DLRM_ARITH_BF16) { r.tm = big ? 4 : 2; r.arith = arith == DLRM_ARITH_BF16X6 ? 1 : 2; }
+        else {
+            r.tm = big ? 4 : 2; r.sched = SD;
+            if (!big) r.nst = nst;
+            if (fast_epi) r.epi = (FORM == 0 && g.act == DLRM_ACT_RELU) ? 2 : 1;
+        }
+        r.bits = (r.tn == 2 && (g.bits_in != nullptr || g.bits_out != nullptr)) ? 1 : 0;
+    }
+    return r;
+}
+
+template <bool A_KC, bool B_KC>
+static int launch_route(GemmArgs& g, const GemmRoute& r, hipStream_t st) {
+    const int splits = r.splits;
+    if (r.path == DLRM_PATH_GEMM3) {
+        constexpr int FORM = (A_KC && B_KC) ? 0 : (A_KC ? 1 : 2);
+        constexpr int SCHED_DEFAULT[3] = {DLRM_SCHED_FWD, DLRM_SCHED_DGRAD, DLRM_SCHED_WGRAD};
+        constexpr int SD = SCHED_DEFAULT[FORM];
+        constexpr int NST_DEFAULT[3] = {DLRM_NST_FWD, DLRM_NST_DGRAD, DLRM_NST_WGRAD};
+        const bool big = r.tm == 4, small = r.tm == 1, tiny = r.tm == 1 && r.tn == 1;
+#ifdef DLRM_TUNING
+#define GEMM3_LAUNCH2(FR, EP) (r.nst == 2 ? launch_gemm3<A_KC, B_KC, 2, 0, FR, 2, SD, EP, 2>(g, splits, st) : launch_gemm3<A_KC, B_KC, 2, 0, FR, 2, SD, EP, 3>(g, splits, st))
 #else
 #define GEMM3_LAUNCH2(FR, EP) launch_gemm3<A_KC, B_KC, 2, 0, FR, 2, SD, EP, NST_DEFAULT[FORM]>(g, splits, st)
 #endif
 #define GEMM3_LAUNCH4(FR, EP) launch_gemm3<A_KC, B_KC, 4, 0, FR, 2, SD, EP>(g, splits, st)
 #define GEMM3_BIG_OR_NOT(FR)                                                                                   \
-        if (fast_epi) {                                                                                        \
-            if constexpr (FORM == 0) { if (g.act == DLRM_ACT_RELU) return big ? GEMM3_LAUNCH4(FR, 2) : GEMM3_LAUNCH2(FR, 2); } \
+        if (r.epi != 0) {                                                                                      \
+            if constexpr (FORM == 0) { if (r.epi == 2) return big ? GEMM3_LAUNCH4(FR, 2) : GEMM3_LAUNCH2(FR, 2); } \
             return big ? GEMM3_LAUNCH4(FR, 1) : GEMM3_LAUNCH2(FR, 1);                                          \
         }                                                                                                      \
         return big ? GEMM3_LAUNCH4(FR, 0) : GEMM3_LAUNCH2(FR, 0);
         if constexpr (!A_KC || !B_KC) {
-            if (arith == DLRM_ARITH_F32 && frag) {
+            if (r.arith == 0 && r.frag) {
                 if (tiny) return launch_gemm3<A_KC, B_KC, 1, 0, 1, 1>(g, splits, st);
                 if (small) return launch_gemm3<A_KC, B_KC, 1, 0, 1>(g, splits, st);
                 GEMM3_BIG_OR_NOT(1)
@@ -1347,9 +1388,9 @@ static int launch_gemm(GemmArgs& g, int splits, hipStream_t st, int arith, bool*
         }
         if (tiny) return launch_gemm3<A_KC, B_KC, 1, 0, 0, 1>(g, splits, st);
         if (small) return launch_gemm3<A_KC, B_KC, 1, 0>(g, splits, st);
-        if (arith == DLRM_ARITH_BF16X6)
+        if (r.arith == 1)
             return big ? launch_gemm3<A_KC, B_KC, 4, 1>(g, splits, st) : launch_gemm3<A_KC, B_KC, 2, 1>(g, splits, st);
-        if (arith == DLRM_ARITH_BF16)
+        if (r.arith == 2)
             return big ? launch_gemm3<A_KC, B_KC, 4, 2>(g, splits, st) : launch_gemm3<A_KC, B_KC, 2, 2>(g, splits, st);
         GEMM3_BIG_OR_NOT(0)
 #undef GEMM3_BIG_OR_NOT
@@ -1375,6 +1416,12 @@ static int launch_gemm(GemmArgs& g, int splits, hipStream_t st, int arith, bool*
     return 0;
 }
 
+static void route_out(const GemmRoute& r, int* out) {      // the layout of include/dlrm_hip.h (DLRM_ROUTE_*)
+    const int v[DLRM_ROUTE_FIELDS] = {r.path, r.tm, r.tn, r.frag, r.epi, r.nst, r.arith, r.sched, r.splits,
+                                      (int)(r.kchunk > 0x7fffffffll ? 0x7fffffffll : r.kchunk), r.bits, r.workspace, r.atomic};
+    for (int i = 0; i < DLRM_ROUTE_FIELDS; ++i) out[i] = v[i];
+}
+
 static bool arith_ok(int a) { return a == DLRM_ARITH_F32 || a == DLRM_ARITH_BF16X6 || a == DLRM_ARITH_BF16; }
 static int vec_ok_kc(const float* p, long long ld, long long kext) { return dlrm_aligned16(p) && ld % 4 == 0 && kext % 4 == 0; }
 // k-strided operand: a 16-byte load may run past the logical column extent as long as it stays inside the
@@ -1393,19 +1440,20 @@ static int relu_bits_from(int64_t M, int N, const float* Y, int64_t ldy, uint64_
     return 0;
 }
 
-extern "C" int dlrm_linear_fwd(int64_t M, int N, int K, const float* X, int64_t ldx, const float* W,
-                               int64_t ldw, const float* bias, int act, float* Y, int64_t ldy,
-                               uint64_t* relu_bits, int arith, void* stream) {
+// Each entry point = a PLAN (argument checks, the gemv / smallk pre-checks, the GemmArgs, the route: host arithmetic only) + the launch of what
+// the plan says.  dlrm_linear_*_route runs the same plan and reports its route instead of launching.
+static int linear_fwd_plan(int64_t M, int N, int K, const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, int act,
+                           float* Y, int64_t ldy, uint64_t* relu_bits, int arith, GemmArgs& g, GemmRoute& r) {
     if (M <= 0 || N <= 0 || K <= 0 || !X || !W || !Y) return DLRM_E_ARG;
     if (!arith_ok(arith)) return DLRM_E_MODE;
     if (relu_bits && act != DLRM_ACT_RELU) return DLRM_E_MODE;
     if (ldx < K || ldw < K || ldy < N) return DLRM_E_ARG;
     if (act < DLRM_ACT_NONE || act > DLRM_ACT_SIGMOID) return DLRM_E_MODE;
-    if (N == 1 && gemm_path() != 2) {                // matrix-vector layer: HBM streaming, not MFMA (gemv.hip)
-        const int rc = dlrm_gemv_fwd(M, K, X, ldx, W, bias, act, Y, ldy, (hipStream_t)stream);
-        if (rc != DLRM_GEMV_NOT_HANDLED) return (rc == 0 && relu_bits) ? relu_bits_from(M, N, Y, ldy, relu_bits, (hipStream_t)stream) : rc;
+    g = GemmArgs{}; r = GemmRoute{};
+    if (N == 1 && gemm_path() != 2 && dlrm_gemv_fwd_handles(K, X, ldx, W)) {      // matrix-vector layer: HBM streaming, not MFMA (gemv.hip)
+        r.path = DLRM_PATH_GEMV; r.splits = 1;
+        return 0;
     }
-    GemmArgs g = {};
     g.M = M; g.N = N; g.K = K;
     g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.C = Y; g.ldc = ldy;
     g.vecA = vec_ok_kc(X, ldx, K); g.vecB = vec_ok_kc(W, ldw, K);
@@ -1413,9 +1461,31 @@ extern "C" int dlrm_linear_fwd(int64_t M, int N, int K, const float* X, int64_t 
     g.kchunk = ((K + BK - 1) / BK) * BK;
     g.bias = bias; g.act = act;
     g.bits_out = (unsigned*)relu_bits; g.bits_nblk = ((long long)N + 63) / 64;
-    bool fast = false;
-    const int rc = launch_gemm<true, true>(g, 1, (hipStream_t)stream, arith, &fast);
-    if (rc == 0 && relu_bits && !fast) return relu_bits_from(M, N, Y, ldy, relu_bits, (hipStream_t)stream);
+    r = gemm_route<true, true>(g, 1, arith);
+    return 0;
+}
+
+extern "C" int dlrm_linear_fwd(int64_t M, int N, int K, const float* X, int64_t ldx, const float* W,
+                               int64_t ldw, const float* bias, int act, float* Y, int64_t ldy,
+                               uint64_t* relu_bits, int arith, void* stream) {
+    GemmArgs g; GemmRoute r;
+    int rc = linear_fwd_plan(M, N, K, X, ldx, W, ldw, bias, act, Y, ldy, relu_bits, arith, g, r);
+    if (rc) return rc;
+    if (r.path == DLRM_PATH_GEMV) rc = dlrm_gemv_fwd(M, K, X, ldx, W, bias, act, Y, ldy, (hipStream_t)stream);
+    else rc = launch_route<true, true>(g, r, (hipStream_t)stream);
+    // sign bits the chosen kernel did not write itself (gemv, the 64 x 64 tiles, the any-shape kernel): the stand-alone bit kernel
+    if (rc == 0 && relu_bits && !r.bits) return relu_bits_from(M, N, Y, ldy, relu_bits, (hipStream_t)stream);
+    return rc;
+}
+
+extern "C" int dlrm_linear_fwd_route(int64_t M, int N, int K, const float* X, int64_t ldx, const float* W,
+                                     int64_t ldw, const float* bias, int act, float* Y, int64_t ldy,
+                                     uint64_t* relu_bits, int arith, void* stream, int* route) {
+    (void)stream;
+    if (!route) return DLRM_E_ARG;
+    GemmArgs g; GemmRoute r;
+    const int rc = linear_fwd_plan(M, N, K, X, ldx, W, ldw, bias, act, Y, ldy, relu_bits, arith, g, r);
+    if (rc == 0) route_out(r, route);
     return rc;
 }
 
@@ -1571,20 +1641,19 @@ extern "C" int64_t dlrm_relu_bits_bytes(int64_t M, int N) {
     return ((M + 31) / 32) * (((int64_t)N + 63) / 64) * 32 * 8;
 }
 
-extern "C" int dlrm_linear_bwd_data(int64_t M, int N, int K, const float* dY, int64_t lddy,
-                                    const float* W, int64_t ldw, const float* Xact, int64_t ldxa,
-                                    int xact_kind, const uint64_t* relu_bits, float* dX, int64_t lddx, int arith, void* stream) {
+static int linear_bwd_data_plan(int64_t M, int N, int K, const float* dY, int64_t lddy, const float* W, int64_t ldw, const float* Xact,
+                                int64_t ldxa, int xact_kind, const uint64_t* relu_bits, float* dX, int64_t lddx, int arith,
+                                GemmArgs& g, GemmRoute& r) {
     if (M <= 0 || N <= 0 || K <= 0 || !dY || !W || !dX) return DLRM_E_ARG;
     if (!arith_ok(arith)) return DLRM_E_MODE;
     if (lddy < N || ldw < K || lddx < K) return DLRM_E_ARG;
     if (xact_kind < DLRM_ACT_NONE || xact_kind > DLRM_ACT_SIGMOID) return DLRM_E_MODE;
     if (xact_kind != DLRM_ACT_NONE && (!Xact || ldxa < K)) return DLRM_E_ARG;
-    if (N == 1 && gemm_path() != 2) {
-        const int rc = dlrm_gemv_bwd_data(M, K, dY, lddy, W, xact_kind != DLRM_ACT_NONE ? Xact : nullptr, ldxa, xact_kind, dX,
-                                          lddx, (hipStream_t)stream);
-        if (rc != DLRM_GEMV_NOT_HANDLED) return rc;
+    g = GemmArgs{}; r = GemmRoute{};
+    if (N == 1 && gemm_path() != 2 && dlrm_gemv_bwd_data_handles(K, W, xact_kind != DLRM_ACT_NONE ? Xact : nullptr, ldxa, dX, lddx)) {
+        r.path = DLRM_PATH_GEMV; r.splits = 1;
+        return 0;
     }
-    GemmArgs g = {};
     g.M = M; g.N = K; g.K = N;                       // output [M, K_layer], reduce over N_layer
     g.A = dY; g.lda = lddy; g.B = W; g.ldb = ldw; g.C = dX; g.ldc = lddx;
     g.vecA = vec_ok_kc(dY, lddy, N); g.vecB = vec_ok_ks(W, ldw, K);
@@ -1599,7 +1668,31 @@ extern "C" int dlrm_linear_bwd_data(int64_t M, int N, int K, const float* dY, in
             g.vecC = g.vecC && dlrm_aligned16(Xact) && ldxa % 4 == 0;
         }
     }
-    return launch_gemm<true, false>(g, 1, (hipStream_t)stream, arith);
+    r = gemm_route<true, false>(g, 1, arith);
+    return 0;
+}
+
+extern "C" int dlrm_linear_bwd_data(int64_t M, int N, int K, const float* dY, int64_t lddy,
+                                    const float* W, int64_t ldw, const float* Xact, int64_t ldxa,
+                                    int xact_kind, const uint64_t* relu_bits, float* dX, int64_t lddx, int arith, void* stream) {
+    GemmArgs g; GemmRoute r;
+    const int rc = linear_bwd_data_plan(M, N, K, dY, lddy, W, ldw, Xact, ldxa, xact_kind, relu_bits, dX, lddx, arith, g, r);
+    if (rc) return rc;
+    if (r.path == DLRM_PATH_GEMV)
+        return dlrm_gemv_bwd_data(M, K, dY, lddy, W, xact_kind != DLRM_ACT_NONE ? Xact : nullptr, ldxa, xact_kind, dX, lddx, (hipStream_t)stream);
+    return launch_route<true, false>(g, r, (hipStream_t)stream);
+}
+
+extern "C" int dlrm_linear_bwd_data_route(int64_t M, int N, int K, const float* dY, int64_t lddy,
+                                          const float* W, int64_t ldw, const float* Xact, int64_t ldxa,
+                                          int xact_kind, const uint64_t* relu_bits, float* dX, int64_t lddx, int arith, void* stream,
+                                          int* route) {
+    (void)stream;
+    if (!route) return DLRM_E_ARG;
+    GemmArgs g; GemmRoute r;
+    const int rc = linear_bwd_data_plan(M, N, K, dY, lddy, W, ldw, Xact, ldxa, xact_kind, relu_bits, dX, lddx, arith, g, r);
+    if (rc == 0) route_out(r, route);
+    return rc;
 }
 
 static void wgrad_plan(int64_t M, int N, int K, int* splits_out, int64_t* kchunk_out) {
@@ -1648,24 +1741,22 @@ extern "C" int64_t dlrm_linear_bwd_weight_workspace_bytes(int64_t M, int N, int 
     return need;
 }
 
-// K_store <= K: dW is [N, K_store]; the columns K_store..K-1 of X are alignment padding (zeros) whose gradient is dropped
-static int linear_bwd_weight_impl(int64_t M, int N, int K, int K_store, const float* dY, int64_t lddy,
+static int linear_bwd_weight_plan(int64_t M, int N, int K, int K_store, const float* dY, int64_t lddy,
                                   const float* X, int64_t ldx, float* dW, int64_t lddw,
                                   float* dbias, int accumulate, void* workspace, int64_t workspace_bytes,
-                                  int arith, void* stream) {
+                                  int arith, GemmArgs& g, GemmRoute& r) {
     if (!arith_ok(arith)) return DLRM_E_MODE;
     if (M <= 0 || N <= 0 || K <= 0 || K_store <= 0 || K_store > K || !dY || !X || !dW) return DLRM_E_ARG;
     if (lddy < N || ldx < K || lddw < K_store) return DLRM_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (N == 1 && K_store == K && gemm_path() != 2) {
-        const int rc = dlrm_gemv_bwd_weight(M, K, dY, lddy, X, ldx, dW, dbias, accumulate, workspace, workspace_bytes, st);
-        if (rc != DLRM_GEMV_NOT_HANDLED) return rc;
+    g = GemmArgs{}; r = GemmRoute{};
+    if (N == 1 && K_store == K && gemm_path() != 2 && dlrm_gemv_bwd_weight_handles(M, K, X, ldx, workspace, workspace_bytes)) {
+        r.path = DLRM_PATH_GEMV; r.splits = 1; r.workspace = 1;
+        return 0;
     }
-    if (K <= 16 && M >= 4096 && gemm_path() != 2) {
-        const int rc = dlrm_smallk_bwd_weight(M, N, K, K_store, dY, lddy, X, ldx, dW, lddw, dbias, accumulate, workspace, workspace_bytes, st);
-        if (rc != DLRM_GEMV_NOT_HANDLED) return rc;
+    if (K <= 16 && M >= 4096 && gemm_path() != 2 && dlrm_smallk_bwd_weight_handles(M, N, K, dY, lddy, X, ldx, workspace, workspace_bytes)) {
+        r.path = DLRM_PATH_SMALLK; r.splits = 1; r.workspace = 1;
+        return 0;
     }
-    GemmArgs g = {};
     g.M = N; g.N = K; g.K = M;                       // output [N_layer, K_layer], reduce over the batch
     g.A = dY; g.lda = lddy; g.B = X; g.ldb = ldx; g.C = dW; g.ldc = lddw;
     g.vecA = vec_ok_ks(dY, lddy, N); g.vecB = vec_ok_ks(X, ldx, K);
@@ -1686,9 +1777,32 @@ static int linear_bwd_weight_impl(int64_t M, int N, int K, int K_store, const fl
     if (K_store < K && !use_ws) return DLRM_E_ARG;   // a narrower dW needs the slab path (pass the queried workspace)
     if (use_ws) {
         g.C = (float*)workspace; g.ldc = ldp; g.vecC = 1; g.c_split_stride = slab; g.atomic_out = 0;
-        float* rs_part = dbias ? (float*)workspace + (int64_t)splits * slab : nullptr;
-        if (dbias) { g.rowsumA = rs_part; g.rowsum_split_stride = N; }
-        int rc = launch_gemm<false, false>(g, splits, st, arith);
+        if (dbias) { g.rowsumA = (float*)workspace + (int64_t)splits * slab; g.rowsum_split_stride = N; }
+    } else {
+        g.atomic_out = (splits > 1 || accumulate) ? 1 : 0;
+    }
+    r = gemm_route<false, false>(g, splits, arith);
+    r.workspace = use_ws ? 1 : 0; r.atomic = g.atomic_out;
+    return 0;
+}
+
+// K_store <= K: dW is [N, K_store]; the columns K_store..K-1 of X are alignment padding (zeros) whose gradient is dropped
+static int linear_bwd_weight_impl(int64_t M, int N, int K, int K_store, const float* dY, int64_t lddy,
+                                  const float* X, int64_t ldx, float* dW, int64_t lddw,
+                                  float* dbias, int accumulate, void* workspace, int64_t workspace_bytes,
+                                  int arith, void* stream) {
+    GemmArgs g; GemmRoute r;
+    const int prc = linear_bwd_weight_plan(M, N, K, K_store, dY, lddy, X, ldx, dW, lddw, dbias, accumulate, workspace, workspace_bytes, arith, g, r);
+    if (prc) return prc;
+    hipStream_t st = (hipStream_t)stream;
+    if (r.path == DLRM_PATH_GEMV) return dlrm_gemv_bwd_weight(M, K, dY, lddy, X, ldx, dW, dbias, accumulate, workspace, workspace_bytes, st);
+    if (r.path == DLRM_PATH_SMALLK)
+        return dlrm_smallk_bwd_weight(M, N, K, K_store, dY, lddy, X, ldx, dW, lddw, dbias, accumulate, workspace, workspace_bytes, st);
+    const int splits = r.splits;
+    if (r.workspace) {
+        const int64_t ldp = g.ldc, slab = g.c_split_stride;
+        float* rs_part = dbias ? g.rowsumA : nullptr;
+        int rc = launch_route<false, false>(g, r, st);
         if (rc) return rc;
         const bool v4 = dlrm_aligned16(dW) && lddw % 4 == 0 && K_store % 4 == 0;
         const long long items = (long long)N * (v4 ? K_store / 4 : K_store);
@@ -1700,14 +1814,25 @@ static int linear_bwd_weight_impl(int64_t M, int N, int K, int K_store, const fl
         DLRM_LAUNCH_CHECK();
         return 0;
     }
-    g.atomic_out = (splits > 1 || accumulate) ? 1 : 0;
     if (!accumulate) {
         int e = 0;                            // zeroed by kernels (no memset nodes in a captured step, common.h)
         if (g.atomic_out) e = dlrm_zero2d(dW, lddw, K, N, st);
         if (e == 0 && dbias) e = dlrm_zero2d(dbias, N, N, 1, st);
         if (e) return e;
     }
-    return launch_gemm<false, false>(g, splits, st, arith);
+    return launch_route<false, false>(g, r, st);
+}
+
+extern "C" int dlrm_linear_bwd_weight_route(int64_t M, int N, int K, int K_store, const float* dY, int64_t lddy,
+                                            const float* X, int64_t ldx, float* dW, int64_t lddw,
+                                            float* dbias, int accumulate, void* workspace, int64_t workspace_bytes,
+                                            int arith, void* stream, int* route) {
+    (void)stream;
+    if (!route) return DLRM_E_ARG;
+    GemmArgs g; GemmRoute r;
+    const int rc = linear_bwd_weight_plan(M, N, K, K_store, dY, lddy, X, ldx, dW, lddw, dbias, accumulate, workspace, workspace_bytes, arith, g, r);
+    if (rc == 0) route_out(r, route);
+    return rc;
 }
 
 // The backward of an N == 1 layer (the 256 -> 1 head of the top tower, dlrm_s_pytorch.py:208-246 / AddmmBackward + SigmoidBackward :1613) in one

@@ -266,13 +266,29 @@ int64_t dlrm_gemv_bwd_weight_workspace_bytes(int64_t M, int K) {
     return (int64_t)nblk * ldp * (int64_t)sizeof(float);
 }
 
+// the pre-checks of the three calls below as pure host predicates (pointers are inspected for alignment only): the calls themselves
+// and the route queries of gemm.hip (dlrm_linear_*_route) ask the same function, so a query cannot drift from the launch
+bool dlrm_gemv_fwd_handles(int K, const float* X, int64_t ldx, const float* w) {
+    if (!gemv_ok(X, ldx, K) || !dlrm_aligned16(w)) return false;
+    const int kq = K / 4;
+    int lpr = 4; while (lpr < 64 && lpr < kq) lpr <<= 1;
+    return lpr * kNJ >= kq;
+}
+bool dlrm_gemv_bwd_data_handles(int K, const float* w, const float* Xact, int64_t ldxa, const float* dX, int64_t lddx) {
+    if (!gemv_ok(dX, lddx, K) || !dlrm_aligned16(w)) return false;
+    return !(Xact && (!dlrm_aligned16(Xact) || ldxa % 4 != 0));
+}
+bool dlrm_gemv_bwd_weight_handles(int64_t M, int K, const float* X, int64_t ldx, const void* workspace, int64_t workspace_bytes) {
+    if (!gemv_ok(X, ldx, K)) return false;
+    return workspace && dlrm_aligned16(workspace) && workspace_bytes >= dlrm_gemv_bwd_weight_workspace_bytes(M, K);
+}
+
 // each returns 0 when it handled the call, DLRM_GEMV_NOT_HANDLED when the caller must use the GEMM path
 int dlrm_gemv_fwd(int64_t M, int K, const float* X, int64_t ldx, const float* w, const float* bias, int act, float* Y,
                   int64_t ldy, hipStream_t st) {
-    if (!gemv_ok(X, ldx, K) || !dlrm_aligned16(w)) return DLRM_GEMV_NOT_HANDLED;
+    if (!dlrm_gemv_fwd_handles(K, X, ldx, w)) return DLRM_GEMV_NOT_HANDLED;
     const int kq = K / 4;
     int lpr = 4; while (lpr < 64 && lpr < kq) lpr <<= 1;      // one 16-byte chunk per lane when the row fits a wave
-    if (lpr * kNJ < kq) return DLRM_GEMV_NOT_HANDLED;
     const long long rows_per_wave_iter = (64 / lpr) * kU;
     long long blocks = (M + rows_per_wave_iter * 4 - 1) / (rows_per_wave_iter * 4);
     if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
@@ -290,8 +306,7 @@ int dlrm_gemv_fwd(int64_t M, int K, const float* X, int64_t ldx, const float* w,
 
 int dlrm_gemv_bwd_data(int64_t M, int K, const float* dY, int64_t lddy, const float* w, const float* Xact, int64_t ldxa,
                        int kind, float* dX, int64_t lddx, hipStream_t st) {
-    if (!gemv_ok(dX, lddx, K) || !dlrm_aligned16(w)) return DLRM_GEMV_NOT_HANDLED;
-    if (Xact && (!dlrm_aligned16(Xact) || ldxa % 4 != 0)) return DLRM_GEMV_NOT_HANDLED;
+    if (!dlrm_gemv_bwd_data_handles(K, w, Xact, ldxa, dX, lddx)) return DLRM_GEMV_NOT_HANDLED;
     const long long total = (long long)M * (K / 4);
     long long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(gemv_bwd_data_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (long long)M, K, dY, (long long)lddy, w,
@@ -302,9 +317,7 @@ int dlrm_gemv_bwd_data(int64_t M, int K, const float* dY, int64_t lddy, const fl
 
 int dlrm_gemv_bwd_weight(int64_t M, int K, const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW,
                          float* dbias, int accumulate, void* workspace, int64_t workspace_bytes, hipStream_t st) {
-    if (!gemv_ok(X, ldx, K)) return DLRM_GEMV_NOT_HANDLED;
-    const int64_t need = dlrm_gemv_bwd_weight_workspace_bytes(M, K);
-    if (!workspace || !dlrm_aligned16(workspace) || workspace_bytes < need) return DLRM_GEMV_NOT_HANDLED;
+    if (!dlrm_gemv_bwd_weight_handles(M, K, X, ldx, workspace, workspace_bytes)) return DLRM_GEMV_NOT_HANDLED;
     int nblk, ldp; long long rpb;
     gemv_wgrad_plan(M, K, &nblk, &rpb, &ldp);
     hipLaunchKernelGGL(gemv_bwd_weight_partial_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (long long)M, K, dY,

@@ -160,12 +160,17 @@ int64_t dlrm_smallk_bwd_weight_workspace_bytes(int64_t M, int N, int K) {
     return (int64_t)nblk * stride * (int64_t)sizeof(float);
 }
 
+// the call's pre-check as a pure host predicate (pointers inspected for alignment only), shared with gemm.hip's route query
+bool dlrm_smallk_bwd_weight_handles(int64_t M, int N, int K, const float* dY, int64_t lddy, const float* X, int64_t ldx,
+                                    const void* workspace, int64_t workspace_bytes) {
+    if (!smallk_shape_ok(N, K) || !dlrm_aligned16(X) || !dlrm_aligned16(dY) || ldx % 4 || lddy % 4) return false;
+    return workspace && dlrm_aligned16(workspace) && workspace_bytes >= dlrm_smallk_bwd_weight_workspace_bytes(M, N, K);
+}
+
 int dlrm_smallk_bwd_weight(int64_t M, int N, int K, int K_store, const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW,
                            int64_t lddw, float* dbias, int accumulate, void* workspace, int64_t workspace_bytes,
                            hipStream_t st) {
-    if (!smallk_shape_ok(N, K) || !dlrm_aligned16(X) || !dlrm_aligned16(dY) || ldx % 4 || lddy % 4) return DLRM_GEMV_NOT_HANDLED;
-    const int64_t need = dlrm_smallk_bwd_weight_workspace_bytes(M, N, K);
-    if (!workspace || !dlrm_aligned16(workspace) || workspace_bytes < need) return DLRM_GEMV_NOT_HANDLED;
+    if (!dlrm_smallk_bwd_weight_handles(M, N, K, dY, lddy, X, ldx, workspace, workspace_bytes)) return DLRM_GEMV_NOT_HANDLED;
     int nblk; long long rpb, stride;
     smallk_wgrad_plan(M, N, K, &nblk, &rpb, &stride);
     const int KQ = K / 4, NQ = N / 4;

@@ -1811,6 +1811,62 @@ def linear_bwd_weight(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, dbias
     return dW
 
 
+# ---- route queries: which kernel a dlrm_linear_* call would launch (include/dlrm_hip.h DLRM_ROUTE_*; host code only, no GPU needed) ----
+PATH_FALLBACK, PATH_GEMM3, PATH_GEMV, PATH_SMALLK = 0, 1, 2, 3
+
+
+class GemmRoute(NamedTuple):
+    """the dispatch decision of csrc/gemm.hip, field for field the int[DLRM_ROUTE_FIELDS] of include/dlrm_hip.h"""
+    path: int
+    tm: int
+    tn: int
+    frag: int
+    epi: int
+    nst: int
+    arith: int
+    sched: int
+    splits: int
+    kchunk: int
+    bits: int
+    workspace: int
+    atomic: int
+
+
+def _addr(p) -> Optional[C.c_void_p]:
+    """an operand of a route query: a tensor (its data pointer), a plain address, or None — only NULL-ness and alignment are looked at"""
+    if p is None:
+        return None
+    return C.c_void_p(p.data_ptr() if isinstance(p, torch.Tensor) else int(p))
+
+
+def _route(name: str, *args) -> GemmRoute:
+    out = (C.c_int * len(GemmRoute._fields))()
+    _lib.check(getattr(_lib.load(), name)(*args, None, out), name)
+    return GemmRoute(*out)
+
+
+def linear_fwd_route(M: int, N: int, K: int, X, ldx: int, W, ldw: int, bias, act: int, Y, ldy: int, relu_bits=None,
+                     arith=_lib.ARITH_F32) -> GemmRoute:
+    """the route of linear_fwd on these operands (tensors or raw addresses; nothing is read, nothing launched)"""
+    return _route("dlrm_linear_fwd_route", M, N, K, _addr(X), ldx, _addr(W), ldw, _addr(bias), int(act), _addr(Y), ldy, _addr(relu_bits),
+                  arith_code(arith))
+
+
+def linear_bwd_data_route(M: int, N: int, K: int, dY, lddy: int, W, ldw: int, Xact, ldxa: int, xact_kind: int, relu_bits, dX, lddx: int,
+                          arith=_lib.ARITH_F32) -> GemmRoute:
+    """the route of linear_bwd_data (Xact None -> no mask, as in the call)"""
+    return _route("dlrm_linear_bwd_data_route", M, N, K, _addr(dY), lddy, _addr(W), ldw, _addr(Xact), ldxa if Xact is not None else 0,
+                  int(xact_kind if Xact is not None else ACT_NONE), _addr(relu_bits) if Xact is not None else None, _addr(dX), lddx,
+                  arith_code(arith))
+
+
+def linear_bwd_weight_route(M: int, N: int, K: int, K_store: int, dY, lddy: int, X, ldx: int, dW, lddw: int, dbias=None,
+                            accumulate: bool = False, workspace=None, workspace_bytes: int = 0, arith=_lib.ARITH_F32) -> GemmRoute:
+    """the route of linear_bwd_weight (K_store < K: the padded form); workspace None = the atomic-accumulation variant"""
+    return _route("dlrm_linear_bwd_weight_route", M, N, K, K_store, _addr(dY), lddy, _addr(X), ldx, _addr(dW), lddw, _addr(dbias),
+                  int(bool(accumulate)), _addr(workspace), int(workspace_bytes), arith_code(arith))
+
+
 def linear_head_bwd(dY: torch.Tensor, Y: Optional[torch.Tensor], act: int, X: torch.Tensor, W: torch.Tensor, xact_kind: int,
                     dX: Optional[torch.Tensor], dW: torch.Tensor, dbias: Optional[torch.Tensor], accumulate: bool = False) -> bool:
     """The whole backward of an N == 1 layer in one pass over X (dlrm_linear_head_bwd): dz = dY * act'(Y), dW [1, K] = dz^T X, dbias [1] = sum dz,

@@ -793,6 +793,49 @@ int dlrm_linear_bwd_weight_padded(int64_t M, int N, int K, int K_store,
 int dlrm_linear_head_bwd(int64_t M, int K, const float* dY, int64_t lddy, const float* Y, int64_t ldy, int act,
                          const float* X, int64_t ldx, const float* W, int xact_kind, float* dX, int64_t lddx,
                          float* dW, float* dbias, int accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+/* ROUTE QUERIES (symbols added, the ABI version stays 17): which kernel a dlrm_linear_* call WOULD launch.  Each takes the arguments of its
+ * call (dlrm_linear_bwd_weight_route: those of dlrm_linear_bwd_weight_padded; K_store == K is dlrm_linear_bwd_weight) plus `route`, an
+ * int[DLRM_ROUTE_FIELDS] it fills; it runs the call's own argument checks and dispatch (the same host code: csrc/gemm.hip gemm_route) and
+ * returns the call's error code without launching anything.  Pure host arithmetic: pointers are inspected for NULL and 16-byte alignment
+ * only, never dereferenced; no HIP call is made, `stream` is ignored, no GPU is needed.  The library has no switch that alters the choice:
+ * it is a function of the arguments alone (tests/gemm_route_cases.py pins it per kernel variant).
+ *   route[DLRM_ROUTE_PATH]    DLRM_PATH_FALLBACK (the any-shape fp32 kernel), _GEMM3 (the MFMA tile kernel), _GEMV (N == 1), _SMALLK (K <= 16 wgrad)
+ *   [TM] [TN] [FRAG] [EPI] [NST] [ARITH] [SCHED]   the tile kernel's variant: 64 * TM x 64 * TN output tile, vector fragments of k-strided
+ *                             operands, epilogue 0 general / 1 straight-line / 2 straight-line + ReLU, ring stages, 0 fp32 / 1 bf16x6 / 2 bf16
+ *                             MFMA, fragment-read schedule; all 0 on the other paths
+ *   [SPLITS] [KCHUNK]         k-slices of the reduction and the length of each (KCHUNK saturates at INT_MAX)
+ *   [BITS]                    1: that kernel itself writes (forward) / reads (data gradient) the ReLU sign bits; 0 with relu_bits given: the
+ *                             forward runs the stand-alone bit kernel behind it, the data gradient masks with the fp32 Xact
+ *   [WORKSPACE] [ATOMIC]      weight gradient: the k-slices store slabs in `workspace` / add into dW with fp32 atomics */
+#define DLRM_ROUTE_FIELDS 13
+#define DLRM_ROUTE_PATH 0
+#define DLRM_ROUTE_TM 1
+#define DLRM_ROUTE_TN 2
+#define DLRM_ROUTE_FRAG 3
+#define DLRM_ROUTE_EPI 4
+#define DLRM_ROUTE_NST 5
+#define DLRM_ROUTE_ARITH 6
+#define DLRM_ROUTE_SCHED 7
+#define DLRM_ROUTE_SPLITS 8
+#define DLRM_ROUTE_KCHUNK 9
+#define DLRM_ROUTE_BITS 10
+#define DLRM_ROUTE_WORKSPACE 11
+#define DLRM_ROUTE_ATOMIC 12
+#define DLRM_PATH_FALLBACK 0
+#define DLRM_PATH_GEMM3 1
+#define DLRM_PATH_GEMV 2
+#define DLRM_PATH_SMALLK 3
+int dlrm_linear_fwd_route(int64_t M, int N, int K,
+                          const float* X, int64_t ldx, const float* W, int64_t ldw,
+                          const float* bias, int act, float* Y, int64_t ldy, uint64_t* relu_bits, int arith, void* stream, int* route);
+int dlrm_linear_bwd_data_route(int64_t M, int N, int K,
+                               const float* dY, int64_t lddy, const float* W, int64_t ldw,
+                               const float* Xact, int64_t ldxa, int xact_kind, const uint64_t* relu_bits,
+                               float* dX, int64_t lddx, int arith, void* stream, int* route);
+int dlrm_linear_bwd_weight_route(int64_t M, int N, int K, int K_store,
+                                 const float* dY, int64_t lddy, const float* X, int64_t ldx,
+                                 float* dW, int64_t lddw, float* dbias, int accumulate,
+                                 void* workspace, int64_t workspace_bytes, int arith, void* stream, int* route);
 /* dst[m, 0:K] = src[m, 0:K], dst[m, K:Kp] = 0   (builds those padded operands: no ATen fill/copy on the hot path) */
 int dlrm_pad_cols(int64_t M, int K, int Kp, const float* src, int64_t ld_src, float* dst, int64_t ld_dst, void* stream);
 
