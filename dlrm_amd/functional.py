@@ -750,6 +750,42 @@ class InteractFunction(Function):
         return (None, None, None, *dblocks) if ctx.order is None else (None, None, None, None, *dblocks)
 
 
+class ProjectInteractFunction(Function):
+    """R = [x | Z flattened row-major], Z[b] = P1[b].view(I1, D) @ P2[b].view(D, I2) — the projected interaction of torchrec's
+    DLRM_Projection (ops.proj_interact_fwd / proj_interact_bwd; fp32).
+
+    forward(D, padded, x, P1, P2): x [B, D] is read in place (a column slice of the feature buffer), P1 [B, I1*D], P2 [B, D*I2]."""
+
+    @staticmethod
+    def forward(ctx, D, padded, x, P1, P2):
+        x, P1, P2 = _rowmajor(x), _rowmajor(P1), _rowmajor(P2)
+        B = x.size(0)
+        I1, I2 = ops._proj_dims(P1, P2, D)
+        Wd = D + I1 * I2
+        ldr = _round4(Wd)
+        Rfull = torch.empty((B, ldr), dtype=torch.float32, device=x.device)
+        ops.proj_interact_fwd(x, P1, P2, D, Rfull)
+        ctx.D = D
+        ctx.save_for_backward(P1, P2)
+        # padded=True hands out the whole [B, round4(width)] buffer (zero padding columns) for MLPFunction
+        return Rfull if (ldr == Wd or padded) else Rfull[:, :Wd]
+
+    @staticmethod
+    def backward(ctx, dR):
+        P1, P2 = ctx.saved_tensors
+        dR = _rowmajor(dR)
+        B, D = P1.size(0), ctx.D
+        # one flat buffer, one contiguous chunk per input, in input order (x, P1, P2)
+        widths = (D, P1.size(1), P2.size(1))
+        flat = torch.empty(B * sum(widths), dtype=torch.float32, device=dR.device)
+        grads, o = [], 0
+        for w in widths:
+            grads.append(flat[o:o + B * w].view(B, w))
+            o += B * w
+        ops.proj_interact_bwd(P1, P2, D, dR, *grads)
+        return (None, None, *grads)
+
+
 class GatherKind(NamedTuple):
     """What the fused lookup + interaction path needs to know of a route's kind (dlrm_net.fused_route): a key of ops.ROW_KINDS, or "fp32".
     The wrappers are NAMES of `ops` attributes, looked up when they are called."""

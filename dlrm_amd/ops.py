@@ -1434,6 +1434,49 @@ def interact_bwd(blocks: Sequence[torch.Tensor], D: int, self_interaction: bool,
     _lib.check(rc, "dlrm_interact_bwd")
 
 
+def _proj_dims(P1: torch.Tensor, P2: torch.Tensor, D: int):
+    """(I1, I2) of the projected interaction's operands P1 [B, I1*D], P2 [B, D*I2]; (0, 0) where the widths are no multiple of D"""
+    D = int(D)
+    if D < 1 or P1.size(1) % D or P2.size(1) % D:
+        return 0, 0
+    return P1.size(1) // D, P2.size(1) // D
+
+
+def proj_interact_fwd(x: torch.Tensor, P1: torch.Tensor, P2: torch.Tensor, D: int, R: torch.Tensor) -> torch.Tensor:
+    """R = [x | (P1 viewed [B, I1, D]) . (P2 viewed [B, D, I2]) flattened row-major | zeros] (dlrm_proj_interact_fwd): x [B, D] may be a
+    column slice of a wider buffer, R [B, >= D + I1*I2]; the columns beyond D + I1*I2 are zero-filled."""
+    lib = _lib.load()
+    for t, name in ((x, "x"), (P1, "P1"), (P2, "P2"), (R, "R")):
+        _req(t, name, ndim=2)
+    B = x.size(0)
+    I1, I2 = _proj_dims(P1, P2, D)
+    if I1 < 1 or I2 < 1 or x.size(1) != D or P1.size(0) != B or P2.size(0) != B or R.size(0) != B or R.size(1) < D + I1 * I2:
+        raise RuntimeError("dlrm_amd: proj_interact_fwd shape mismatch")
+    with _timed("proj_interact_fwd"):
+        rc = lib.dlrm_proj_interact_fwd(B, D, I1, I2, C.c_void_p(x.data_ptr()), _ld(x), C.c_void_p(P1.data_ptr()), _ld(P1),
+                                        C.c_void_p(P2.data_ptr()), _ld(P2), C.c_void_p(R.data_ptr()), _ld(R), _stream(R))
+    _lib.check(rc, "dlrm_proj_interact_fwd")
+    return R
+
+
+def proj_interact_bwd(P1: torch.Tensor, P2: torch.Tensor, D: int, dR: torch.Tensor, dx: torch.Tensor, dP1: torch.Tensor,
+                      dP2: torch.Tensor) -> None:
+    """dx = dR[:, :D], dP1 = dZ . Bm^T, dP2 = A^T . dZ (dlrm_proj_interact_bwd): overwrites dx [B, D], dP1 [B, I1*D], dP2 [B, D*I2]"""
+    lib = _lib.load()
+    for t, name in ((P1, "P1"), (P2, "P2"), (dR, "dR"), (dx, "dx"), (dP1, "dP1"), (dP2, "dP2")):
+        _req(t, name, ndim=2)
+    B = P1.size(0)
+    I1, I2 = _proj_dims(P1, P2, D)
+    if (I1 < 1 or I2 < 1 or P2.size(0) != B or dR.size(0) != B or dR.size(1) < D + I1 * I2 or tuple(dx.shape) != (B, D)
+            or dP1.shape != P1.shape or dP2.shape != P2.shape):
+        raise RuntimeError("dlrm_amd: proj_interact_bwd shape mismatch")
+    with _timed("proj_interact_bwd"):
+        rc = lib.dlrm_proj_interact_bwd(B, D, I1, I2, C.c_void_p(P1.data_ptr()), _ld(P1), C.c_void_p(P2.data_ptr()), _ld(P2),
+                                        C.c_void_p(dR.data_ptr()), _ld(dR), C.c_void_p(dx.data_ptr()), _ld(dx),
+                                        C.c_void_p(dP1.data_ptr()), _ld(dP1), C.c_void_p(dP2.data_ptr()), _ld(dP2), _stream(dR))
+    _lib.check(rc, "dlrm_proj_interact_bwd")
+
+
 # ------------------------------------------------------------------------------------------------
 # MLP layers
 # ------------------------------------------------------------------------------------------------

@@ -12,6 +12,11 @@ torch operators, not against torchrec output.  What differs from `dlrm_s_pytorch
   * the embedding optimizer is applied in backward (`apply_optimizer_in_backward`, dlrm_main.py:647-651): here the fused sparse
     update (row-wise Adagrad / SGD) launched by the optimizer-step hook — or, with `overlap_streams`, during backward itself.
 Inputs are the multi-hot batches of `dlrm_amd.multihot.Multihot` (int32 ids, per-table local offsets).
+
+The trainer builds one of three models (dlrm_main.py:598-635, --interaction_type): `DLRM` (original), `DLRM_DCN` (dcn: the DCN-v2 low-rank
+cross network over [dense | sparse]) and `DLRM_Projection` (projection: two MLP branches over [dense | sparse] whose outputs, viewed
+[I1, D] and [D, I2], are multiplied per sample — `dlrm_proj_interact_fwd / _bwd`, csrc/interact_proj.hip).  All three are restated here,
+UNPINNED alike; `DLRMTrain` wraps any of them.  `DLRM_Projection` is single-process: no distributed forward, no graph capture.
 """
 from __future__ import annotations
 
@@ -282,3 +287,66 @@ class DLRM_DCN(DLRM_Net):
         E = self._emb_packed(lS_o, lS_i, self.emb_l, self.v_W_l, out_slot=OutSlot(feat[:, D:]))
         z = self.crossnet(CatFunction.apply(OutSlot(feat), x, E))          # the feature buffer IS cat([dense, sparse]): no copy
         return self.apply_mlp(z, self.top_l)
+
+
+class DLRM_Projection(DLRM_Net):
+    """torchrec.models.dlrm.DLRM_Projection (torchrec_dlrm/dlrm_main.py:620-635, --interaction_type=projection): dense arch and pooled
+    embeddings are concatenated to C [B, F*D] — the feature buffer the bottom tower and the embedding kernel write side by side — and
+    two MLP branches (a Linear and a ReLU on every layer, the last included) project it to P1 [B, I1*D] and P2 [B, D*I2].  Per sample,
+    Z = P1[b].view(I1, D) @ P2[b].view(D, I2); the over arch takes [x | Z flattened row-major] and ends with a bare Linear (logits).
+    torchrec is absent from the reference tree and not installed: this restatement is the specification, parity is UNPINNED (checked
+    against a composition of torch operators).  The per-sample product is the library's own kernel pair (csrc/interact_proj.hip,
+    functional.ProjectInteractFunction) and stays fp32 under every tower arithmetic.  C feeds both branches and x also feeds R: those
+    gradients are summed by autograd's own accumulation (three elementwise adds per step that are not the library's kernels)."""
+
+    quantize_embedding = _no_quantized_tables
+    quantize_mlp = _no_quantized_towers
+    _qr_supported = False
+    _md_supported = False
+    _bf16_supported = False
+
+    def __init__(self, num_embeddings_per_feature: Sequence[int], embedding_dim: int, dense_in_features: int,
+                 dense_arch_layer_sizes: Sequence[int], over_arch_layer_sizes: Sequence[int],
+                 interaction_branch1_layer_sizes: Sequence[int], interaction_branch2_layer_sizes: Sequence[int]):
+        if list(dense_arch_layer_sizes)[-1] != embedding_dim:
+            raise ValueError("dense_arch_layer_sizes[-1] must equal the embedding dimension")
+        sizes1, sizes2 = list(interaction_branch1_layer_sizes), list(interaction_branch2_layer_sizes)
+        for name, sizes in (("interaction_branch1_layer_sizes", sizes1), ("interaction_branch2_layer_sizes", sizes2)):
+            if not sizes or sizes[-1] < embedding_dim or sizes[-1] % embedding_dim != 0:
+                raise ValueError("Final interaction branch layer size (%s[-1]) must be a multiple of the embedding dimension %d"
+                                 % (name, embedding_dim))
+        F = len(num_embeddings_per_feature) + 1
+        I1, I2 = sizes1[-1] // embedding_dim, sizes2[-1] // embedding_dim
+        ln_bot = np.asarray([dense_in_features] + list(dense_arch_layer_sizes))
+        ln_top = np.asarray([embedding_dim + I1 * I2] + list(over_arch_layer_sizes))
+        super().__init__(embedding_dim, np.asarray(list(num_embeddings_per_feature)), ln_bot, ln_top, arch_interaction_op="cat",
+                         sigmoid_bot=-1, sigmoid_top=-1, loss_function="bce")
+        self.I1, self.I2 = I1, I2
+        arith = self.top_l.arith
+        self.top_l = FusedMLP(*list(self.top_l.children())[:-1])
+        self.top_l.arith = arith
+        # drawn after the top tower, branch 1 before branch 2 (numpy's global RNG, create_mlp)
+        self.proj1_l = self.create_mlp(np.asarray([F * embedding_dim] + sizes1), -1)
+        self.proj2_l = self.create_mlp(np.asarray([F * embedding_dim] + sizes2), -1)
+        self.loss_fn = FusedBCEWithLogitsLoss()
+
+    def set_mlp_arith(self, name: str) -> None:
+        super().set_mlp_arith(name)
+        for tower in (self.proj1_l, self.proj2_l):
+            tower.arith = name
+
+    def distributed_forward(self, dense_x, lS_o, lS_i):
+        sys.exit("ERROR: DLRM_Projection is single-process only (the table-sharded distributed forward is not built for it)")
+
+    def sequential_forward(self, dense_x, lS_o, lS_i):
+        from . import ops
+        from .functional import CatFunction, OutSlot, ProjectInteractFunction
+        ops.check_index_errors()
+        B, T, D = dense_x.size(0), len(self.emb_l), self.m_spa
+        feat = torch.empty((B, (1 + T) * D), dtype=torch.float32, device=dense_x.device)
+        x = self.apply_mlp(dense_x, self.bot_l, out_slot=OutSlot(feat[:, :D]))
+        E = self._emb_packed(lS_o, lS_i, self.emb_l, self.v_W_l, out_slot=OutSlot(feat[:, D:]))
+        C_ = CatFunction.apply(OutSlot(feat), x, E)                         # the feature buffer IS cat([dense, sparse]): no copy
+        P1, P2 = self.apply_mlp(C_, self.proj1_l), self.apply_mlp(C_, self.proj2_l)
+        R = ProjectInteractFunction.apply(D, True, x, P1, P2)               # x read in place: the first D columns of the buffer
+        return self.apply_mlp(R, self.top_l)

@@ -582,6 +582,34 @@ int dlrm_interact_bwd(int64_t B, int F, int D,
                       int self_interaction, const float* dR, int64_t ldr,
                       void* const* dfeat_host, const int64_t* dfeat_ld_host, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K6p  projected interaction (torchrec DLRM_Projection's InteractionProjectionArch), forward.
+ * Replaces: torch.bmm(P1.view(B, I1, D), P2.view(B, D, I2)) + torch.cat([x, Z.view(B, -1)], dim=1).
+ *   per sample b:  A [I1, D] = P1[b] row-major (A[i, d] = P1[b*p1_ld + i*D + d]),  Bm [D, I2] = P2[b] row-major
+ *                  (Bm[d, j] = P2[b*p2_ld + d*I2 + j]),  Z = A . Bm
+ *   R[b, 0:D]            = x[b, 0:D]            (bit-exact copy; x is a column slice of the feature buffer: x_ld >= D)
+ *   R[b, D + i*I2 + j]   = Z[i, j]
+ *   columns [D + I1*I2, ldr) of R are zero-filled (ldr may pad the row for alignment).
+ * All leading dimensions count elements; offsets are 64-bit.  fp32 throughout, no atomics: sample b's outputs depend on sample
+ * b's inputs only, bit-identical from run to run and independent of B and of the sample's position in the batch.
+ * One entry point, two kernels the caller never chooses between: D % 4 == 0, I1, I2 <= 32, staged operands within 64 KB of
+ * LDS, every pointer 16-byte aligned and every leading dimension a multiple of 4 take the LDS + fp32-MFMA (16x16x4) kernel;
+ * everything else takes a one-thread-per-output kernel that reads global memory (correct, not fast).
+ * B == 0 returns 0 without a launch.  DLRM_E_ARG (before any launch): B < 0, D / I1 / I2 < 1, x_ld < D, p1_ld < I1*D,
+ * p2_ld < D*I2, ldr < D + I1*I2, a null pointer with B > 0.
+ */
+int dlrm_proj_interact_fwd(int64_t B, int D, int I1, int I2,
+                           const float* x, int64_t x_ld, const float* P1, int64_t p1_ld, const float* P2, int64_t p2_ld,
+                           float* R, int64_t ldr, void* stream);
+
+/* K6p backward:  dx = dR[:, 0:D] (bit-exact),  dA = dZ . Bm^T  (dP1[b, i*D + d] = sum_j dZ[i, j] * P2[b, d*I2 + j]),
+ * dBm = A^T . dZ  (dP2[b, d*I2 + j] = sum_i P1[b, i*D + d] * dZ[i, j]),  dZ[i, j] = dR[b, D + i*I2 + j].
+ * Writes dx [B, D], dP1 [B, I1*D] and dP2 [B, D*I2] completely (overwrites, never accumulates) and reads nothing but P1, P2 and
+ * dR.  Paths, numerics and errors as the forward (the same conditions over its own operands). */
+int dlrm_proj_interact_bwd(int64_t B, int D, int I1, int I2,
+                           const float* P1, int64_t p1_ld, const float* P2, int64_t p2_ld, const float* dR, int64_t ldr,
+                           float* dx, int64_t dx_ld, float* dP1, int64_t dp1_ld, float* dP2, int64_t dp2_ld, void* stream);
+
 /* K1 + K6 fused for one-lookup-per-bag inputs (the Criteo data sets: offsets = arange, dlrm_data_pytorch.py:334-337):
  * features whose index_host[f] != NULL are NOT [B, D] matrices but EmbeddingBag tables — feature f of sample b is row
  * index_host[f][b] of the table at feat_host[f] (feat_ld_host[f] = D), fetched by the interaction kernel itself.  The

@@ -17,11 +17,14 @@ CATS = {
     "interact_bwd": ["interact_bwd"],
     "emb_interact_fwd": ["interact_fwd_dma_kernel<"],
     "emb_interact_bwd": ["interact_bwd_dma_kernel<"],
+    "proj_interact_fwd": ["proj_interact_fwd"],                        # (DLRM_Projection's per-sample product: csrc/interact_proj.hip)
+    "proj_interact_bwd": ["proj_interact_bwd"],
     "linear_fwd": ["gemm3_kernel<true, true", "gemm_f32_kernel<true, true"],
     "linear_bwd_data": ["gemm3_kernel<true, false", "gemm_f32_kernel<true, false"],
     "linear_bwd_weight": ["gemm3_kernel<false, false", "gemm_f32_kernel<false, false", "splitk_reduce_kernel"],
 }
 CALLS_PER_STEP = {"emb_fwd": 1, "emb_bwd_sgd": 1, "interact_fwd": 1, "interact_bwd": 1, "emb_interact_fwd": 1, "emb_interact_bwd": 1,
+                  "proj_interact_fwd": 1, "proj_interact_bwd": 1,
                   "linear_fwd": 8, "linear_bwd_data": 7, "linear_bwd_weight": 8}
 
 
@@ -35,7 +38,7 @@ def in_cat(cat, pats, kernel):
     if cat.startswith("emb_interact"):
         return gather and any(p in kernel for p in pats)
     if cat.startswith("interact"):
-        return not gather and any(p in kernel for p in pats)
+        return not gather and "proj_interact" not in kernel and any(p in kernel for p in pats)
     return any(p in kernel for p in pats)
 
 
