@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
+#include <mutex>
 #include "../../include/dlrm_hip.h"
 
 #define DLRM_WAVE 64
@@ -27,6 +29,24 @@
 static inline int dlrm_current_device() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < DLRM_MAX_DEVICES) ? d : 0; }
 
 static inline bool dlrm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// The dynamic-LDS limit of a kernel, THE one way to raise it: dlrm_lds_limit<kernel>(bytes) in front of the launch.  The attribute is per
+// (function, device); the helper remembers the largest size it has set for each and makes the driver call only on the first use or when
+// a launch asks for more — a kernel with one size per instantiation sets it once, a kernel whose LDS follows the call's sizes (the generic
+// interaction kernels, the tower kernels) raises it as needed.  Threads: the usual call reads one atomic int; raising the limit and
+// recording it happen under a lock, so what is recorded is what was set last, whichever host threads launch the kernel (the autograd
+// thread and the main thread, two models in one process).
+template <auto Kernel>
+static inline void dlrm_lds_limit(size_t bytes) {
+    static std::atomic<int> set[DLRM_MAX_DEVICES];      // (static storage: zero)
+    static std::mutex raising;
+    std::atomic<int>& hi = set[dlrm_current_device()];
+    if ((int)bytes <= hi.load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> lock(raising);
+    if ((int)bytes <= hi.load(std::memory_order_relaxed)) return;
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    hi.store((int)bytes, std::memory_order_release);
+}
 
 // timing-only tuning switches (DLRM_GEMM_DEBUG, DLRM_INTERACT_DEBUG, DLRM_SEG_DEBUG) make kernels skip work: results are WRONG.
 // They — and since round 6 EVERY environment variable the library ever read — exist ONLY in a tuning build (`make TUNING=1` -> -DDLRM_TUNING, tools/probes/): the product library never reads these

@@ -341,7 +341,7 @@ static inline size_t gather_lds(int nb, bool bwd) {
 template <typename S, int NB, typename IT>
 void launch_fwd(const typename S::Args& ba, const float* x, long long x_ld, long long B, int F, int self, float* R, long long ldr, hipStream_t st) {
     const size_t lds = gather_lds<S>(NB, false);
-    (void)hipFuncSetAttribute((const void*)gather_fwd_kernel<S, NB, IT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    dlrm_lds_limit<gather_fwd_kernel<S, NB, IT>>(lds);
     hipLaunchKernelGGL((gather_fwd_kernel<S, NB, IT>), dim3((unsigned)gather_grid(B, lds)), dim3(64 * GC_WAVES), lds, st, ba, x, x_ld, B, F,
                        self, R, ldr);
 }
@@ -350,7 +350,7 @@ template <typename S, int NB, typename IT>
 void launch_bwd(const typename S::Args& ba, const float* x, long long x_ld, long long B, int F, int self, const float* dR, long long ldr, float* dx,
                 long long dx_ld, float* dE, long long dE_ld, hipStream_t st) {
     const size_t lds = gather_lds<S>(NB, true);
-    (void)hipFuncSetAttribute((const void*)gather_bwd_kernel<S, NB, IT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    dlrm_lds_limit<gather_bwd_kernel<S, NB, IT>>(lds);
     hipLaunchKernelGGL((gather_bwd_kernel<S, NB, IT>), dim3((unsigned)gather_grid(B, lds)), dim3(64 * GC_WAVES), lds, st, ba, x, x_ld, B, F,
                        self, dR, ldr, dx, dx_ld, dE, dE_ld);
 }

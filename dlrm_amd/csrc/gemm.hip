@@ -1255,12 +1255,7 @@ static int launch_gemm3(GemmArgs& g, int splits, hipStream_t st) {
         static const int pad = DLRM_TUNE_ENV("DLRM_GEMM_LDS_PAD", 0);
         lds += (size_t)pad;
     }
-    static bool attr_done[DLRM_MAX_DEVICES] = {};      // the attribute is per (function, device)
-    const int dev = dlrm_current_device();
-    if (!attr_done[dev]) {
-        (void)hipFuncSetAttribute((const void*)gemm3_kernel<A_KC, B_KC, TM, ARITH, ROWSUM, FRAG, TN, SCHED, NST, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done[dev] = true;
-    }
+    dlrm_lds_limit<gemm3_kernel<A_KC, B_KC, TM, ARITH, ROWSUM, FRAG, TN, SCHED, NST, EPI>>(lds);
     dim3 grid((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)splits), block(256);
     hipLaunchKernelGGL((gemm3_kernel<A_KC, B_KC, TM, ARITH, ROWSUM, FRAG, TN, SCHED, NST, EPI>), grid, block, lds, st, g);
     DLRM_LAUNCH_CHECK();
@@ -1404,12 +1399,7 @@ static int launch_route(GemmArgs& g, const GemmRoute& r, hipStream_t st) {
     if (dbg < 0) dbg = DLRM_DEBUG_ENV("DLRM_GEMM_DEBUG", 0x7fffffff);
     g.debug = dbg;
     const size_t lds = 2 * 2 * TILE_F * sizeof(float);   // 73,728 B: two workgroups per CU
-    static bool attr_done[DLRM_MAX_DEVICES] = {};
-    const int dev = dlrm_current_device();
-    if (!attr_done[dev]) {
-        (void)hipFuncSetAttribute((const void*)gemm_f32_kernel<A_KC, B_KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done[dev] = true;
-    }
+    dlrm_lds_limit<gemm_f32_kernel<A_KC, B_KC>>(lds);
     dim3 grid((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)splits), block(256);
     hipLaunchKernelGGL((gemm_f32_kernel<A_KC, B_KC>), grid, block, lds, st, g);
     DLRM_LAUNCH_CHECK();

@@ -678,12 +678,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_phased_kernel(BfArgs g) {
 
 constexpr int LDS_PL1 = 2 * STAGE_BYTES;              // 128 KiB: one workgroup per CU
 constexpr int LDS_PL3 = 2 * 2 * (3 * 256 * 32);       //  96 KiB (>= the 72 KiB of epilogue staging + bias-gradient partials)
-static void phased_attr(const void* fn, bool& done, int bytes = LDS_PL1) {
-    if (!done) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        done = true;
-    }
-}
 
 static int phased_enabled() {           // tuning builds, DLRM_BF16_PHASED=0: keep the fp32-shaped kernels everywhere (A/B runs)
     static const int enabled = DLRM_TUNE_ENV("DLRM_BF16_PHASED", 1);
@@ -715,19 +709,17 @@ int dlrm_gemm_bf16_phased(int64_t M, int N, int K, const uint16_t* A, int64_t ld
     static const int epi_on = DLRM_TUNE_ENV("DLRM_BF16_EPI", 1);
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
     if (epi_on && g.wide16 && (act == DLRM_ACT_NONE || act == DLRM_ACT_RELU)) {
-        static bool attr1_done[DLRM_MAX_DEVICES] = {}, attr2_done[DLRM_MAX_DEVICES] = {};
         if (act == DLRM_ACT_RELU) {
-            phased_attr((const void*)gemm_bf16_phased_kernel<false, 1, 2>, attr2_done[dlrm_current_device()]);
+            dlrm_lds_limit<gemm_bf16_phased_kernel<false, 1, 2>>(LDS_PL1);
             hipLaunchKernelGGL((gemm_bf16_phased_kernel<false, 1, 2>), grid, dim3(512), LDS_PL1, st, g);
         } else {
-            phased_attr((const void*)gemm_bf16_phased_kernel<false, 1, 1>, attr1_done[dlrm_current_device()]);
+            dlrm_lds_limit<gemm_bf16_phased_kernel<false, 1, 1>>(LDS_PL1);
             hipLaunchKernelGGL((gemm_bf16_phased_kernel<false, 1, 1>), grid, dim3(512), LDS_PL1, st, g);
         }
         DLRM_LAUNCH_CHECK();
         return 0;
     }
-    static bool attr_done[DLRM_MAX_DEVICES] = {};
-    phased_attr((const void*)gemm_bf16_phased_kernel<false, 1>, attr_done[dlrm_current_device()]);
+    dlrm_lds_limit<gemm_bf16_phased_kernel<false, 1>>(LDS_PL1);
     hipLaunchKernelGGL((gemm_bf16_phased_kernel<false, 1>), grid, dim3(512), LDS_PL1, st, g);
     DLRM_LAUNCH_CHECK();
     return 0;
@@ -759,8 +751,7 @@ int dlrm_gemm_bf16x6_phased(int64_t M, int N, int K, const uint16_t* A, int64_t 
     { static int dbg = -1; if (dbg < 0) dbg = DLRM_DEBUG_ENV("DLRM_BF16_DEBUG", 31); g.debug = dbg; }
 #endif
     g.wide16 = (Cp && !C && N % 8 == 0 && ldcp % 8 == 0 && planeC % 8 == 0 && dlrm_aligned16(Cp)) ? 1 : 0;
-    static bool attr_done[DLRM_MAX_DEVICES] = {};
-    phased_attr((const void*)gemm_bf16_phased_kernel<false, 3>, attr_done[dlrm_current_device()], LDS_PL3);
+    dlrm_lds_limit<gemm_bf16_phased_kernel<false, 3>>(LDS_PL3);
     hipLaunchKernelGGL((gemm_bf16_phased_kernel<false, 3>), dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(512), LDS_PL3, st, g);
     DLRM_LAUNCH_CHECK();
     return 0;
@@ -808,14 +799,12 @@ int dlrm_gemm_bf16_wgrad_phased(int64_t Mb, int N_out, int K_in, const uint16_t*
         // (a k-tile of the k-strided form holds 16 batch rows of every plane)
         if (!planes_reachable(planeZ, lddz, 16) || !planes_reachable(planeX, ldx, 16)) return DLRM_E_ALIGN;
         g.planeA = planeZ * 2; g.planeB = planeX * 2;
-        static bool attr3_done[DLRM_MAX_DEVICES] = {};
-        phased_attr((const void*)gemm_bf16_phased_kernel<true, 3, 3>, attr3_done[dlrm_current_device()], LDS_PL3);
+        dlrm_lds_limit<gemm_bf16_phased_kernel<true, 3, 3>>(LDS_PL3);
         hipLaunchKernelGGL((gemm_bf16_phased_kernel<true, 3, 3>), dim3((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)splits), dim3(512), LDS_PL3, st, g);
         DLRM_LAUNCH_CHECK();
         return 0;
     }
-    static bool attr_done[DLRM_MAX_DEVICES] = {};       // (the weight gradient's slabs always leave through the straight-line fp32 epilogue, EP = 3)
-    phased_attr((const void*)gemm_bf16_phased_kernel<true, 1, 3>, attr_done[dlrm_current_device()]);
+    dlrm_lds_limit<gemm_bf16_phased_kernel<true, 1, 3>>(LDS_PL1);      // (the weight gradient's slabs always leave through the straight-line fp32 epilogue, EP = 3)
     hipLaunchKernelGGL((gemm_bf16_phased_kernel<true, 1, 3>), dim3((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)splits), dim3(512), LDS_PL1, st, g);
     DLRM_LAUNCH_CHECK();
     return 0;

@@ -17,6 +17,8 @@
 //           grad / all-to-all send buffer), with dR[:, 0:D] added into row 0.
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -870,6 +872,9 @@ __global__ __launch_bounds__(256) void interact_bwd_dma_kernel(FeatArgs fa, Feat
     }
 }
 
+// -------------------------------------------------------------------------------------------
+// host side: a call is PLANNED (plan_fwd / plan_bwd: every check, the path, every size), then launched as the plan says
+// -------------------------------------------------------------------------------------------
 static int fill_feat(FeatArgs& fa, int F, const void* const* p, const int64_t* ld) {
     for (int f = 0; f < DLRM_MAX_FEATURES; ++f) {
         fa.p[f] = (const float*)p[f < F ? f : 0];
@@ -884,11 +889,6 @@ static int log2_exact(int x) {
     int s = 0; while ((1 << s) < x) ++s; return s;
 }
 
-static bool interact_dma_ok(int F, int D, int vec) {
-    static const int off = DLRM_TUNE_ENV("DLRM_INTERACT_PATH", 0) == 1;      // tuning builds: 1 forces the register-staged kernels
-    return !off && D == IDMA_D && F >= 1 && F <= IDMA_ROWS && vec;
-}
-
 // tuning aid (env DLRM_INTERACT_DEBUG, D = 128 forward kernels): 1 = no DMA and no waits in the sample loop (compute + stores only),
 // 2 = no multiplication and no stores (DMA only), 4 = no stores — WRONG results, timing only
 static int interact_debug() {
@@ -896,6 +896,8 @@ static int interact_debug() {
     if (dbg < 0) dbg = DLRM_DEBUG_ENV("DLRM_INTERACT_DEBUG", 7);
     return dbg;
 }
+
+constexpr size_t LDS_MAX = 160 * 1024;
 
 // forward D = 128 kernels: waves per workgroup (one workgroup per CU) and its LDS — tables, two 2 NI-row images per wave, the selector
 // slots (gather mode; in plain mode they are the slack the second 16-row tile may read into)
@@ -910,15 +912,37 @@ static size_t fwd_dma_lds(int ni, int W) {
 static int fwd_dma_waves(int ni) {
     static const int forced = DLRM_TUNE_ENV("DLRM_INTERACT_WAVES", 0);      // (tuning builds)
     int W = (forced >= 1 && forced <= 5) ? forced : 4;      // five waves fit F <= 28 but two of them then share a SIMD: 245 vs 211 us measured
-    while (W > 1 && fwd_dma_lds(ni, W) > 160 * 1024) --W;
+    while (W > 1 && fwd_dma_lds(ni, W) > LDS_MAX) --W;
     return W;
 }
 
-static int pick_grid(int64_t B) {
-    // 4 samples per workgroup pass; ~2 resident workgroups per CU x 256 CUs x 4 oversubscription
-    int64_t nb = (B + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    return (int)nb;
+// D = 128 kernels: one workgroup per CU, a sample per wave and pass
+static unsigned dma_grid(int64_t B, int W) { return (unsigned)std::min<int64_t>((B + W - 1) / W, 256); }
+// generic kernels: 4 samples per workgroup pass; ~2 resident workgroups per CU x 256 CUs x 4 oversubscription.  Behind a device predicate
+// the grid is capped (the kernels walk the batch with a grid stride): a launch that must not run still dispatches
+static unsigned generic_grid(int64_t B, bool pred) { return (unsigned)std::min<int64_t>((B + 3) / 4, pred ? 512 : 2048); }
+static int generic_lds_check(const char* who, int F, int D, size_t lds) {
+    if (lds <= LDS_MAX) return 0;
+    fprintf(stderr, "libdlrm_hip: %s: F=%d, D=%d needs %zu B of LDS (> 160 KiB)\n", who, F, D, lds);
+    return DLRM_E_RANGE;
+}
+static int pairs(int F, int self) { return (self & 1) ? F * (F + 1) / 2 : F * (F - 1) / 2; }
+// every matrix of the list can be read and written as float4
+static int feats_vec(int F, const void* const* p, const int64_t* ld) {
+    for (int f = 0; f < F; ++f) if (!dlrm_aligned16(p[f]) || ld[f] % 4) return 0;
+    return 1;
+}
+
+// f(std::integral_constant<int, n>) for n = 1 .. MAX (any other n: MAX) — the template argument NI / NB of a launch
+template <int MAX, int N = 1, typename Fn>
+static void dispatch_n(int n, Fn&& f) {
+    if constexpr (N == MAX) f(std::integral_constant<int, MAX>{});
+    else if (n == N) f(std::integral_constant<int, N>{});
+    else dispatch_n<MAX, N + 1>(n, f);
+}
+template <typename Fn>
+static void dispatch_flag(bool on, Fn&& f) {
+    if (on) f(std::true_type{}); else f(std::false_type{});
 }
 
 }  // namespace
@@ -939,14 +963,176 @@ static int fill_gather(GatherArgs& ga, int F, const void* const* gidx, const voi
     return 0;
 }
 
+// the dR row image of the D = 128 backward kernels
+static int64_t dr_image_bytes(bool gather) { return gather ? GDR_BYTES : IDMA_DR_BYTES; }
+
 // F <= 27: the dR row (D + F (F + 1) / 2 floats with self pairs, padded to 4) must fit the 2 KiB image of the gather backward
 extern "C" int dlrm_interact_gather_ok(int F, int D) {
-    return (D == IDMA_D && F >= 1 && F <= IDMA_ROWS && 4 * ((IDMA_D + F * (F + 1) / 2 + 3) & ~3) <= GDR_BYTES) ? 1 : 0;
+    return (D == IDMA_D && F >= 1 && F <= IDMA_ROWS && 4 * ((IDMA_D + F * (F + 1) / 2 + 3) & ~3) <= dr_image_bytes(true)) ? 1 : 0;
+}
+
+// "this call takes the D = 128 image (LDS-DMA) kernels", forward and backward: the shape, every feature readable as float4, and R / dR too
+static bool image_kernels(bool gather, int F, int D, int vec, const float* R, int64_t ldr) {
+    // tuning builds: 1 forces the register-staged kernels — for plain features only (gathered ones have no other kernel: the knob never applied)
+    static const int off = DLRM_TUNE_ENV("DLRM_INTERACT_PATH", 0) == 1;
+    const bool shape = gather ? dlrm_interact_gather_ok(F, D) != 0 : (!off && D == IDMA_D && F >= 1 && F <= IDMA_ROWS);
+    return shape && vec && dlrm_aligned16(R) && ldr % 4 == 0;
+}
+
+enum InteractPath { PATH_GENERIC, PATH_DMA, PATH_DMA_GATHER, PATH_DMA_GATHER_SGD };
+struct InteractPlan {
+    InteractPath path;
+    int      n;          // the template argument: NI = ceil(F / 2) of the D = 128 kernels, NB = ceil(F / 16) of the generic backward
+    int      waves;      // per workgroup
+    size_t   lds;        // dynamic LDS of a workgroup
+    unsigned grid;
+    int      vec, d4s;   // generic kernels: float4 staging; log2(D / 4) where that is a power of two, else -1
+    bool     pred;       // generic kernels: the instantiation that reads the launch predicate (the D = 128 kernels always do)
+};
+
+// The checks stand in the order the entry points have always made them: the first one that fails decides the return code.
+static int plan_fwd(InteractPlan& p, FeatArgs& fa, GatherArgs& ga, int64_t B, int F, int D, const void* const* feat, const int64_t* feat_ld,
+                    const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits, int self, const float* R,
+                    int64_t ldr, int64_t* err, DlrmPred pred) {
+    if (B <= 0 || F <= 0 || D <= 0 || !feat || !feat_ld || !R) return DLRM_E_ARG;
+    if (F > DLRM_MAX_FEATURES) {
+        fprintf(stderr, "libdlrm_hip: dlrm_interact_fwd: F=%d exceeds %d features\n", F, DLRM_MAX_FEATURES);
+        return DLRM_E_RANGE;
+    }
+    if (self < 0 || self > 2) return DLRM_E_MODE;     // 0 tril, 1 tril + diagonal, 2 torchrec triu order
+    if (ldr < D + pairs(F, self)) return DLRM_E_ARG;
+    int rc = fill_feat(fa, F, feat, feat_ld);
+    if (rc) return rc;
+    p.vec = D % 4 == 0 && feats_vec(F, feat, feat_ld);
+    p.d4s = p.vec ? log2_exact(D / 4) : -1;
+    rc = fill_gather(ga, F, gidx, goff, grows, idx_bits, err);
+    if (rc) return rc;
+    ga.pred = pred;
+    const bool gather = gidx != nullptr, image = image_kernels(gather, F, D, p.vec, R, ldr);
+    if (gather && !image) return DLRM_E_MODE;         // gathered features exist only in the D = 128 LDS-DMA kernel
+    if (image) {
+        p.path = gather ? PATH_DMA_GATHER : PATH_DMA;
+        p.n = (F + 1) / 2;
+        p.waves = fwd_dma_waves(p.n);
+        p.lds = fwd_dma_lds(p.n, p.waves);
+        p.grid = dma_grid(B, p.waves);
+        return 0;
+    }
+    const int Dp = (D + 15) & ~15;
+    p.path = PATH_GENERIC;
+    p.waves = 4;
+    p.lds = 2 * DLRM_MAX_FEATURES * sizeof(long long) + 4 * (size_t)(((F + 15) >> 4) * 16) * (Dp + 4) * sizeof(float);
+    p.pred = pred.flag != nullptr;
+    p.grid = generic_grid(B, p.pred);
+    return generic_lds_check("dlrm_interact_fwd", F, D, p.lds);
+}
+
+static int plan_bwd(InteractPlan& p, FeatArgs& fa, FeatArgs& da, GatherArgs& ga, int64_t B, int F, int D, const void* const* feat,
+                    const int64_t* feat_ld, const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits, int self,
+                    const float* dR, int64_t ldr, const void* const* dfeat, const int64_t* dfeat_ld, int64_t* err, DlrmPred pred,
+                    const uint32_t* single_mask) {
+    if (B <= 0 || F <= 0 || D <= 0 || !feat || !feat_ld || !dR || !dfeat || !dfeat_ld) return DLRM_E_ARG;
+    if (F > DLRM_MAX_FEATURES) return DLRM_E_RANGE;
+    // bits 0-1: 0 tril, 1 tril + diagonal, 2 torchrec triu order; bit 2 (DLRM_INTERACT_RELU_X, backward only): feature 0 is the output of a
+    // ReLU and dfeat_0 is multiplied by its derivative [feature 0 > 0] (the bottom tower's last act_bwd pass, dlrm_s_pytorch.py:238-241)
+    if (self < 0 || self > 7 || (self & 3) > 2) return DLRM_E_MODE;
+    if (ldr < D + pairs(F, self)) return DLRM_E_ARG;
+    int rc = fill_feat(fa, F, feat, feat_ld);
+    if (rc) return rc;
+    rc = fill_feat(da, F, dfeat, dfeat_ld);
+    if (rc) return rc;
+    p.vec = D % 4 == 0 && feats_vec(F, feat, feat_ld);
+    p.d4s = p.vec ? log2_exact(D / 4) : -1;
+    rc = fill_gather(ga, F, gidx, goff, grows, idx_bits, err);
+    if (rc) return rc;
+    ga.pred = pred;
+    const bool gather = gidx != nullptr;
+    const bool image = image_kernels(gather, F, D, p.vec, dR, ldr) && feats_vec(F, dfeat, dfeat_ld) &&
+                       ldr * 4 < dr_image_bytes(gather);      // (strictly: the image's last word stays zero)
+    if (gather && !image) return DLRM_E_MODE;
+    if (single_mask && !gather) return DLRM_E_ARG;
+    p.waves = 4;
+    if (image) {
+        p.path = !gather ? PATH_DMA : single_mask ? PATH_DMA_GATHER_SGD : PATH_DMA_GATHER;
+        p.n = (F + 1) / 2;
+        p.lds = 7 * DLRM_MAX_FEATURES * sizeof(long long) +
+                4 * (2 * (size_t)IDMA_IMG + 2 * (size_t)dr_image_bytes(gather) + (gather ? (size_t)GSEL_WAVE_BYTES : 0));
+        p.grid = dma_grid(B, p.waves);
+        return 0;
+    }
+    const int Dp = (D + 15) & ~15;
+    p.path = PATH_GENERIC;
+    p.n = (F + 15) >> 4;
+    p.lds = 4 * DLRM_MAX_FEATURES * sizeof(long long) + 4 * ((size_t)F * (Dp + 16) + (size_t)F * (p.n * 16 + 1)) * sizeof(float);
+    p.pred = pred.flag != nullptr;
+    p.grid = generic_grid(B, p.pred);
+    rc = generic_lds_check("dlrm_interact_bwd", F, D, p.lds);
+    return rc ? rc : p.n > 4 ? DLRM_E_RANGE : 0;       // (NB = 1 .. 4 are built)
+}
+
+// one launch as the plan says: the kernel's dynamic-LDS limit, then the kernel
+template <auto Kernel, typename... Args>
+static void plan_launch(const InteractPlan& p, void* stream, const Args&... args) {
+    dlrm_lds_limit<Kernel>(p.lds);
+    hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(64 * p.waves), p.lds, (hipStream_t)stream, args...);
 }
 
 static int interact_fwd_impl(int64_t B, int F, int D, const void* const* feat_host, const int64_t* feat_ld_host,
                              const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits,
-                             int self_interaction, float* R, int64_t ldr, int64_t* err, void* stream, DlrmPred pred = DlrmPred{nullptr, 0});
+                             int self_interaction, float* R, int64_t ldr, int64_t* err, void* stream, DlrmPred pred = DlrmPred{nullptr, 0}) {
+    InteractPlan p = {};
+    FeatArgs fa;
+    GatherArgs ga;          // (the kernels' argument blocks: the plan functions fill them)
+    const int rc = plan_fwd(p, fa, ga, B, F, D, feat_host, feat_ld_host, gidx, goff, grows, idx_bits, self_interaction, R, ldr, err, pred);
+    if (rc) return rc;
+    if (p.path == PATH_GENERIC)
+        dispatch_flag(p.pred, [&](auto predicated) {
+            plan_launch<interact_fwd_kernel<decltype(predicated)::value>>(p, stream, fa, (long long)B, F, D, self_interaction & 3, R,
+                                                                          (long long)ldr, p.vec, p.d4s, pred);
+        });
+    else
+        dispatch_flag(p.path == PATH_DMA_GATHER, [&](auto gather) {
+            dispatch_n<IDMA_MAXI>(p.n, [&](auto ni) {
+                plan_launch<interact_fwd_dma_kernel<decltype(ni)::value, decltype(gather)::value>>(
+                    p, stream, fa, ga, (long long)B, F, (self_interaction & 3) | (interact_debug() << 6), R, (long long)ldr);
+            });
+        });
+    DLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+static int interact_bwd_impl(int64_t B, int F, int D, const void* const* feat_host, const int64_t* feat_ld_host,
+                             const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits,
+                             int self_interaction, const float* dR, int64_t ldr, void* const* dfeat_host,
+                             const int64_t* dfeat_ld_host, int64_t* err, void* stream, DlrmPred pred = DlrmPred{nullptr, 0},
+                             const uint32_t* single_mask = nullptr, DlrmStep neg_lr = DlrmStep{0.f, nullptr, 0.f}) {
+    InteractPlan p = {};
+    FeatArgs fa, da;
+    GatherArgs ga;
+    const int rc = plan_bwd(p, fa, da, ga, B, F, D, feat_host, feat_ld_host, gidx, goff, grows, idx_bits, self_interaction, dR, ldr,
+                            (const void* const*)dfeat_host, dfeat_ld_host, err, pred, single_mask);
+    if (rc) return rc;
+    if (p.path == PATH_GENERIC)
+        dispatch_n<4>(p.n, [&](auto nb) {
+            dispatch_flag(p.pred, [&](auto predicated) {
+                plan_launch<interact_bwd_kernel<decltype(nb)::value, decltype(predicated)::value>>(
+                    p, stream, fa, da, (long long)B, F, D, self_interaction & 7, dR, (long long)ldr, p.vec, p.d4s, pred);
+            });
+        });
+    else
+        dispatch_n<IDMA_MAXI>(p.n, [&](auto ni) {
+            // (single_mask and neg_lr are the kernel's defaults, NULL and zero, on every path but the last)
+            auto launch = [&](auto gather, auto upd) {
+                plan_launch<interact_bwd_dma_kernel<decltype(ni)::value, decltype(gather)::value, decltype(upd)::value>>(
+                    p, stream, fa, da, ga, (long long)B, F, self_interaction & 7, dR, (long long)ldr, (const unsigned*)single_mask, neg_lr);
+            };
+            if (p.path == PATH_DMA_GATHER_SGD) launch(std::true_type{}, std::true_type{});
+            else if (p.path == PATH_DMA_GATHER) launch(std::true_type{}, std::false_type{});
+            else launch(std::false_type{}, std::false_type{});
+        });
+    DLRM_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int dlrm_interact_fwd(int64_t B, int F, int D, const void* const* feat_host,
                                  const int64_t* feat_ld_host, int self_interaction, float* R,
@@ -977,98 +1163,6 @@ extern "C" int dlrm_interact_fwd_pred(int64_t B, int F, int D, const void* const
     return interact_fwd_impl(B, F, D, feat_host, feat_ld_host, index_host, offsets_host, rows_host, idx_bits, self_interaction, R,
                              ldr, err, stream, DlrmPred{(const int*)pred_flag, pred_nonzero});
 }
-
-static int interact_fwd_impl(int64_t B, int F, int D, const void* const* feat_host, const int64_t* feat_ld_host,
-                             const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits,
-                             int self_interaction, float* R, int64_t ldr, int64_t* err, void* stream, DlrmPred pred) {
-    if (B <= 0 || F <= 0 || D <= 0 || !feat_host || !feat_ld_host || !R) return DLRM_E_ARG;
-    if (F > DLRM_MAX_FEATURES) {
-        fprintf(stderr, "libdlrm_hip: dlrm_interact_fwd: F=%d exceeds %d features\n", F, DLRM_MAX_FEATURES);
-        return DLRM_E_RANGE;
-    }
-    if (self_interaction < 0 || self_interaction > 2) return DLRM_E_MODE;     // 0 tril, 1 tril + diagonal, 2 torchrec triu order
-    const int P = (self_interaction & 1) ? F * (F + 1) / 2 : F * (F - 1) / 2;
-    if (ldr < D + P) return DLRM_E_ARG;
-    FeatArgs fa;
-    int rc = fill_feat(fa, F, feat_host, feat_ld_host);
-    if (rc) return rc;
-    int vec = (D % 4 == 0);
-    for (int f = 0; f < F; ++f) vec = vec && dlrm_aligned16(feat_host[f]) && (feat_ld_host[f] % 4 == 0);
-    GatherArgs ga;
-    rc = fill_gather(ga, F, gidx, goff, grows, idx_bits, err);
-    if (rc) return rc;
-    ga.pred = pred;
-    if (gidx) {          // gathered features exist only in the D = 128 LDS-DMA kernel
-        if (!(dlrm_interact_gather_ok(F, D) && vec && dlrm_aligned16(R) && ldr % 4 == 0)) return DLRM_E_MODE;
-        const int ni = (F + 1) / 2;
-        const int W = fwd_dma_waves(ni);
-        const size_t lds = fwd_dma_lds(ni, W);
-        int64_t nb = (B + W - 1) / W; if (nb > 256) nb = 256;
-#define FWD_G(NIV)                                                                                           \
-        do {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)interact_fwd_dma_kernel<NIV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((interact_fwd_dma_kernel<NIV, true>), dim3((unsigned)nb), dim3(64 * W), lds, (hipStream_t)stream, fa, ga, \
-                               (long long)B, F, (self_interaction & 3) | (interact_debug() << 6), R, (long long)ldr); \
-        } while (0)
-        switch (ni) {
-            case 1: FWD_G(1); break;   case 2: FWD_G(2); break;   case 3: FWD_G(3); break;   case 4: FWD_G(4); break;
-            case 5: FWD_G(5); break;   case 6: FWD_G(6); break;   case 7: FWD_G(7); break;   case 8: FWD_G(8); break;
-            case 9: FWD_G(9); break;   case 10: FWD_G(10); break; case 11: FWD_G(11); break; case 12: FWD_G(12); break;
-            case 13: FWD_G(13); break; case 14: FWD_G(14); break; case 15: FWD_G(15); break; default: FWD_G(16); break;
-        }
-#undef FWD_G
-        DLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (interact_dma_ok(F, D, vec) && dlrm_aligned16(R) && ldr % 4 == 0) {
-        const int ni = (F + 1) / 2;
-        const int W = fwd_dma_waves(ni);
-        const size_t lds = fwd_dma_lds(ni, W);                                                      // one workgroup per CU
-        int64_t nb = (B + W - 1) / W; if (nb > 256) nb = 256;
-#define FWD_DMA(NIV)                                                                                         \
-        do {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)interact_fwd_dma_kernel<NIV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((interact_fwd_dma_kernel<NIV, false>), dim3((unsigned)nb), dim3(64 * W), lds, (hipStream_t)stream, fa, ga, \
-                               (long long)B, F, (self_interaction & 3) | (interact_debug() << 6), R, (long long)ldr); \
-        } while (0)
-        switch (ni) {
-            case 1: FWD_DMA(1); break;   case 2: FWD_DMA(2); break;   case 3: FWD_DMA(3); break;   case 4: FWD_DMA(4); break;
-            case 5: FWD_DMA(5); break;   case 6: FWD_DMA(6); break;   case 7: FWD_DMA(7); break;   case 8: FWD_DMA(8); break;
-            case 9: FWD_DMA(9); break;   case 10: FWD_DMA(10); break; case 11: FWD_DMA(11); break; case 12: FWD_DMA(12); break;
-            case 13: FWD_DMA(13); break; case 14: FWD_DMA(14); break; case 15: FWD_DMA(15); break; default: FWD_DMA(16); break;
-        }
-#undef FWD_DMA
-        DLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    const int Dp = (D + 15) & ~15;
-    const size_t lds = 2 * DLRM_MAX_FEATURES * sizeof(long long) + 4 * (size_t)(((F + 15) >> 4) * 16) * (Dp + 4) * sizeof(float);
-    if (lds > 160 * 1024) {
-        fprintf(stderr, "libdlrm_hip: dlrm_interact_fwd: F=%d, D=%d needs %zu B of LDS (> 160 KiB)\n", F, D, lds);
-        return DLRM_E_RANGE;
-    }
-    if (pred.flag) {           // the generic kernel behind a device predicate: a capped grid, since a launch that must not run still dispatches
-        const int gp = pick_grid(B) < 512 ? pick_grid(B) : 512;
-        (void)hipFuncSetAttribute((const void*)interact_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(interact_fwd_kernel<true>, dim3(gp), dim3(256), lds, (hipStream_t)stream, fa,
-                           (long long)B, F, D, self_interaction & 3, R, (long long)ldr, vec,
-                           vec ? log2_exact(D / 4) : -1, pred);
-        DLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    (void)hipFuncSetAttribute((const void*)interact_fwd_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(interact_fwd_kernel<>, dim3(pick_grid(B)), dim3(256), lds, (hipStream_t)stream, fa,
-                       (long long)B, F, D, self_interaction & 3, R, (long long)ldr, vec,
-                       vec ? log2_exact(D / 4) : -1, pred);
-    DLRM_LAUNCH_CHECK();
-    return 0;
-}
-
-static int interact_bwd_impl(int64_t B, int F, int D, const void* const* feat_host, const int64_t* feat_ld_host,
-                             const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits,
-                             int self_interaction, const float* dR, int64_t ldr, void* const* dfeat_host,
-                             const int64_t* dfeat_ld_host, int64_t* err, void* stream, DlrmPred pred = DlrmPred{nullptr, 0},
-                             const uint32_t* single_mask = nullptr, DlrmStep neg_lr = DlrmStep{0.f, nullptr, 0.f});
 
 extern "C" int dlrm_interact_bwd(int64_t B, int F, int D, const void* const* feat_host,
                                  const int64_t* feat_ld_host, int self_interaction, const float* dR,
@@ -1115,102 +1209,4 @@ extern "C" int dlrm_interact_bwd_gather_sgd(int64_t B, int F, int D, const void*
     return interact_bwd_impl(B, F, D, feat_host, feat_ld_host, index_host, offsets_host, rows_host, idx_bits, self_interaction, dR,
                              ldr, dfeat_host, dfeat_ld_host, err, stream, DlrmPred{(const int*)pred_flag, pred_nonzero}, single_mask,
                              dlrm_step_neg(lr, lr_dev));
-}
-
-static int interact_bwd_impl(int64_t B, int F, int D, const void* const* feat_host, const int64_t* feat_ld_host,
-                             const void* const* gidx, const void* const* goff, const int64_t* grows, int idx_bits,
-                             int self_interaction, const float* dR, int64_t ldr, void* const* dfeat_host,
-                             const int64_t* dfeat_ld_host, int64_t* err, void* stream, DlrmPred pred, const uint32_t* single_mask,
-                             DlrmStep neg_lr) {
-    if (B <= 0 || F <= 0 || D <= 0 || !feat_host || !feat_ld_host || !dR || !dfeat_host || !dfeat_ld_host)
-        return DLRM_E_ARG;
-    if (F > DLRM_MAX_FEATURES) return DLRM_E_RANGE;
-    // bits 0-1: 0 tril, 1 tril + diagonal, 2 torchrec triu order; bit 2 (DLRM_INTERACT_RELU_X, backward only): feature 0 is the output of a
-    // ReLU and dfeat_0 is multiplied by its derivative [feature 0 > 0] (the bottom tower's last act_bwd pass, dlrm_s_pytorch.py:238-241)
-    if (self_interaction < 0 || self_interaction > 7 || (self_interaction & 3) > 2) return DLRM_E_MODE;
-    const int P = (self_interaction & 1) ? F * (F + 1) / 2 : F * (F - 1) / 2;
-    if (ldr < D + P) return DLRM_E_ARG;
-    FeatArgs fa, da;
-    int rc = fill_feat(fa, F, feat_host, feat_ld_host);
-    if (rc) return rc;
-    rc = fill_feat(da, F, (const void* const*)dfeat_host, dfeat_ld_host);
-    if (rc) return rc;
-    int vec = (D % 4 == 0);
-    for (int f = 0; f < F; ++f) vec = vec && dlrm_aligned16(feat_host[f]) && (feat_ld_host[f] % 4 == 0);
-    {
-        int dvec = 1;
-        for (int f = 0; f < F; ++f) dvec = dvec && dlrm_aligned16(dfeat_host[f]) && (dfeat_ld_host[f] % 4 == 0);
-        GatherArgs ga;
-        rc = fill_gather(ga, F, gidx, goff, grows, idx_bits, err);
-        if (rc) return rc;
-        ga.pred = pred;
-        const bool dma_path = (gidx ? (dlrm_interact_gather_ok(F, D) && vec) : interact_dma_ok(F, D, vec)) && dvec && dlrm_aligned16(dR) &&
-                              ldr % 4 == 0 && ldr * 4 < (gidx ? GDR_BYTES : IDMA_DR_BYTES);      // (strictly: the image's last word stays zero)
-        if (gidx && !dma_path) return DLRM_E_MODE;
-        if (single_mask && !gidx) return DLRM_E_ARG;
-        if (dma_path) {
-            const size_t lds_dma = 7 * DLRM_MAX_FEATURES * sizeof(long long) +
-                                   (gidx ? 4 * (2 * (size_t)IDMA_IMG + 2 * (size_t)GDR_BYTES + (size_t)GSEL_WAVE_BYTES)
-                                         : 4 * (2 * (size_t)IDMA_IMG + 2 * (size_t)IDMA_DR_BYTES));
-            int64_t nb = (B + 3) / 4; if (nb > 256) nb = 256;
-            const int ni = (F + 1) / 2;
-#define BWD_DMA(NIV)                                                                                         \
-            do {                                                                                             \
-                if (gidx && single_mask) {                                                                   \
-                    (void)hipFuncSetAttribute((const void*)interact_bwd_dma_kernel<NIV, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dma); \
-                    hipLaunchKernelGGL((interact_bwd_dma_kernel<NIV, true, true>), dim3((unsigned)nb), dim3(256), lds_dma, (hipStream_t)stream, fa, da, ga, \
-                                       (long long)B, F, self_interaction & 7, dR, (long long)ldr, (const unsigned*)single_mask, neg_lr); \
-                } else if (gidx) {                                                                           \
-                    (void)hipFuncSetAttribute((const void*)interact_bwd_dma_kernel<NIV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dma); \
-                    hipLaunchKernelGGL((interact_bwd_dma_kernel<NIV, true>), dim3((unsigned)nb), dim3(256), lds_dma, (hipStream_t)stream, fa, da, ga, \
-                                       (long long)B, F, self_interaction & 7, dR, (long long)ldr);       \
-                } else {                                                                                     \
-                    (void)hipFuncSetAttribute((const void*)interact_bwd_dma_kernel<NIV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dma); \
-                    hipLaunchKernelGGL((interact_bwd_dma_kernel<NIV, false>), dim3((unsigned)nb), dim3(256), lds_dma, (hipStream_t)stream, fa, da, ga, \
-                                       (long long)B, F, self_interaction & 7, dR, (long long)ldr);       \
-                }                                                                                            \
-            } while (0)
-            switch (ni) {
-                case 1: BWD_DMA(1); break;   case 2: BWD_DMA(2); break;   case 3: BWD_DMA(3); break;   case 4: BWD_DMA(4); break;
-                case 5: BWD_DMA(5); break;   case 6: BWD_DMA(6); break;   case 7: BWD_DMA(7); break;   case 8: BWD_DMA(8); break;
-                case 9: BWD_DMA(9); break;   case 10: BWD_DMA(10); break; case 11: BWD_DMA(11); break; case 12: BWD_DMA(12); break;
-                case 13: BWD_DMA(13); break; case 14: BWD_DMA(14); break; case 15: BWD_DMA(15); break; default: BWD_DMA(16); break;
-            }
-#undef BWD_DMA
-            DLRM_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    const int Dp = (D + 15) & ~15, NB = (F + 15) >> 4, rows = NB * 16;
-    const size_t lds = 4 * DLRM_MAX_FEATURES * sizeof(long long) +
-                       4 * ((size_t)F * (Dp + 16) + (size_t)F * (rows + 1)) * sizeof(float);
-    if (lds > 160 * 1024) {
-        fprintf(stderr, "libdlrm_hip: dlrm_interact_bwd: F=%d, D=%d needs %zu B of LDS (> 160 KiB)\n", F, D, lds);
-        return DLRM_E_RANGE;
-    }
-    const int d4s = vec ? log2_exact(D / 4) : -1;
-    dim3 grid(pick_grid(B)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define BWD_LAUNCH(NBV)                                                                                  \
-    do {                                                                                                 \
-        if (pred.flag) {       /* behind a device predicate: a capped grid (the kernel walks the batch with a grid stride) */ \
-            (void)hipFuncSetAttribute((const void*)interact_bwd_kernel<NBV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((interact_bwd_kernel<NBV, true>), dim3(grid.x < 512u ? grid.x : 512u), block, lds, st, fa, da, (long long)B, F, D, \
-                               self_interaction & 7, dR, (long long)ldr, vec, d4s, pred);            \
-            break;                                                                                       \
-        }                                                                                                \
-        (void)hipFuncSetAttribute((const void*)interact_bwd_kernel<NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(interact_bwd_kernel<NBV>, grid, block, lds, st, fa, da, (long long)B, F, D,   \
-                           self_interaction & 7, dR, (long long)ldr, vec, d4s, pred);                \
-    } while (0)
-    switch (NB) {
-        case 1: BWD_LAUNCH(1); break;
-        case 2: BWD_LAUNCH(2); break;
-        case 3: BWD_LAUNCH(3); break;
-        case 4: BWD_LAUNCH(4); break;
-        default: return DLRM_E_RANGE;
-    }
-#undef BWD_LAUNCH
-    DLRM_LAUNCH_CHECK();
-    return 0;
 }

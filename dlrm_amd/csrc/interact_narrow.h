@@ -440,7 +440,7 @@ constexpr size_t narrow_lds(bool bwd, int ntab = 4) {
 template <typename S, int D, int NB, typename IT>
 void launch_fwd(const typename S::Args& na, const float* x, long long x_ld, long long B, int F, int self, float* R, long long ldr, hipStream_t st) {
     constexpr size_t lds = narrow_lds<D, NB>(false, S::NTAB);
-    (void)hipFuncSetAttribute((const void*)interact_fwd_narrow_kernel<S, D, NB, IT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    dlrm_lds_limit<interact_fwd_narrow_kernel<S, D, NB, IT>>(lds);
     hipLaunchKernelGGL((interact_fwd_narrow_kernel<S, D, NB, IT>), dim3((unsigned)gather_grid(B, lds)), dim3(64 * GC_WAVES), lds, st, na, x, x_ld,
                        B, F, self, R, ldr);
 }
@@ -449,7 +449,7 @@ template <typename S, int D, int NB, typename IT>
 void launch_bwd(const typename S::Args& na, const float* x, long long x_ld, long long B, int F, int self, const float* dR, long long ldr, float* dx,
                 long long dx_ld, float* dE, long long dE_ld, hipStream_t st) {
     constexpr size_t lds = narrow_lds<D, NB>(true, S::NTAB);
-    (void)hipFuncSetAttribute((const void*)interact_bwd_narrow_kernel<S, D, NB, IT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    dlrm_lds_limit<interact_bwd_narrow_kernel<S, D, NB, IT>>(lds);
     hipLaunchKernelGGL((interact_bwd_narrow_kernel<S, D, NB, IT>), dim3((unsigned)gather_grid(B, lds)), dim3(64 * GC_WAVES), lds, st, na, x, x_ld,
                        B, F, self, dR, ldr, dx, dx_ld, dE, dE_ld);
 }

@@ -530,7 +530,7 @@ extern "C" int dlrm_tower_fwd(int64_t M, int L, const int* widths, const int* ac
         a.Y[l] = (float*)Y_host[l]; a.ldy[l] = ldy_host[l];
     }
     const size_t lds = ((size_t)2 * TW_ROWS * a.ld_lds + TW_WST_FLOATS) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)tower_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    dlrm_lds_limit<tower_fwd_kernel>(lds);          // (lds follows the widths: raised when a wider tower comes)
     hipLaunchKernelGGL(tower_fwd_kernel, dim3((unsigned)((M + TW_ROWS - 1) / TW_ROWS)), dim3(TW_THREADS), lds, (hipStream_t)stream, a);
     DLRM_LAUNCH_CHECK();
     return 0;
@@ -556,7 +556,7 @@ extern "C" int dlrm_tower_bwd(int64_t M, int L, const int* widths, const int* ac
         a.dZ[l] = (float*)dZ_host[l]; a.lddz[l] = lddz_host[l];
     }
     const size_t lds = ((size_t)2 * TW_ROWS * a.ld_lds + TW_WST_FLOATS) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)tower_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    dlrm_lds_limit<tower_bwd_kernel>(lds);
     hipLaunchKernelGGL(tower_bwd_kernel, dim3((unsigned)((M + TW_ROWS - 1) / TW_ROWS)), dim3(TW_THREADS), lds, (hipStream_t)stream, a);
     DLRM_LAUNCH_CHECK();
     return 0;
