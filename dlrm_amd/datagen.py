@@ -18,6 +18,12 @@ from . import _lib, ops
 
 
 class UniformBatchGenerator:
+    """One generator per run: `batch(B, batch_no)` returns batch `batch_no` of the stream keyed by `seed`.
+
+    `index_dtype=torch.int32` holds ids up to 2^31 - 1 only: the constructor raises RuntimeError for a table of more than
+    2^31 rows (largest id `rows - 1`), which the kernel's narrowing store would otherwise truncate silently.  A table of
+    exactly 2^31 rows is the largest that int32 ids address."""
+
     def __init__(self, m_den: int, ln_emb: Sequence[int], num_indices_per_lookup: int = 10,
                  num_indices_per_lookup_fixed: bool = False, round_targets: bool = True, seed: int = 123,
                  device=None, index_dtype: torch.dtype = torch.int64):
@@ -29,6 +35,8 @@ class UniformBatchGenerator:
         self.device = torch.device(device if device is not None else "cuda:0")
         if self.device.type != "cuda":
             raise RuntimeError("dlrm_amd.datagen: the generator runs on the GPU only (no CPU fallback)")
+        if index_dtype == torch.int32 and any(n > 2 ** 31 for n in self.rows):
+            raise RuntimeError("dlrm_amd.datagen: int32 indices cannot address a table of more than 2**31 rows; use index_dtype=torch.int64")
         self.index_dtype = index_dtype
         self._ws = None
 

@@ -978,7 +978,8 @@ int dlrm_gen_uniform_dense(int64_t n, float* x, int round_values, uint64_t seed,
 
 /* Criteo-Terabyte binary records -> model inputs on the device.  Replaces CriteoBinDataset.__getitem__ +
  * _transform_features (data_loader_terabyte.py:233-248, 74-93).  raw: device int32 [B, 40] = label | 13 dense | 26 ids.
- *   X[b, 0:13] = logf(float(dense) + 1);  indices[t*ld_idx + b] = id_t mod max_ind_range (if > 0; result in [0, m));
+ *   X[b, 0:13] = float(log(double(float(dense) + 1))): the fp32 sum, its logarithm taken in fp64 and rounded once;
+ *   indices[t*ld_idx + b] = id_t mod max_ind_range (if > 0; result in [0, m));
  *   offsets[t*ld_idx + b] = b;  target[b] = float(label).   indices/offsets: int32 or int64 [26, ld_idx >= B]. */
 int dlrm_criteo_bin_transform(int64_t B, const int32_t* raw, int64_t max_ind_range, int idx_bits, float* X,
                               int64_t ldx, void* indices, void* offsets, int64_t ld_idx, float* target, void* stream);
