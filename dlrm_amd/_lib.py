@@ -112,6 +112,11 @@ SIGNATURES = {
                                      _f32, _vp, _i32, C.c_uint64, _i32, _vp, _i64, _vp, _vp]),
     "dlrm_emb_bwd_rowwise_adagrad_bf16": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32,
                                                  _vp, _i64, _f32, _vp, _f32, _i32, C.c_uint64, _i32, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_bwd_sgd_bf16_devkey": (_i32, [_i32, _i64, _i32, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32, _vp, _i64,
+                                            _f32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "dlrm_emb_bwd_rowwise_adagrad_bf16_devkey": (_i32, [_i32, _i64, _i32, _pp, _pp, _pi64, _pp, _pp, _pi64, _pp, _i32,
+                                                        _vp, _i64, _f32, _vp, _f32, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "dlrm_philox_key_next": (_i32, [C.c_uint64, _vp, _vp, _vp]),
     "dlrm_interact_fwd": (_i32, [_i64, _i32, _i32, _pp, _pi64, _i32, _vp, _i64, _vp]),
     "dlrm_interact_bwd": (_i32, [_i64, _i32, _i32, _pp, _pi64, _i32, _vp, _i64, _pp, _pi64, _vp]),
     "dlrm_proj_interact_fwd": (_i32, [_i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),

@@ -91,7 +91,18 @@ __global__ __launch_bounds__(256) void emb_fwd_bf16_scalar_kernel(EmbArgs a, lon
 // -------------------------------------------------------------------------------------------
 // rounding
 // -------------------------------------------------------------------------------------------
-struct RoundArgs { int stochastic; unsigned k0, k1; unsigned tbase; };   // tbase: index of the launch group's first table in the caller's list
+// tbase: index of the launch group's first table in the caller's list.  key_dev != nullptr: the Philox key is READ FROM DEVICE MEMORY when the
+// kernel runs (the *_devkey calls: what a captured HIP graph needs, as DlrmStep's `dev` is for the step size), else it is (k0, k1) by value.
+struct RoundArgs { int stochastic; unsigned k0, k1; unsigned tbase; const unsigned long long* key_dev; };
+
+// the call's rounding arguments with the key in registers: one uniform 8-byte load per workgroup when the key lives on the device
+__device__ __forceinline__ RoundArgs round_args_now(RoundArgs ra) {
+    if (ra.key_dev) {
+        const unsigned long long k = *ra.key_dev;
+        ra.k0 = (unsigned)(k & 0xFFFFFFFFull); ra.k1 = (unsigned)(k >> 32);
+    }
+    return ra;
+}
 
 __device__ __forceinline__ void philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned (&out)[4]) {
     unsigned c[4] = {c0, c1, c2, c3};
@@ -213,9 +224,10 @@ __global__ __launch_bounds__(256, (kBf16GroupsMinWaves<VEC, LPB, NCH, KT, ADA>))
                                                           const KT* __restrict__ keys, const unsigned* __restrict__ vals,
                                                           const unsigned* __restrict__ bag_of,
                                                           const float* __restrict__ dout, long long dout_ld,
-                                                          DlrmStep step_, float eps, RoundArgs ra, float* __restrict__ edge_first,
+                                                          DlrmStep step_, float eps, RoundArgs ra_, float* __restrict__ edge_first,
                                                           float* __restrict__ edge_last) {
     const float step = step_;            // (by value, or read from the device scalar: common.h DlrmStep)
+    const RoundArgs ra = round_args_now(ra_);
     WALK_STAGE_TABLES(sa, aa);
     walk_groups<VEC, LPB, NCH, KT, kC>(wt, L, D, row_bits, keys, vals, bag_of, dout, dout_ld, Bf16Update<ADA>{step, eps, ra}, edge_first,
                                        edge_last);
@@ -223,9 +235,10 @@ __global__ __launch_bounds__(256, (kBf16GroupsMinWaves<VEC, LPB, NCH, KT, ADA>))
 
 template <int VEC, int LPB, int NCH, typename KT, bool ADA>
 __global__ __launch_bounds__(256) void bf16_fixup_kernel(SortedArgs sa, StateArgs aa, long long L, int D, int row_bits,
-                                                         const KT* __restrict__ keys, DlrmStep step_, float eps, RoundArgs ra,
+                                                         const KT* __restrict__ keys, DlrmStep step_, float eps, RoundArgs ra_,
                                                          const float* __restrict__ edge_first, const float* __restrict__ edge_last) {
     const float step = step_;
+    const RoundArgs ra = round_args_now(ra_);
     walk_fixup<VEC, LPB, NCH, KT>(sa, aa.state, L, D, row_bits, keys, Bf16Update<ADA>{step, eps, ra}, edge_first, edge_last);
 }
 
@@ -233,8 +246,8 @@ template <bool ADA>
 static int bwd_bf16_impl(const char* what, int T, int64_t B, int D, void* const* weight_host, void* const* state_host,
                          const int64_t* rows_host, const void* const* indices_host, const void* const* offsets_host,
                          const int64_t* nnz_host, const void* const* psw_host, int idx_bits, const float* dout, int64_t dout_ld,
-                         DlrmStep step, float eps, int rounding, uint64_t seed, int table0, void* workspace, int64_t workspace_bytes,
-                         int64_t* err, void* stream) {
+                         DlrmStep step, float eps, int rounding, uint64_t seed, const uint64_t* seed_dev, int table0, void* workspace,
+                         int64_t workspace_bytes, int64_t* err, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0 || !weight_host || (ADA && !state_host) || !rows_host || !indices_host || !offsets_host || !nnz_host ||
         !dout || dout_ld < (int64_t)T * D)
         return DLRM_E_ARG;
@@ -258,6 +271,7 @@ static int bwd_bf16_impl(const char* what, int T, int64_t B, int D, void* const*
         for (int k = 0; k < DLRM_MAX_TABLES_PER_LAUNCH; ++k) aa.state[k] = ADA ? (float*)state_host[w.g->t0 + (k < w.g->n ? k : 0)] : nullptr;
         RoundArgs ra;
         ra.stochastic = rounding; ra.k0 = (unsigned)(seed & 0xFFFFFFFFull); ra.k1 = (unsigned)(seed >> 32); ra.tbase = (unsigned)(table0 + w.g->t0);
+        ra.key_dev = (const unsigned long long*)seed_dev;
         hipLaunchKernelGGL((bf16_groups_kernel<V, LP, NC, KT, ADA>), w.grid, w.block, 0, st, w.sa, aa, (long long)w.g->L, D, w.g->row_bits, w.keys, w.vals,
                            w.bag_of, dout, (long long)dout_ld, step, eps, ra, w.edge_first, w.edge_last);
         DLRM_LAUNCH_CHECK();
@@ -343,8 +357,8 @@ extern "C" int dlrm_emb_bwd_sgd_bf16(int T, int64_t B, int D, void* const* weigh
                                      const float* lr_dev, int rounding, uint64_t seed, int table0, void* workspace, int64_t workspace_bytes,
                                      int64_t* err, void* stream) {
     return bwd_bf16_impl<false>("dlrm_emb_bwd_sgd_bf16", T, B, D, weight_host, nullptr, rows_host, indices_host, offsets_host, nnz_host, psw_host,
-                                idx_bits, dout, dout_ld, dlrm_step_neg(lr, lr_dev), 0.f, rounding, seed, table0, workspace, workspace_bytes, err,
-                                stream);
+                                idx_bits, dout, dout_ld, dlrm_step_neg(lr, lr_dev), 0.f, rounding, seed, nullptr, table0, workspace, workspace_bytes,
+                                err, stream);
 }
 
 extern "C" int dlrm_emb_bwd_rowwise_adagrad_bf16(int T, int64_t B, int D, void* const* weight_host, void* const* state_host,
@@ -354,6 +368,58 @@ extern "C" int dlrm_emb_bwd_rowwise_adagrad_bf16(int T, int64_t B, int D, void* 
                                                  int rounding, uint64_t seed, int table0, void* workspace, int64_t workspace_bytes,
                                                  int64_t* err, void* stream) {
     return bwd_bf16_impl<true>("dlrm_emb_bwd_rowwise_adagrad_bf16", T, B, D, weight_host, state_host, rows_host, indices_host, offsets_host,
-                               nnz_host, psw_host, idx_bits, dout, dout_ld, dlrm_step_pos(lr, lr_dev), eps, rounding, seed, table0, workspace,
-                               workspace_bytes, err, stream);
+                               nnz_host, psw_host, idx_bits, dout, dout_ld, dlrm_step_pos(lr, lr_dev), eps, rounding, seed, nullptr, table0,
+                               workspace, workspace_bytes, err, stream);
+}
+
+// The two update calls with the Philox key READ FROM DEVICE MEMORY when the kernels run (seed_dev: 8-byte aligned device uint64): the same
+// kernels, the same bits as the by-value calls given the same key.  What a captured whole-step graph takes: dlrm_philox_key_next writes a
+// fresh key in front of every replayed update.
+extern "C" int dlrm_emb_bwd_sgd_bf16_devkey(int T, int64_t B, int D, void* const* weight_host, const int64_t* rows_host,
+                                            const void* const* indices_host, const void* const* offsets_host, const int64_t* nnz_host,
+                                            const void* const* psw_host, int idx_bits, const float* dout, int64_t dout_ld, float lr,
+                                            const float* lr_dev, int rounding, const uint64_t* seed_dev, int table0, void* workspace,
+                                            int64_t workspace_bytes, int64_t* err, void* stream) {
+    if (!seed_dev) return DLRM_E_ARG;
+    if (((uintptr_t)seed_dev) & 7u) return DLRM_E_ALIGN;
+    return bwd_bf16_impl<false>("dlrm_emb_bwd_sgd_bf16_devkey", T, B, D, weight_host, nullptr, rows_host, indices_host, offsets_host, nnz_host,
+                                psw_host, idx_bits, dout, dout_ld, dlrm_step_neg(lr, lr_dev), 0.f, rounding, 0, seed_dev, table0, workspace,
+                                workspace_bytes, err, stream);
+}
+
+extern "C" int dlrm_emb_bwd_rowwise_adagrad_bf16_devkey(int T, int64_t B, int D, void* const* weight_host, void* const* state_host,
+                                                        const int64_t* rows_host, const void* const* indices_host,
+                                                        const void* const* offsets_host, const int64_t* nnz_host,
+                                                        const void* const* psw_host, int idx_bits, const float* dout, int64_t dout_ld,
+                                                        float lr, const float* lr_dev, float eps, int rounding, const uint64_t* seed_dev,
+                                                        int table0, void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
+    if (!seed_dev) return DLRM_E_ARG;
+    if (((uintptr_t)seed_dev) & 7u) return DLRM_E_ALIGN;
+    return bwd_bf16_impl<true>("dlrm_emb_bwd_rowwise_adagrad_bf16_devkey", T, B, D, weight_host, state_host, rows_host, indices_host,
+                               offsets_host, nnz_host, psw_host, idx_bits, dout, dout_ld, dlrm_step_pos(lr, lr_dev), eps, rounding, 0, seed_dev,
+                               table0, workspace, workspace_bytes, err, stream);
+}
+
+namespace {
+// one lane: key = mix(seed0, calls), calls += 1 (the mix of dlrm_net._mix_seed(seed0, call_no, 0): wrap-around 64-bit arithmetic)
+__global__ __launch_bounds__(64) void philox_key_next_kernel(unsigned long long seed0, unsigned long long* __restrict__ calls,
+                                                             unsigned long long* __restrict__ key) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const unsigned long long n = *calls;
+    unsigned long long z = seed0 * 0x9E3779B97F4A7C15ull + n * 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 31;
+    *key = z;
+    *calls = n + 1ull;
+}
+}  // namespace
+
+// The per-update Philox key of a model, advanced ON THE DEVICE: *key_dev = mix(seed0, *calls_dev), then *calls_dev += 1.  One launch of one
+// workgroup; allocates nothing and synchronises nothing (capturable).  calls_dev, key_dev: distinct 8-byte aligned device uint64.
+extern "C" int dlrm_philox_key_next(uint64_t seed0, uint64_t* calls_dev, uint64_t* key_dev, void* stream) {
+    if (!calls_dev || !key_dev || calls_dev == key_dev) return DLRM_E_ARG;
+    if ((((uintptr_t)calls_dev) | ((uintptr_t)key_dev)) & 7u) return DLRM_E_ALIGN;
+    hipLaunchKernelGGL(philox_key_next_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)seed0,
+                       (unsigned long long*)calls_dev, (unsigned long long*)key_dev);
+    DLRM_LAUNCH_CHECK();
+    return 0;
 }

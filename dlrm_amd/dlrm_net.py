@@ -416,6 +416,9 @@ class DLRM_Net(nn.Module):
     _md_supported = True        # (the same for mixed-dimension tables)
     _bf16_supported = True      # (the same for bfloat16 tables: embedding_bfloat16 / set_embedding_dtype)
     emb_bf16 = None             # (rounding, seed) once the tables are bfloat16
+    # set by GraphedTrainStep(device_step_state=True): called in front of an EAGER bf16 key draw, so that _bf16_update_calls first takes in the
+    # update calls the graph's replays made on the device (graph.py, "host mirrors")
+    _step_state_settle = None
     # opt-in (launcher: --bf16-fuse-interact): a bfloat16 model enters the fused lookup + interaction branch of sequential_forward under the
     # fp32 branch's conditions and runs csrc/interact_bf16.hip (forward and backward) instead of dlrm_emb_fwd_bf16 + the interaction kernels
     # through the pooled [B, T*D] buffer — the same bits.  Off: a bfloat16 model runs exactly the two-kernel form.
@@ -885,10 +888,20 @@ class DLRM_Net(nn.Module):
         (UPDATE_REFUSALS)."""
         kind = plan[0]
         if self.emb_bf16 is not None:
-            if kind == "sgd":
-                ops.emb_bwd_sgd_bf16(weights, bags, dout, plan[1], self.emb_bf16[0], self._bf16_next_seed())
+            dev_state = ops.device_step_state(self)
+            if dev_state is not None:
+                # a whole-step graph is capturing (graph.py, device_step_state): the key is drawn ON THE DEVICE, from the counter the replays advance
+                ops.philox_key_next(self.emb_bf16[1], dev_state.calls, dev_state.key)
+                dev_state.draws += 1
+                seed = dev_state.key
             else:
-                ops.emb_bwd_rowwise_adagrad_bf16(weights, plan[3], bags, dout, plan[1], plan[2], self.emb_bf16[0], self._bf16_next_seed())
+                if self._step_state_settle is not None:
+                    self._step_state_settle()                 # (replays of such a graph advanced the device counter: the host one follows first)
+                seed = self._bf16_next_seed()
+            if kind == "sgd":
+                ops.emb_bwd_sgd_bf16(weights, bags, dout, plan[1], self.emb_bf16[0], seed)
+            else:
+                ops.emb_bwd_rowwise_adagrad_bf16(weights, plan[3], bags, dout, plan[1], plan[2], self.emb_bf16[0], seed)
         elif kind == "sgd":
             ops.emb_bwd_sgd(weights, bags, dout, plan[1], self.emb_update_mode)
         elif kind == "rwsadagrad":
@@ -1060,6 +1073,9 @@ class DLRM_Net(nn.Module):
 
     def _apply_pending(self, pending, optimizer, lr):
         pending = [ParkedGrad(*entry) for entry in pending]
+        dev_state = ops.device_step_state(self)
+        if dev_state is not None:
+            dev_state.passes += len(pending)                      # (what a capturing whole-step graph checks its key draws against)
         for weights, bags, dout, pre in pending:
             if pre is not None:
                 # (the backward pass already took the single-lookup rows with pre.lr — the optimizer's lr then; the rest takes the same step size)

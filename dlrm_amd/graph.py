@@ -28,7 +28,20 @@ Constraints (checked, never silently worked around):
     carry new lr values writes them in front of the launch (dlrm_graph_replay / dlrm_set_f32: values in the kernarg, no host buffer, no
     synchronisation) — the reference's LRPolicyScheduler, which moves lr EVERY iteration during warm-up and decay
     (dlrm_s_pytorch.py:169-203, :1621), is followed with ONE capture.  Any other optimizer (torch.optim.SGD: its foreach step takes lr as a
-    host number) keeps the old rule: lr is baked in at capture time and a change re-captures the step.
+    host number) keeps the old rule: lr is baked in at capture time and a change re-captures the step;
+  * step state (opt-in: GraphedTrainStep(..., device_step_state=True)): what else changes from step to step moves to the device the way
+    the learning rates did.  bfloat16 tables (torch SGD, FusedSGD, FusedRWSAdagrad): the Philox key of every update is drawn by a captured
+    dlrm_philox_key_next launch from a device counter of update calls, and the captured *_devkey update kernels read it when they run
+    (include/dlrm_hip.h "STEP STATE ON THE DEVICE") — the key sequence of the eager step, bit for bit.  The counter starts, at every capture,
+    from model._bf16_update_calls.  The bf16 update is sort-based always: the Adagrad rule of _settle_sort_mode applies (a table segment
+    that needs the general sorter raises; nothing is captured), and a captured step that drew other than one key per parked backward pass
+    raises.  FusedAdagrad (lr_decay == 0): its kernels read lr from the group's device scalar as the other two optimizers' do.  HOST MIRRORS:
+    model._bf16_update_calls and every optimizer.state[p]["step"] the captured step advances are pure functions of the number of replays;
+    replays are counted and the counters are brought up to date where someone can observe them — optimizer.state_dict() /
+    load_state_dict(), an eager optimizer step or eager bf16 update, _drop_graph, a re-capture (_settle) — never per replay, never with a
+    host wait.  Eager bf16 updates between replays move the host counter; the device counter is rewritten in front of the next replay.
+    Without the keyword bf16 tables and FusedAdagrad exit as before; QR, mixed-dimension and quantised models, a stock torch.optim.Adagrad
+    with model.fused_adagrad (its dense step is torch's) and lr_decay != 0 are refused either way.  The capture stays single-stream.
 """
 from __future__ import annotations
 
@@ -36,6 +49,7 @@ from typing import List, Optional, Sequence, Union
 
 import os as _os
 import sys
+import weakref
 
 import torch
 
@@ -97,7 +111,7 @@ class GraphedTrainStep:
     next call captures the step and every call from then on copies its inputs into the static buffers and replays.
     `self.out` holds the predictions of the last step (static buffer)."""
 
-    def __init__(self, model, optimizer, warmup: int = 2):
+    def __init__(self, model, optimizer, warmup: int = 2, device_step_state: bool = False):
         if ext_dist.is_distributed():       # (a forced one-rank group routes through distributed_forward as well: its RCCL calls must not be captured)
             raise RuntimeError("dlrm_amd.graph: the whole-step HIP graph is single-process only "
                                "(RCCL all-to-all / DDP all-reduce are not captured)")
@@ -109,9 +123,14 @@ class GraphedTrainStep:
             sys.exit("ERROR: GraphedTrainStep is not built for QR embedding tables (their backward allocates the split index arrays per step)")
         if getattr(model, "_has_md", None) is not None and model._has_md(getattr(model, "emb_l", None)):
             sys.exit("ERROR: GraphedTrainStep is not built for mixed-dimension embedding tables (their backward builds the per-width bag lists per step)")
-        if getattr(model, "emb_bf16", None) is not None:
+        # device_step_state (module docstring, "step state"): the per-step state of bf16 tables and of FusedAdagrad lives on the device / is
+        # mirrored on the host, which lifts the next two refusals — but not for a stock torch.optim.Adagrad, whose dense step is torch's
+        self.device_step_state = bool(device_step_state)
+        self._bf16 = getattr(model, "emb_bf16", None) is not None
+        if self._bf16 and not self.device_step_state:
             sys.exit("ERROR: GraphedTrainStep is not built for bfloat16 embedding tables (the per-step rounding seed would be baked into the capture)")
-        if type(optimizer).__name__ == "FusedAdagrad" or (getattr(model, "fused_adagrad", False) and type(optimizer) is torch.optim.Adagrad):
+        if (type(optimizer).__name__ == "FusedAdagrad" and not self.device_step_state) or \
+                (getattr(model, "fused_adagrad", False) and type(optimizer) is torch.optim.Adagrad):
             sys.exit("ERROR: GraphedTrainStep is not built for the fused exact Adagrad update (FusedAdagrad, or torch.optim.Adagrad with "
                      "model.fused_adagrad); use the eager step")
         self.model, self.optimizer = model, optimizer
@@ -142,7 +161,9 @@ class GraphedTrainStep:
         self.out: Optional[torch.Tensor] = None
         self._lrs: List[float] = []
         # step sizes on the device: one fp32 scalar per param group, read by the captured update kernels (module docstring)
-        self._lr_on_device = type(optimizer).__name__ in ("FusedSGD", "FusedRWSAdagrad") and _os.environ.get("DLRM_GTS_DEVICE_LR", "1") == "1"
+        # (FusedAdagrad gets here only with device_step_state)
+        self._lr_on_device = (type(optimizer).__name__ in ("FusedSGD", "FusedRWSAdagrad", "FusedAdagrad")
+                              and _os.environ.get("DLRM_GTS_DEVICE_LR", "1") == "1")
         self._lr_dev: Optional[torch.Tensor] = None
         self.lr_writes = 0          # replays that carried new step sizes (observability: tests, bench)
         self.captures = 0
@@ -154,6 +175,63 @@ class GraphedTrainStep:
         self.raw = _os.environ.get("DLRM_GTS_RAW", "1") == "1"
         self._exec = None          # hipGraphExec_t of the captured step (None: not available -> torch's replay)
         self._raw_arrays = None    # cached ctypes arrays of the raw call
+        # step state (device_step_state): what ONE replay advances — bf16 key draws and (parameter, state["step"] increment) pairs, found at
+        # capture time — and the replays the host mirrors have not taken in yet (_settle)
+        self._step_dev = None      # ops.DeviceStepState the captured kernels read and advance
+        self._draws = 0
+        self._step_deltas = []
+        self._unsettled = 0
+        self._calls_seen = 0       # model._bf16_update_calls when the device counter last agreed with it (_resync_step_state)
+        if self.device_step_state:
+            settle = weakref.WeakMethod(self._settle)       # (the optimizer and the model must not keep this object alive)
+
+            def _observed(*_args, _m=settle):
+                f = _m()
+                if f is not None:
+                    f()
+            # the observation points of the host mirrors: state_dict(), load_state_dict(), an eager optimizer step; the model calls the
+            # same function in front of an eager bf16 key draw, which comes before the optimizer's own pre-hooks (a global hook)
+            self._hooks = [optimizer.register_state_dict_pre_hook(_observed), optimizer.register_load_state_dict_pre_hook(_observed),
+                           optimizer.register_step_pre_hook(_observed)]
+            model._step_state_settle = _observed
+
+    def __del__(self):
+        try:
+            self._settle()
+            for h in getattr(self, "_hooks", ()):
+                h.remove()
+        except Exception:                                   # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def _settle(self) -> None:
+        """Host mirrors <- the replays since the last call: model._bf16_update_calls and every optimizer.state[p]["step"] the captured step
+        advances read as if those replays had been eager steps.  Pure host arithmetic (a replay advances them by known amounts): no wait,
+        no per-replay work — called where someone can observe the counters (the hooks of __init__, _drop_graph, a re-capture)."""
+        n, self._unsettled = self._unsettled, 0
+        if not n:
+            return
+        if self._draws:
+            self.model._bf16_update_calls += self._draws * n
+            self._calls_seen = self.model._bf16_update_calls
+        state = self.optimizer.state
+        for p, d in self._step_deltas:
+            st = state.get(p)
+            if st is not None and "step" in st:
+                st["step"] = st["step"] + d * n
+
+    def _resync_step_state(self) -> None:
+        """In front of a replay: EAGER bf16 update calls since the device counter was last written (a step taken outside this object) moved
+        the host counter on; the device counter follows, written in stream order.  One comparison per replay otherwise."""
+        sd = self._step_dev
+        if sd is not None and self.model._bf16_update_calls != self._calls_seen:
+            self._settle()          # (the eager draw settled already: nothing is pending; kept for a counter someone set by hand)
+            self._calls_seen = self.model._bf16_update_calls
+            sd.calls.fill_(self._calls_seen)
+
+    def _step_counts(self):
+        """id(parameter) -> its state["step"] now (python numbers, or a copy of a tensor)"""
+        return {id(p): (st["step"].clone() if isinstance(st["step"], torch.Tensor) else st["step"])
+                for p, st in self.optimizer.state.items() if "step" in st}
 
     def _settle_sort_mode(self, lS_o, lS_i) -> None:
         """First batch: keep the sort-based embedding update only if every table segment goes through the library's own segmented
@@ -162,7 +240,11 @@ class GraphedTrainStep:
             return
         self._sort_checked = True
         model, optimizer = self.model, self.optimizer
-        adagrad = any(type(optimizer).__name__ == n for n in ("RWSAdagrad", "FusedRWSAdagrad"))
+        adagrad = any(type(optimizer).__name__ == n for n in ("RWSAdagrad", "FusedRWSAdagrad", "FusedAdagrad"))
+        what = "the fused %s Adagrad update" % ("exact" if type(optimizer).__name__ == "FusedAdagrad" else "row-wise")
+        if self._bf16:
+            # the bf16 update is sort-based whatever the optimizer and has no atomic form to fall back to: the Adagrad rule
+            adagrad, what = True, "the bfloat16 table update"
         if not adagrad and getattr(model, "emb_update_mode", None) != ops.UPD_SORTED:
             return
         safe, lookups, why = False, 0, None
@@ -182,7 +264,7 @@ class GraphedTrainStep:
         if safe:
             return
         if adagrad:
-            raise RuntimeError("dlrm_amd.graph: the fused row-wise Adagrad update of this batch cannot be replayed from a HIP graph: " +
+            raise RuntimeError("dlrm_amd.graph: " + what + " of this batch cannot be replayed from a HIP graph: " +
                                ("the sorter check itself failed (%s)" % why if why else
                                 "a table segment needs the general (rocPRIM) sorter, which cannot be replayed on this ROCm "
                                 "(tools/probes/graph_sorted_probe.py)") + "; use the eager step")
@@ -220,6 +302,7 @@ class GraphedTrainStep:
         cached argument arrays go with the graph — a dangling hipGraphExec_t must never reach dlrm_graph_replay"""
         if self.graph is None:
             return
+        self._settle()
         dev = like.device if isinstance(like, torch.Tensor) else like[0].device
         torch.cuda.current_stream(dev).synchronize()
         self._replayed = False
@@ -259,6 +342,17 @@ class GraphedTrainStep:
             self.graph.reset()
         self.graph = torch.cuda.CUDAGraph()
         groups = self.optimizer.param_groups
+        model = self.model
+        self._settle()              # a re-capture starts from settled host counters
+        self._step_dev, self._draws, self._step_deltas, before = None, 0, [], None
+        if self.device_step_state:
+            before = self._step_counts()
+            if self._bf16:
+                # (calls, key) on the device, calls = the host counter; registered, like the step sizes below, for the duration of the capture only
+                self._step_dev = ops.DeviceStepState(model._bf16_update_calls, dev)
+                self._calls_seen = model._bf16_update_calls
+                self.stream.wait_stream(torch.cuda.current_stream(dev))
+                ops._graph_step_state[id(model)] = self._step_dev
         if self._lr_on_device:
             # one device scalar per param group, holding the CURRENT lr; registered for the duration of the capture only, so that an eager
             # step of the same optimizer outside the graph keeps passing its host value
@@ -273,6 +367,9 @@ class GraphedTrainStep:
         finally:
             for g in groups:
                 ops._graph_lr.pop(id(g), None)
+            ops._graph_step_state.pop(id(model), None)
+        if before is not None:
+            self._adopt_step_state(before)
         self.out, self.loss = Z.detach(), E.detach()
         self._lrs = self._current_lrs()
         # the graph holds raw pointers into the cached scratch workspaces: pin those tensors so that a later, larger
@@ -286,6 +383,26 @@ class GraphedTrainStep:
             except Exception:                               # noqa: BLE001 - a torch without the raw handle: keep its own replay
                 self._exec = None
         torch.cuda.current_stream(dev).wait_stream(self.stream)
+
+    def _adopt_step_state(self, before) -> None:
+        """After a capture: what one replay advances.  The capture RECORDED a step and ran none, yet its Python side advanced the optimizer's
+        step counts: they are put back, so that every replay — the one that executes this step included — counts the same way (_settle)."""
+        for p, st in self.optimizer.state.items():
+            if "step" not in st:
+                continue
+            was = before.get(id(p), 0)
+            d = st["step"] - was
+            if float(d) != 0.0:
+                st["step"] = was
+                self._step_deltas.append((p, d))
+        sd = self._step_dev
+        if sd is not None:
+            if sd.draws < 1 or sd.draws != sd.passes:
+                self.graph.reset()
+                self.graph, self._exec, self._raw_arrays, self._step_dev, self._step_deltas = None, None, None, None, []
+                raise RuntimeError("dlrm_amd.graph: the captured step drew %d bf16 rounding keys for %d parked backward passes (one per pass "
+                                   "is what a replay can follow); use the eager step" % (sd.draws, sd.passes))
+            self._draws = sd.draws
 
     def _changed_lrs(self):
         """(count, device pointers, values) of the step sizes this replay must write first: every group's value whenever any changed (a
@@ -328,9 +445,11 @@ class GraphedTrainStep:
         for i, (d, s_) in enumerate(pairs):
             dst[i], src[i], nbytes[i] = d.data_ptr(), s_.data_ptr(), d.numel() * d.element_size()
         ns, sdst, sval = self._changed_lrs()
+        self._resync_step_state()
         rc = _lib.load().dlrm_graph_replay(n, dst, src, nbytes, ns, sdst, sval, C.c_void_p(self._exec), int(self._replayed),
                                            C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream))
         _lib.check(rc, "dlrm_graph_replay")
+        self._unsettled += 1                                # (host mirrors of the step state: taken in lazily, _settle)
         self._keep = pairs                                  # the sources stay alive until the next call (their copies are asynchronous)
         self._replayed = self.serialize
         return True
@@ -383,6 +502,8 @@ class GraphedTrainStep:
         if ns:                       # torch's replay path: the new step sizes go in front of the launch on the same stream
             from . import _lib
             _lib.check(_lib.load().dlrm_set_f32(ns, sdst, sval, torch.cuda.current_stream(dev).cuda_stream), "dlrm_set_f32")
+        self._resync_step_state()
         self.graph.replay()
+        self._unsettled += 1
         self._replayed = self.serialize
         return self.loss

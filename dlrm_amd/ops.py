@@ -711,7 +711,8 @@ def sort_is_graph_safe(weights: Sequence[torch.Tensor], bags: BagBatch) -> bool:
     (csrc/seg_sort.h: plain kernels, replayable inside a HIP graph); False when a table segment needs the general sorter."""
     if len(weights) != bags.T:
         raise RuntimeError("dlrm_amd: sort_is_graph_safe needs one table per bag list")
-    _, _, rows = _weights_desc(weights)
+    desc = _bf16_weights_desc if weights and weights[0].dtype == torch.bfloat16 else _weights_desc      # (one sorter under every walk)
+    _, _, rows = desc(weights)
     return _lib.load().dlrm_emb_sort_kind(bags.T, bags._nnz, rows) == 1
 
 
@@ -818,7 +819,54 @@ def emb_bwd_sgd_presorted(weights: Sequence[torch.Tensor], bags: BagBatch, dout:
 # ---- bfloat16 embedding tables: csrc/emb_bf16.hip.  Tables are torch.bfloat16 [rows, D]; the feature buffer, the gradient, the Adagrad
 # accumulators and every sum stay fp32.  An update rounds each touched row ONCE: "nearest" (even) or "stochastic" (Philox4x32-10 keyed by
 # `seed`: the same seed gives the same bits; the host restatement is tests/test_bf16_emb_host.py).
+# `seed` is a Python int (the key travels by value in the launch) or a 1-element int64 GPU tensor holding the key's 64 bits, which the kernels
+# read WHEN THEY RUN (the *_devkey calls, include/dlrm_hip.h "STEP STATE ON THE DEVICE") — the form a captured whole-step graph takes, as
+# LrLike is for step sizes: GraphedTrainStep(device_step_state=True) registers a DeviceStepState per model for the duration of the capture,
+# DLRM_Net._run_update then draws its keys with philox_key_next instead of on the host.
 BF16_ROUNDINGS = {"nearest": 0, "stochastic": 1}
+SeedLike = Union[int, torch.Tensor]
+
+
+class DeviceStepState:
+    """(calls, key): the number of bf16 update calls so far and the Philox key of the current one, both on the device (one int64 [2] tensor);
+    draws / passes: keys drawn and parked backward passes applied while it was registered (what the capture is checked against)."""
+
+    __slots__ = ("buf", "calls", "key", "draws", "passes")
+
+    def __init__(self, calls: int, device):
+        self.buf = torch.tensor([int(calls), 0], dtype=torch.int64, device=device)
+        self.calls, self.key = self.buf[0:1], self.buf[1:2]
+        self.draws = self.passes = 0
+
+
+_graph_step_state = {}   # id(model) -> DeviceStepState; populated only while a GraphedTrainStep(device_step_state=True) captures
+
+
+def device_step_state(model):
+    """the device step state registered for this model (inside a graph capture), else None"""
+    return _graph_step_state.get(id(model))
+
+
+def _seed_args(seed: SeedLike):
+    """(True, pointer) for a device-side key, (False, the 64 bits) for a host one"""
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
+            raise RuntimeError("dlrm_amd: a device-side bf16 rounding seed must be a 1-element int64 GPU tensor")
+        return True, C.c_void_p(seed.data_ptr())
+    return False, int(seed) & (2 ** 64 - 1)
+
+
+def philox_key_next(seed0: int, calls: torch.Tensor, key: torch.Tensor) -> None:
+    """key[0] = _mix_seed(seed0, calls[0]) (dlrm_net), then calls[0] += 1, on the device in stream order (dlrm_philox_key_next: one tiny
+    launch, nothing allocated, nothing synchronised).  calls, key: distinct 1-element int64 GPU tensors (the key's 64 bits as stored)."""
+    for t, name in ((calls, "calls"), (key, "key")):
+        _req(t, name, dtype=torch.int64)
+        if t.numel() != 1:
+            raise RuntimeError("dlrm_amd: philox_key_next takes 1-element int64 GPU tensors")
+    if calls.device != key.device or calls.data_ptr() == key.data_ptr():
+        raise RuntimeError("dlrm_amd: philox_key_next needs distinct tensors on one device")
+    rc = _lib.load().dlrm_philox_key_next(int(seed0) & (2 ** 64 - 1), C.c_void_p(calls.data_ptr()), C.c_void_p(key.data_ptr()), _stream(key))
+    _lib.check(rc, "dlrm_philox_key_next")
 
 
 def _bf16_rounding(rounding) -> int:
@@ -916,7 +964,7 @@ UPDATE_KINDS = {
 
 
 def _sparse_update(kind: str, weights, bags: BagBatch, dout: torch.Tensor, lr: LrLike, states=None, eps=None, mode=None, rounding=None,
-                   seed: int = 0, table0: int = 0) -> None:
+                   seed: SeedLike = 0, table0: int = 0) -> None:
     """the update of `kind` over one backward pass (the public wrappers below say what each computes); states: the accumulators, one per table"""
     k = UPDATE_KINDS[kind]
     lib = _lib.load()
@@ -938,10 +986,14 @@ def _sparse_update(kind: str, weights, bags: BagBatch, dout: torch.Tensor, lr: L
                     raise RuntimeError("dlrm_amd: adagrad sum must be a contiguous [rows, D] tensor on its table's device")
         tables = (wp, _lib.ptr_array([s_.data_ptr() for s_ in states]))
     extra = (float(eps),) if k.eps else ()
+    fn = k.fn
     if k.mode:
         extra += (int(mode),)
     if k.rounding:
-        extra += (_bf16_rounding(rounding), int(seed) & (2 ** 64 - 1), int(table0))
+        on_device, seed_arg = _seed_args(seed)
+        if on_device:
+            fn += "_devkey"
+        extra += (_bf16_rounding(rounding), seed_arg, int(table0))
     ws_ptr, ws_bytes = None, 0
     if not k.mode or mode == UPD_SORTED:
         need = getattr(lib, k.ws)(bags.T, bags._nnz, rows) if k.mode else getattr(lib, k.ws)(bags.T, D, bags._nnz, rows)
@@ -952,9 +1004,9 @@ def _sparse_update(kind: str, weights, bags: BagBatch, dout: torch.Tensor, lr: L
     lr_v, lr_p = _lr_args(lr)
     err = None if bags.ignore_oob else C.c_void_p(_err_block(dout.device).data_ptr())
     with _timed(k.timer):
-        rc = getattr(lib, k.fn)(bags.T, bags.B, D, *tables, rows, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
-                                C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, *extra, ws_ptr, ws_bytes, err, _stream(dout))
-    _lib.check(rc, k.fn)
+        rc = getattr(lib, fn)(bags.T, bags.B, D, *tables, rows, bags._idx, bags._off, bags._nnz, bags._psw, bags.idx_bits,
+                              C.c_void_p(dout.data_ptr()), _ld(dout), lr_v, lr_p, *extra, ws_ptr, ws_bytes, err, _stream(dout))
+    _lib.check(rc, fn)
 
 
 def emb_bwd_sgd(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor, lr: LrLike,
@@ -981,15 +1033,16 @@ def emb_bwd_adagrad(weights: Sequence[torch.Tensor], sums: Sequence[torch.Tensor
 
 
 def emb_bwd_sgd_bf16(weights: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor, lr: LrLike, rounding: str = "stochastic",
-                     seed: int = 0, table0: int = 0) -> None:
+                     seed: SeedLike = 0, table0: int = 0) -> None:
     """Fused EmbeddingBag backward + sparse SGD over torch.bfloat16 tables, in place: per touched row r, g_r = the fp32 sum of its lookups'
     gradients (sorted walk, deterministic), W[r] = round(fmaf(-lr, g_r, float(W[r]))) — one rounding per row per call.  table0: index of
-    weights[0] in the caller's full table list (the random stream of a table does not depend on how the list is cut into calls)."""
+    weights[0] in the caller's full table list (the random stream of a table does not depend on how the list is cut into calls).  seed: the
+    Philox key, an int or a 1-element int64 GPU tensor read when the kernels run (SeedLike above): the same key, the same bits."""
     _sparse_update("sgd_bf16", weights, bags, dout, lr, rounding=rounding, seed=seed, table0=table0)
 
 
 def emb_bwd_rowwise_adagrad_bf16(weights: Sequence[torch.Tensor], states: Sequence[torch.Tensor], bags: BagBatch, dout: torch.Tensor,
-                                 lr: LrLike, eps: float, rounding: str = "stochastic", seed: int = 0, table0: int = 0) -> None:
+                                 lr: LrLike, eps: float, rounding: str = "stochastic", seed: SeedLike = 0, table0: int = 0) -> None:
     """emb_bwd_rowwise_adagrad over torch.bfloat16 tables, in place.  `states` stay fp32 and receive the bits emb_bwd_rowwise_adagrad gives
     them on the upcast tables; W[r] = round(fmaf(-lr, g_r / (sqrt(states[t][r]) + eps), float(W[r]))), one rounding per row per call."""
     _sparse_update("rwsadagrad_bf16", weights, bags, dout, lr, states, eps, None, rounding, seed, table0)

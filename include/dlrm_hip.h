@@ -353,6 +353,34 @@ int dlrm_emb_bwd_rowwise_adagrad_bf16(int T, int64_t B, int D,
                           int rounding, uint64_t seed, int table0,
                           void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
 
+/* STEP STATE ON THE DEVICE for bfloat16 tables (csrc/emb_bf16.hip; symbols added, the ABI version stays 17).  What LEARNING RATES (below)
+ * did for the step size, for the per-call Philox key: a captured whole-step HIP graph replays its kernels with the arguments of the capture, so
+ * a key passed by value would repeat in every replay.
+ * dlrm_emb_bwd_sgd_bf16_devkey / dlrm_emb_bwd_rowwise_adagrad_bf16_devkey: the operands of the two calls above with `uint64_t seed` replaced
+ *   by `const uint64_t* seed_dev` (device memory, 8-byte aligned, not NULL: DLRM_E_ARG / DLRM_E_ALIGN).  The kernels read the key from
+ *   *seed_dev WHEN THEY RUN, once per workgroup; counter layout, table0, rounding rule, sorted walk and the one rounding per touched row are
+ *   those of the by-value calls — the same kernels.  Given the same key the tables (and Adagrad states) get the SAME BITS.
+ * dlrm_philox_key_next: *key_dev = mix(seed0, *calls_dev), then *calls_dev += 1, by ONE lane of one tiny launch (plain vector stores):
+ *     z = seed0 * 0x9E3779B97F4A7C15 + *calls_dev * 0xBF58476D1CE4E5B9   (mod 2^64);   mix = z ^ (z >> 31)
+ *   — the key sequence dlrm_amd/dlrm_net.py draws on the host (_mix_seed(seed0, call_no, 0)).  calls_dev and key_dev are distinct 8-byte
+ *   aligned device uint64.  Allocates nothing, synchronises nothing: capturable, and stream order makes the key visible to the update
+ *   enqueued behind it. */
+int dlrm_emb_bwd_sgd_bf16_devkey(int T, int64_t B, int D,
+                          void* const* weight_host, const int64_t* rows_host,
+                          const void* const* indices_host, const void* const* offsets_host,
+                          const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                          const float* dout, int64_t dout_ld, float lr, const float* lr_dev,
+                          int rounding, const uint64_t* seed_dev, int table0,
+                          void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
+int dlrm_emb_bwd_rowwise_adagrad_bf16_devkey(int T, int64_t B, int D,
+                          void* const* weight_host, void* const* state_host, const int64_t* rows_host,
+                          const void* const* indices_host, const void* const* offsets_host,
+                          const int64_t* nnz_host, const void* const* psw_host, int idx_bits,
+                          const float* dout, int64_t dout_ld, float lr, const float* lr_dev, float eps,
+                          int rounding, const uint64_t* seed_dev, int table0,
+                          void* workspace, int64_t workspace_bytes, int64_t* err, void* stream);
+int dlrm_philox_key_next(uint64_t seed0, uint64_t* calls_dev, uint64_t* key_dev, void* stream);
+
 /* Fused lookup + interaction over bfloat16 tables, FORWARD and BACKWARD (csrc/interact_bf16.hip; symbols added, the ABI version stays 17).
  * Replaces, for one-lookup-per-bag batches without per-sample weights: dlrm_emb_fwd_bf16 + dlrm_interact_fwd, and dlrm_interact_bwd over the
  * pooled buffer.  Feature 0 is the fp32 block x ([B, D], row stride x_ld); feature f = 1 .. F-1 is row index_host[f-1][b] of the bf16 table
