@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include "../../include/dlrm_hip.h"
 
@@ -29,6 +30,20 @@
 static inline int dlrm_current_device() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < DLRM_MAX_DEVICES) ? d : 0; }
 
 static inline bool dlrm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// Wait for everything enqueued on `st` — the previous replay of a captured graph (dlrm_graph_replay, dlrm_forward_replay).  POLLED
+// (hipStreamQuery), not slept on: how long a thread blocked in hipStreamSynchronize takes to wake up after the GPU signalled is the box's
+// business (30 us ... 1.2 ms measured on this pool, profiles/round6/proof_wait.md) and a launch-bound replay (Criteo-Kaggle: 0.32 ms) pays
+// it every time.  The wait is one replay long; after 50 ms the thread sleeps.
+static inline hipError_t dlrm_stream_wait_polling(hipStream_t st) {
+    hipError_t e = hipStreamQuery(st);
+    if (e == hipErrorNotReady) {
+        const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(50);
+        while ((e = hipStreamQuery(st)) == hipErrorNotReady)
+            if (std::chrono::steady_clock::now() > t_end) { e = hipStreamSynchronize(st); break; }
+    }
+    return e;
+}
 
 // The dynamic-LDS limit of a kernel, THE one way to raise it: dlrm_lds_limit<kernel>(bytes) in front of the launch.  The attribute is per
 // (function, device); the helper remembers the largest size it has set for each and makes the driver call only on the first use or when

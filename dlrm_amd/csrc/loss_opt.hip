@@ -367,15 +367,7 @@ extern "C" int dlrm_graph_replay(int n, void* const* dst_host, const void* const
     if (n < 0 || !graph_exec || (n > 0 && (!dst_host || !src_host || !bytes_host))) return DLRM_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (sync_first) {
-        // the previous replay is POLLED for (hipStreamQuery), not slept on: how long a thread blocked in hipStreamSynchronize takes to wake up
-        // after the GPU signalled is the box's business (30 us ... 1.2 ms measured on this pool, profiles/round6/proof_wait.md) and a
-        // launch-bound step (Criteo-Kaggle: 0.32 ms per replay) pays it every step.  The wait is one step long; after 50 ms the thread sleeps.
-        hipError_t e = hipStreamQuery(st);
-        if (e == hipErrorNotReady) {
-            const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(50);
-            while ((e = hipStreamQuery(st)) == hipErrorNotReady)
-                if (std::chrono::steady_clock::now() > t_end) { e = hipStreamSynchronize(st); break; }
-        }
+        const hipError_t e = dlrm_stream_wait_polling(st);      // the previous replay: polled for, not slept on (common.h)
         if (e != hipSuccess) return (int)e;
     }
     for (int i = 0; i < n; ++i) {

@@ -18,10 +18,20 @@ from . import ext_dist, ops
 
 
 @torch.no_grad()
-def inference(model, test_batches: Iterable, device: Optional[torch.device] = None, nbatches: int = -1) -> Dict[str, float]:
+def inference(model, test_batches: Iterable, device: Optional[torch.device] = None, nbatches: int = -1,
+              graphed: bool = False) -> Dict[str, float]:
     """`test_batches` yields (X, lS_o, lS_i, T) like the reference's unpack_batch (:733-757).  Returns the
-    validation_results dictionary of the reference plus `round_accuracy` (its non-mlperf accuracy) and raw counts."""
+    validation_results dictionary of the reference plus `round_accuracy` (its non-mlperf accuracy) and raw counts.
+    graphed=True: the batches run through one dlrm_amd.graph.GraphedForward (an exact-shape graph per batch shape: the short last batch
+    captures a second one; single process only) — its predictions are a static buffer, so each batch's are cloned before the next call."""
     scores, targets = [], []
+    forward = model
+    if graphed:
+        from .graph import GraphedForward
+        fwd = GraphedForward(model)
+
+        def forward(X_, lS_o_, lS_i_):
+            return fwd(X_, lS_o_, lS_i_).clone()
     for i, (X, lS_o, lS_i, T) in enumerate(test_batches):
         if 0 < nbatches <= i:
             break
@@ -33,7 +43,7 @@ def inference(model, test_batches: Iterable, device: Optional[torch.device] = No
             lS_o = [o.to(device) for o in lS_o] if isinstance(lS_o, (list, tuple)) else lS_o.to(device)
             lS_i = [x.to(device) for x in lS_i] if isinstance(lS_i, (list, tuple)) else lS_i.to(device)
             T = T.to(device)
-        Z = model(X, lS_o, lS_i)
+        Z = forward(X, lS_o, lS_i)
         if ext_dist.is_distributed():
             _, batch_split_lengths = ext_dist.get_split_lengths(X.size(0))
             Z = ext_dist.all_gather(Z, batch_split_lengths)

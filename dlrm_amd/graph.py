@@ -507,3 +507,6 @@ class GraphedTrainStep:
         self._unsettled += 1
         self._replayed = self.serialize
         return self.loss
+
+
+from .graph_forward import GraphedForward  # noqa: E402,F401  (the forward pass's twin of GraphedTrainStep: dlrm_amd/graph_forward.py)

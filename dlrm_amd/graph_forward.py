@@ -1,0 +1,574 @@
+"""Whole-forward HIP graph for small-batch serving: `model(X, lS_o, lS_i)` under no_grad captured once per shape and replayed with one
+host call per request (dlrm_forward_replay: wait for the previous replay, stage the request into the static buffers, hipGraphLaunch).
+The twin of graph.GraphedTrainStep, which captures a training step and therefore refuses the inference models (packed tables, int8 /
+fp16 towers); re-exported as dlrm_amd.graph.GraphedForward.
+
+    fwd = GraphedForward(model, batch_sizes=(64, 256, 2048))
+    Z = fwd(X, lS_o, lS_i)          # [n, 1] view of a static buffer, valid until the next call
+
+What is captured is the model's own forward, unchanged: every table kind and tower kind whose forward is built.  The rules of
+GraphedTrainStep._capture hold (own stream, no event timers, the scratch workspaces of the capture pinned, single stream, single process).
+
+Shapes.  Without `batch_sizes` every distinct request shape gets its own graph (at most `max_exact_shapes`, least recently used dropped).
+With `batch_sizes` a request of n rows whose lookup structure is FIXED — table k has exactly P_k lookups in every bag, offsets ==
+P_k * arange(n), proven on the caller's tensors — runs in the smallest bucket >= n: its rows go to the head of the bucket's static
+buffers (the static offsets are P_k * arange(bucket) and never change), Z[:n] comes back.  Rows n.. keep what earlier requests left there or
+the zeros of the capture: every sample's forward is independent, so rows < n do not depend on them — with one exception, the int8 towers,
+whose activation range is taken over the whole batch tensor; such a model is refused with buckets.  The answer of a bucket is the eager
+forward on the padded batch, bit for bit (the library picks GEMM variants by M: the eager forward at n may sum in another order).  A ragged
+request, or n above the largest bucket, takes an exact-shape graph.
+
+Fused lookup + interaction.  Inside a capture nothing can ask the device whether offsets == arange(B); the proof is made per request on
+the caller's tensors (ops.offsets_are_iota: cached per tensor object, free for producer-tagged tensors), only for models that have a fused
+route at all, and its verdict is part of the graph's key: a request that fails it runs the graph captured with the two-kernel form.  The
+verdict reaches the captured forward through the proof's own cache, set on the STATIC offsets tensors this object owns — the model's
+fuse_emb_interact is never touched.
+
+Staleness.  A graph holds raw pointers.  Every call compares the model's table kind, quantize_bits, quantize_mlp_bits, bf16 flag and the
+first and last data_ptr of the tensors the forward reads with what the captures saw; a difference drops every graph (`invalidate()`
+does the same on request).  In-place weight updates need nothing.
+
+Index errors surface exactly as eager: at the next call's ops.check_index_errors().  When one does, the index buffers of every bucket are
+zeroed before the error is raised, so a bad id never stays behind in tail rows.
+"""
+from __future__ import annotations
+
+import collections
+import contextlib
+import ctypes as C
+import os as _os
+import sys
+import weakref
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import ext_dist, ops
+
+STAGE_MEMCPY_MAX = 4        # requests of at most this many segments are staged with one hipMemcpyAsync each (stacked inputs), more with one
+                            # dlrm_stage_inputs launch (profiles/graph_forward/rates.md)
+STAGE_SEGS_PER_LAUNCH = 64  # DLRM_MAX_STAGE_SEGS of csrc/stage.hip
+
+
+# ------------------------------------------------------------------------------------------------ host logic (no device needed)
+def pick_bucket(n: int, batch_sizes: Optional[Sequence[int]]) -> Optional[int]:
+    """the smallest bucket >= n; None: no buckets, or n above the largest (an exact-shape graph)"""
+    best = None
+    for b in batch_sizes or ():
+        if b >= n and (best is None or b < best):
+            best = b
+    return best
+
+
+def _is_stacked(lS_o, lS_i) -> bool:
+    so, si = isinstance(lS_o, torch.Tensor), isinstance(lS_i, torch.Tensor)
+    if so != si or (so and (lS_o.dim() != 2 or lS_i.dim() != 2 or lS_o.size(0) != lS_i.size(0))):
+        raise RuntimeError("dlrm_amd.graph: offsets and indices must both be lists of 1-D tensors or both stacked [T, n] tensors")
+    if not so and len(lS_o) != len(lS_i):
+        raise RuntimeError("dlrm_amd.graph: offsets / indices table counts differ")
+    return so
+
+
+_steps_cache: dict = {}      # id(offsets tensor) -> (weakref, _version, P, verdict): offsets == P * arange, as iota.py caches P == 1
+
+
+def _offsets_are_steps(o: torch.Tensor, P) -> bool:
+    """o (1-D, or stacked [T, n] with P a tuple) == P * arange(n): one comparison on the tensor's device + a host wait, once per tensor object"""
+    e = _steps_cache.get(id(o))
+    if e is not None and e[0]() is o and e[1] == o._version and e[2] == P:
+        return e[3]
+    n = o.size(-1)
+    step = torch.arange(n, dtype=o.dtype, device=o.device)
+    if o.dim() == 2:
+        want = step.unsqueeze(0) * torch.tensor(P, dtype=o.dtype, device=o.device).unsqueeze(1)
+    else:
+        want = step * P
+    ok = bool(torch.equal(o, want))
+    if len(_steps_cache) > 256:
+        for k in [k for k, v in _steps_cache.items() if v[0]() is None]:
+            del _steps_cache[k]
+        if len(_steps_cache) > 256:
+            _steps_cache.clear()
+    _steps_cache[id(o)] = (weakref.ref(o), o._version, P, ok)
+    return ok
+
+
+def fixed_bag_lengths(lS_o, lS_i, n: int) -> Optional[Tuple[int, ...]]:
+    """(P_0, ..., P_{T-1}) when table k has exactly P_k >= 1 lookups in every one of its n bags (numel(indices_k) == P_k * n and
+    offsets_k == P_k * arange(n)), else None.  What a bucket needs: the static offsets of the padded batch are then P_k * arange(bucket).
+    All P_k == 1 on the GPU is the library's one-lookup-per-bag proof (ops.offsets_are_iota: producer tags, cached verdicts)."""
+    stacked = _is_stacked(lS_o, lS_i)
+    if n <= 0:
+        return None
+    T = lS_o.size(0) if stacked else len(lS_o)
+    Ps = []
+    for k in range(T):
+        no, ni = (lS_o.size(1), lS_i.size(1)) if stacked else (lS_o[k].numel(), lS_i[k].numel())
+        if no != n or ni < n or ni % n != 0:
+            return None
+        Ps.append(ni // n)
+    Ps = tuple(Ps)
+    on_gpu = lS_o.is_cuda if stacked else all(o.is_cuda for o in lS_o)
+    if on_gpu and all(p == 1 for p in Ps):
+        return Ps if ops.offsets_are_iota(lS_o) else None
+    if stacked:
+        return Ps if _offsets_are_steps(lS_o, Ps) else None
+    return Ps if all(_offsets_are_steps(o, p) for o, p in zip(lS_o, Ps)) else None
+
+
+def alias_pattern(ts) -> Optional[tuple]:
+    """None when every tensor of the list is its own object, else for each position the first position holding the same object (a request
+    that shares ONE offsets tensor among its tables is staged once, into one static tensor)"""
+    first, out, shared = {}, [], False
+    for k, t in enumerate(ts):
+        j = first.setdefault(id(t), k)
+        shared |= j != k
+        out.append(j)
+    return tuple(out) if shared else None
+
+
+class LRU:
+    """key -> value, at most `cap` entries; put() returns the values that fell out (least recently used first)"""
+
+    def __init__(self, cap: int):
+        self.cap = max(int(cap), 1)
+        self._d: "collections.OrderedDict" = collections.OrderedDict()
+
+    def get(self, key):
+        v = self._d.get(key)
+        if v is not None:
+            self._d.move_to_end(key)
+        return v
+
+    def put(self, key, value) -> list:
+        self._d[key] = value
+        self._d.move_to_end(key)
+        out = []
+        while len(self._d) > self.cap:
+            out.append(self._d.popitem(last=False)[1])
+        return out
+
+    def values(self):
+        return list(self._d.values())
+
+    def keys(self):
+        return list(self._d.keys())
+
+    def clear(self) -> None:
+        self._d.clear()
+
+    def __len__(self) -> int:
+        return len(self._d)
+
+
+class StagePlan:
+    """The segment list of one graph: static buffers <- a request of the same input structure, as the ctypes arrays of
+    dlrm_forward_replay.  Built ONCE per graph (destinations never change); patch() writes the source pointers and lengths of a request.
+      X          one segment: the request's n rows are the head of the static [B, m] buffer;
+      a list     one segment per DISTINCT static tensor (alias_pattern), the request's tensor at the first position that maps to it;
+      stacked    one segment, the whole [T, n'] tensor — unless its group is named in `by_rows`: then the T rows, each into the head of
+                 its row of the static buffer.  A BUCKET names its stacked indices there whatever the width of the request the plan is
+                 built from: a later request of the same key may be narrower, and T rows laid end to end are not the heads of T rows.
+    A group whose static is None is not staged (a bucket's offsets never change).  patch() refuses a segment longer than its destination."""
+
+    def __init__(self, statics: Sequence, like: Sequence, by_rows: Sequence[int] = ()):
+        self.entries = []       # (group, position in the list or None, row or None)
+        dst, cap = [], []
+        for g, (s, r) in enumerate(zip(statics, like)):
+            if s is None:
+                continue
+            if isinstance(s, torch.Tensor):
+                if not isinstance(r, torch.Tensor) or r.dtype != s.dtype or r.dim() != s.dim():
+                    raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
+                if g in by_rows:
+                    if s.dim() != 2 or r.size(0) != s.size(0) or r.size(1) > s.size(1) or (s.size(1) > 1 and s.stride(1) != 1):
+                        raise RuntimeError("dlrm_amd.graph: a stacked input does not fit its static buffer")
+                    for k in range(s.size(0)):
+                        self.entries.append((g, None, k))
+                        dst.append(s.data_ptr() + k * s.stride(0) * s.element_size())
+                        cap.append(s.size(1) * s.element_size())
+                else:
+                    if s.dim() == 2 and r.size(1) != s.size(1):
+                        raise RuntimeError("dlrm_amd.graph: a stacked input narrower than its static buffer is staged by rows (by_rows)")
+                    self.entries.append((g, None, None))
+                    dst.append(s.data_ptr())
+                    cap.append(s.numel() * s.element_size())
+                continue
+            if isinstance(r, torch.Tensor) or len(r) != len(s):
+                raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
+            seen = set()
+            for k, t in enumerate(s):
+                if id(t) in seen:
+                    continue
+                seen.add(id(t))
+                self.entries.append((g, k, None))
+                dst.append(t.data_ptr())
+                cap.append(t.numel() * t.element_size())
+        self.n = len(dst)
+        m = max(self.n, 1)
+        self.cap = cap
+        self.dst = (C.c_void_p * m)(*dst)
+        self.src = (C.c_void_p * m)()
+        self.nbytes = (C.c_int64 * m)()
+
+    def patch(self, request: Sequence) -> None:
+        src, nbytes, cap = self.src, self.nbytes, self.cap
+        for j, (g, k, row) in enumerate(self.entries):
+            t = request[g] if k is None else request[g][k]
+            if row is None:
+                p, nb = t.data_ptr(), t.numel() * t.element_size()
+            else:
+                nb = t.size(1) * t.element_size()
+                p = t.data_ptr() + row * nb
+            if nb > cap[j]:
+                raise RuntimeError("dlrm_amd.graph: an input is larger than the static buffer it is staged into")
+            src[j], nbytes[j] = p, nb
+
+    def launches(self, memcpy_max: int) -> int:
+        """kernel launches of one staging (0: the memcpy path)"""
+        return 0 if self.n <= memcpy_max else (self.n + STAGE_SEGS_PER_LAUNCH - 1) // STAGE_SEGS_PER_LAUNCH
+
+
+def model_tensors(model) -> list:
+    """the tensors a forward reads through raw pointers: the tables (packed ones first), then every parameter, then the towers' packed
+    int8 weights"""
+    out = []
+    if getattr(model, "quantize_emb", False):
+        out += [t for t in (getattr(model, "emb_l_q", None) or []) if isinstance(t, torch.Tensor)]
+    out += list(model.parameters())
+    for name in ("bot_l", "top_l"):
+        tower = getattr(model, name, None)
+        tower = getattr(tower, "module", tower)
+        for q in getattr(tower, "_q8", None) or []:
+            out += [t for t in (q if isinstance(q, (tuple, list)) else [q]) if isinstance(t, torch.Tensor)]
+    return out
+
+
+def model_scalars(model) -> tuple:
+    kind = model._table_kind() if hasattr(model, "_table_kind") else None
+    return (kind, getattr(model, "quantize_bits", None), getattr(model, "quantize_mlp_bits", 32), getattr(model, "emb_bf16", None) is not None)
+
+
+def fingerprint(model, tensors: Sequence) -> tuple:
+    """the cheap per-call form: the scalars plus the first and last pointer of `tensors` (model_tensors at the time of the captures)"""
+    if not tensors:
+        return model_scalars(model) + (0, 0)
+    return model_scalars(model) + (tensors[0].data_ptr(), tensors[-1].data_ptr())
+
+
+class _Graph:
+    __slots__ = ("key", "bucket", "n", "static", "plan", "graph", "exec", "out", "eager_calls", "pinned_ws", "views", "iota")
+
+    def __init__(self, key, bucket, n):
+        self.key, self.bucket, self.n = key, bucket, n
+        self.static = self.plan = self.graph = self.exec = self.out = None
+        self.eager_calls = 0
+        self.pinned_ws = None
+        self.views = {}
+        self.iota = None          # the offsets verdict the forward on the static buffers runs with (None: no fused route asks)
+
+
+# ------------------------------------------------------------------------------------------------ the class
+class GraphedForward:
+    """fwd = GraphedForward(model, batch_sizes=None, warmup=2);  Z = fwd(X, lS_o, lS_i)   ([n, 1] view of a static buffer)
+
+    The first `warmup` calls of a graph are eager forwards on its static buffers (kernel attributes, workspaces and allocator pools
+    settle; a bucket answers with the padded batch's bits from its first call on); the next call captures, every later one stages and
+    replays.  Counters: captures, replays, staged_launches (dlrm_stage_inputs kernel launches of the replays; the memcpy path adds
+    none), buckets_in_use."""
+
+    def __init__(self, model, batch_sizes: Optional[Sequence[int]] = None, warmup: int = 2, max_exact_shapes: int = 8):
+        if ext_dist.is_distributed():
+            raise RuntimeError("dlrm_amd.graph: the whole-forward HIP graph is single-process only "
+                               "(the RCCL all-to-all of the distributed forward is not captured)")
+        self.batch_sizes = tuple(sorted({int(b) for b in batch_sizes})) if batch_sizes else None
+        if self.batch_sizes and self.batch_sizes[0] < 1:
+            raise ValueError("dlrm_amd.graph: batch_sizes must be positive")
+        self.model = model
+        self._refuse_int8_buckets()
+        self.warmup = max(int(warmup), 1)
+        self.stream: Optional[torch.cuda.Stream] = None
+        self.stage_memcpy_max = STAGE_MEMCPY_MAX
+        self.serialize = _os.environ.get("DLRM_GTS_SERIALIZE", "1") == "1"      # one replay in flight (graph.py: the ROCm 7.2 rule)
+        self._exact = LRU(max_exact_shapes)
+        self._buckets: dict = {}
+        self._in_flight = False
+        self._keep = None
+        self._tensors: list = []
+        self._fp = None
+        self._route = False
+        self.captures = 0
+        self.replays = 0
+        self.staged_launches = 0
+
+    # ---- refusals, staleness ------------------------------------------------------------------------------------------------------
+    def _refuse_int8_buckets(self) -> None:
+        if self.batch_sizes and getattr(self.model, "quantize_mlp_bits", 32) == 8:
+            sys.exit("ERROR: GraphedForward with batch_sizes: int8 towers quantise per batch; padded buckets would change the result "
+                     "(exact-shape graphs work: batch_sizes=None)")
+
+    @property
+    def buckets_in_use(self) -> int:
+        return len({g.bucket for g in self._buckets.values() if g.graph is not None})
+
+    @property
+    def exact_shapes(self) -> int:
+        return len(self._exact)
+
+    def invalidate(self) -> None:
+        """forget every captured graph (the next calls capture again) — after anything that moved a tensor the forward reads"""
+        self._wait()
+        for g in self._exact.values() + list(self._buckets.values()):
+            if g.graph is not None:
+                g.graph.reset()
+        self._exact.clear()
+        self._buckets.clear()
+        self._keep = None
+        self._fp = None
+
+    def _refresh(self) -> None:
+        """what the captures depend on, taken from the model as it is now"""
+        model = self.model
+        self._refuse_int8_buckets()
+        self._tensors = model_tensors(model)
+        self._fp = fingerprint(model, self._tensors)
+        self._route = self._has_fused_route()
+
+    def _has_fused_route(self) -> bool:
+        """does this model have fused lookup + interaction kernels at all (dlrm_net.fused_route, asked as DLRM_Net._fused_forward asks under
+        no_grad)?  Only then is a request's offsets proof worth its host wait."""
+        m = self.model
+        if not (getattr(m, "fuse_emb_interact", False) and hasattr(m, "_table_kind")):
+            return False
+        from .dlrm_net import DLRM_Net, fused_route
+        if type(m).sequential_forward is not DLRM_Net.sequential_forward:
+            return False                      # (the cat-interaction variants bring their own forward: no route)
+        tables = m._table_kind()
+        packed = tables == "quant"
+        try:
+            T, D = (len(m.emb_l_q), m.emb_q_dim) if packed else (len(m.emb_l), m._emb_dim(m.emb_l))
+        except (AttributeError, IndexError, TypeError):
+            return False
+        return fused_route(tables, 1 + T, D, m.quantize_bits if packed else 0, fuse_emb_interact=True,
+                           fuse_quant_interact=m.fuse_quant_interact, fuse_qr_interact=m.fuse_qr_interact,
+                           fuse_bf16_interact=m.fuse_bf16_interact, fuse_narrow_interact=m.fuse_narrow_interact,
+                           update_in_backward=m.update_in_backward, interaction_op=m.arch_interaction_op,
+                           pooling_weights=any(w is not None for w in (m.v_W_l or [])), grad_wanted=False,
+                           bf16_rows=m.emb_bf16 is not None) is not None
+
+    # ---- helpers -------------------------------------------------------------------------------------------------------------------
+    def _wait(self) -> None:
+        if self._in_flight:
+            ops.wait_spinning(torch.cuda.current_stream())
+            self._in_flight = False
+
+    def _check_errors(self) -> None:
+        """ops.check_index_errors() as the eager forward calls it.  A reported id may still sit in a bucket's rows, and a request replayed
+        since — before the report was seen — may have met it there again and reported it once more: everything enqueued is waited for, the
+        index rows of every bucket are zeroed, and what the error block received meanwhile is dropped where it is the same bad id (another
+        one is reported in the same exception), so that ONE bad request raises ONCE and no later request answers for it."""
+        try:
+            ops.check_index_errors()
+        except IndexError as first:
+            ops.wait_spinning(torch.cuda.current_stream())
+            self._in_flight = False
+            second = None
+            try:
+                ops.check_index_errors()
+            except IndexError as e:
+                if str(e) != str(first):            # (another bad id, of a request replayed since: reported with this one, not lost)
+                    second = e
+            for g in self._buckets.values():
+                seen = set()
+                for t in ([g.static[2]] if isinstance(g.static[2], torch.Tensor) else g.static[2]):
+                    if id(t) not in seen:
+                        seen.add(id(t))
+                        t.zero_()
+            if second is not None:
+                raise IndexError("%s; and, from a request replayed since: %s" % (first, second)) from first
+            raise
+
+    @contextlib.contextmanager
+    def _single_stream(self):
+        """the captured forward is single-stream (a replayed graph has no launch gaps to hide); the model's own setting comes back"""
+        model = self.model
+        was = getattr(model, "overlap_streams", False)
+        if was:
+            model.overlap_streams = False
+        try:
+            yield
+        finally:
+            if was:
+                model.overlap_streams = True
+
+    def _normalise(self, X, lS_o, lS_i, dev):
+        def fix(t):
+            if t.device != dev:
+                t = t.to(dev)
+            return t if t.is_contiguous() else t.contiguous()
+        X = fix(X)
+        if isinstance(lS_o, torch.Tensor):
+            return X, fix(lS_o), fix(lS_i)
+        fixed = {}
+        return X, [fixed.setdefault(id(t), fix(t)) for t in lS_o], [fixed.setdefault(id(t), fix(t)) for t in lS_i]
+
+    def _lookup(self, X, lS_o, lS_i):
+        """-> the graph this request runs in (made on first sight)"""
+        stacked = _is_stacked(lS_o, lS_i)
+        n = X.size(0)
+        bucket = pick_bucket(n, self.batch_sizes)
+        Ps = fixed_bag_lengths(lS_o, lS_i, n) if bucket is not None else None
+        idt = lS_i.dtype if stacked else lS_i[0].dtype
+        if Ps is not None:
+            T = len(Ps)
+            key = ("bucket", bucket, stacked, X.size(1), X.dtype, idt, Ps, None if stacked else alias_pattern(lS_i))
+            g = self._buckets.get(key)
+            if g is None:
+                g = self._buckets[key] = _Graph(key, bucket, bucket)
+                dev = X.device
+                Xs = torch.zeros((bucket, X.size(1)), dtype=X.dtype, device=dev)
+                step = torch.arange(bucket, dtype=idt, device=dev)
+                if stacked:
+                    Os = step.unsqueeze(0) * torch.tensor(Ps, dtype=idt, device=dev).unsqueeze(1)
+                    Is = torch.zeros((T, bucket * Ps[0]), dtype=idt, device=dev)
+                else:
+                    Os = [step * p for p in Ps]
+                    made = {}
+                    Is = [made.setdefault(id(t), torch.zeros(bucket * p, dtype=idt, device=dev)) for t, p in zip(lS_i, Ps)]
+                g.static = (Xs, Os, Is)
+                # (stacked ids go in by rows whatever this first request's width: the next one of the key may be narrower)
+                g.plan = StagePlan((Xs, None, Is), (X, lS_o, lS_i), by_rows=(2,) if stacked else ())
+                g.iota = all(p == 1 for p in Ps)
+            return g
+        # exact shape.  The offsets' verdict is part of the key where the model could take a fused route with these shapes
+        if stacked:
+            shape = (tuple(lS_o.shape), tuple(lS_i.shape))
+            one = lS_o.size(1) == n and lS_i.size(1) == n
+        else:
+            no, ni = [o.numel() for o in lS_o], [i.numel() for i in lS_i]
+            shape = (tuple(no), tuple(ni), alias_pattern(lS_o), alias_pattern(lS_i))
+            one = no.count(n) == len(no) and ni.count(n) == len(ni)
+        iota = bool(ops.offsets_are_iota(lS_o)) if (self._route and one and n > 0) else None
+        key = ("exact", stacked, tuple(X.shape), X.dtype, idt, shape, iota)
+        g = self._exact.get(key)
+        if g is None:
+            g = _Graph(key, None, n)
+            from .graph import _clone_struct
+            g.static = (X.clone(), _clone_struct(lS_o), _clone_struct(lS_i))
+            g.plan = StagePlan(g.static, (X, lS_o, lS_i))
+            g.iota = iota
+            dropped = self._exact.put(key, g)
+            if dropped:
+                self._wait()
+                for d in dropped:
+                    if d.graph is not None:
+                        d.graph.reset()
+        return g
+
+    @staticmethod
+    def _vouch(g: _Graph) -> None:
+        """the verdict of the offsets proof, stated for the STATIC offsets tensors (iota.vouch_offsets): the forward run or captured on them
+        takes the fused kernels alone (True) or the two-kernel form (False).  Stated in front of EVERY forward on the static buffers — the
+        record is a cache entry that other proofs can evict — and true whenever it is stated: every request is proven before it is staged."""
+        if g.iota is None:
+            return
+        from . import iota as _iota
+        static_o = g.static[1]
+        for t in ([static_o] if isinstance(static_o, torch.Tensor) else static_o):
+            _iota.vouch_offsets(t, g.iota)
+
+    def _stage_now(self, g: _Graph, request) -> None:
+        """request -> static buffers on the current stream, outside a replay (the eager calls in front of the capture)"""
+        from . import _lib
+        g.plan.patch(request)
+        if g.plan.n:
+            rc = _lib.load().dlrm_stage_inputs(g.plan.n, g.plan.dst, g.plan.src, g.plan.nbytes,
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.check(rc, "dlrm_stage_inputs")
+
+    def _eager(self, g: _Graph, dev):
+        """the model's forward on the static buffers, on the stream the capture uses (its scratch workspaces are per stream)"""
+        cur = torch.cuda.current_stream(dev)
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=dev)
+        self.stream.wait_stream(cur)
+        self._vouch(g)
+        with self._single_stream(), torch.no_grad(), torch.cuda.stream(self.stream):
+            Z = self.model(*g.static)
+        cur.wait_stream(self.stream)
+        Z.record_stream(cur)
+        return Z
+
+    def _capture(self, g: _Graph, dev) -> None:
+        if ops.timers is not None:
+            raise RuntimeError("dlrm_amd.graph: per-kernel event timers cannot be recorded inside a graph capture")
+        cur = torch.cuda.current_stream(dev)
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=dev)
+        self.stream.wait_stream(cur)
+        graph = torch.cuda.CUDAGraph()
+        self._vouch(g)
+        # ("relaxed": the forward polls events of finished offsets proofs and reads the pinned error block while the stream captures)
+        with self._single_stream(), torch.no_grad(), torch.cuda.graph(graph, stream=self.stream, capture_error_mode="relaxed"):
+            Z = self.model(*g.static)
+        if Z.dim() != 2 or Z.size(0) != g.n or not Z.is_contiguous():
+            graph.reset()
+            raise RuntimeError("dlrm_amd.graph: the captured forward returned %s, expected a contiguous [%d, k] tensor" % (tuple(Z.shape), g.n))
+        g.graph, g.out, g.views = graph, Z.detach(), {}
+        # the graph holds raw pointers into the cached scratch workspaces: pinned, as GraphedTrainStep pins them
+        g.pinned_ws = [w for (_, d_, _), w in ops._scratch_ws.items() if d_ == dev]
+        try:
+            g.exec = int(graph.raw_cuda_graph_exec())
+        except Exception:                                   # noqa: BLE001 - a torch without the raw handle: its own replay
+            g.exec = None
+        self.captures += 1
+        cur.wait_stream(self.stream)
+
+    # ---- the call ------------------------------------------------------------------------------------------------------------------
+    def __call__(self, X, lS_o, lS_i):
+        self._check_errors()
+        model = self.model
+        if self._fp is None or fingerprint(model, self._tensors) != self._fp:
+            if self._fp is not None:
+                self.invalidate()
+            self._refresh()
+        dev = self._tensors[0].device if self._tensors else X.device
+        if dev.type != "cuda":
+            raise RuntimeError("dlrm_amd.graph: GraphedForward captures a HIP graph; move the model to the GPU first (model.to('cuda'))")
+        X, lS_o, lS_i = self._normalise(X, lS_o, lS_i, dev)
+        n = X.size(0)
+        g = self._lookup(X, lS_o, lS_i)
+        request = (X, lS_o, lS_i)
+        if g.graph is None:
+            self._wait()
+            self._check_errors()            # (exact for everything this object enqueued: nothing of it is in flight any more)
+            if g.eager_calls < self.warmup:
+                self._stage_now(g, request)
+                g.out = self._eager(g, dev)
+                g.eager_calls += 1
+                self._keep = request
+                return g.out if g.bucket is None else g.out[:n]
+            self._capture(g, dev)           # capture only records; the replay below executes this request
+        plan = g.plan
+        from . import _lib
+        if g.exec is not None:
+            plan.patch(request)
+            rc = _lib.load().dlrm_forward_replay(plan.n, plan.dst, plan.src, plan.nbytes, self.stage_memcpy_max, C.c_void_p(g.exec),
+                                                 int(self._in_flight), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.check(rc, "dlrm_forward_replay")
+            self.staged_launches += plan.launches(self.stage_memcpy_max)
+        else:
+            self._wait()
+            self._stage_now(g, request)
+            g.graph.replay()
+            self.staged_launches += plan.launches(0)
+        self.replays += 1
+        self._keep = request                # the sources stay alive until the next call (their copies are asynchronous)
+        self._in_flight = self.serialize
+        if g.bucket is None:
+            return g.out
+        z = g.views.get(n)
+        if z is None:
+            z = g.views[n] = g.out[:n]
+        return z
+

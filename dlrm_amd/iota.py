@@ -59,6 +59,14 @@ def _iota_remember(t: torch.Tensor, verdict: bool) -> None:
     _iota_cache[id(t)] = (weakref.ref(t), t._version, verdict)
 
 
+def vouch_offsets(t: torch.Tensor, verdict: bool) -> None:
+    """The owner of an offsets tensor states the verdict a proof would reach — for tensors written through raw pointers only (the static
+    offsets buffers of dlrm_amd.graph.GraphedForward, whose every request is proven before it is staged): recorded like a finished proof,
+    per tensor object and in-place version.  The record is a cache entry and can be evicted (_iota_remember): state it again in front of
+    every use that depends on it."""
+    _iota_remember(t, bool(verdict))
+
+
 POOL_SLOTS = 1024
 PENDING_REMEMBERED = 64      # device proofs whose verdict is still wanted: one nobody came back for within 64 steps is not remembered
 

@@ -1041,6 +1041,21 @@ int dlrm_graph_replay(int n, void* const* dst_host, const void* const* src_host,
                       int sync_first, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One replay of a captured FORWARD (dlrm_amd.graph.GraphedForward; csrc/stage.hip; symbols added, the ABI version stays 17).
+ * dlrm_stage_inputs: n_seg device-to-device copies dst_host[i][0 .. bytes_host[i]) = src_host[i][...] in ONE kernel launch per 64 copying
+ *   segments — pointers and lengths by value in the kernarg, nothing read from host memory after the call returns.  Every pointer and
+ *   length must be a multiple of 4 (DLRM_E_ALIGN otherwise: the inputs of a forward are fp32 / int32 / int64 tensors).  Per segment the
+ *   kernel moves 16-byte elements where destination and source are congruent modulo 16 (4-byte words in front of the first and behind the
+ *   last 16-byte boundary), 8-byte elements where they are congruent modulo 8, else 4-byte words.  A segment of 0 bytes, or one whose
+ *   source is its destination, copies nothing; segments must not overlap otherwise.
+ * dlrm_forward_replay: optionally wait for the stream (the previous replay; the polling wait of dlrm_graph_replay), stage the n_seg
+ *   segments — one hipMemcpyAsync each when n_seg <= memcpy_max_segs (a stacked [T, B] request is three tensors), one
+ *   dlrm_stage_inputs otherwise — then hipGraphLaunch(graph_exec). */
+int dlrm_stage_inputs(int n_seg, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host, void* stream);
+int dlrm_forward_replay(int n_seg, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host,
+                        int memcpy_max_segs, void* graph_exec, int sync_first, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Strided block copy = torch.cat / torch.split along dim 1 without ATen:
  *   for k < nblk:  dst_host[k][m*dst_ld_host[k] + c] = src_host[k][m*src_ld_host[k] + c],  m < M, c < width_host[k]
  * Uses: the "cat" interaction R = cat([x] + ly, 1) (dlrm_s_pytorch.py:505-507) when the features do not already sit
