@@ -6,6 +6,7 @@
 //   All2All_Wait.forward's split + view of the receive buffer          extend_distributed.py:446-465
 #include <chrono>
 #include "common.h"
+#include "replay.h"
 
 namespace {
 
@@ -339,9 +340,7 @@ extern "C" int dlrm_hip_device_info(int device, int* cu_count, int* lds_bytes, i
     return 0;
 }
 
-// One replay of a captured training step (dlrm_amd.graph.GraphedTrainStep) from ONE host call: wait for the previous replay, copy the
-// step's inputs into the graph's static buffers, launch.  At Criteo-Kaggle shapes the GPU finishes a replay in ~0.3 ms and then waits for
-// the host; the same sequence issued from Python (stream.synchronize(), one copy_ per input, CUDAGraph.replay()) was ~60 us of that wait.
+// The device scalars of a captured training step (dlrm_amd.graph.GraphedTrainStep) and its replay call (replay.h).
 namespace {
 #define DLRM_MAX_SCALARS 16
 struct SetF32Args { float* dst[DLRM_MAX_SCALARS]; float v[DLRM_MAX_SCALARS]; int n; };
@@ -364,24 +363,8 @@ extern "C" int dlrm_set_f32(int n, float* const* dst_host, const float* values_h
 extern "C" int dlrm_graph_replay(int n, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host,
                                  int n_scalars, float* const* scalar_dst_host, const float* scalar_values_host, void* graph_exec,
                                  int sync_first, void* stream) {
-    if (n < 0 || !graph_exec || (n > 0 && (!dst_host || !src_host || !bytes_host))) return DLRM_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (sync_first) {
-        const hipError_t e = dlrm_stream_wait_polling(st);      // the previous replay: polled for, not slept on (common.h)
-        if (e != hipSuccess) return (int)e;
-    }
-    for (int i = 0; i < n; ++i) {
-        if (!dst_host[i] || !src_host[i] || bytes_host[i] < 0) return DLRM_E_ARG;
-        if (dst_host[i] == src_host[i] || bytes_host[i] == 0) continue;
-        hipError_t e = hipMemcpyAsync(dst_host[i], src_host[i], (size_t)bytes_host[i], hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (n_scalars > 0) {          // the step sizes of this replay (a schedule changed them): written behind the previous replay, in front of this one
-        const int rc = dlrm_set_f32(n_scalars, scalar_dst_host, scalar_values_host, stream);
-        if (rc) return rc;
-    }
-    hipError_t e = hipGraphLaunch((hipGraphExec_t)graph_exec, st);
-    return e == hipSuccess ? 0 : (int)e;
+    // (a step has four inputs: one hipMemcpyAsync per segment whatever their number)
+    return dlrm_replay(n, dst_host, src_host, bytes_host, INT_MAX, n_scalars, scalar_dst_host, scalar_values_host, graph_exec, sync_first, stream);
 }
 
 extern "C" int64_t dlrm_loss_workspace_bytes(int64_t B) {

@@ -4,6 +4,7 @@
 // graph whose whole replay is a few hundred microseconds; here the (destination, source, length) triples travel BY VALUE in the kernarg,
 // like every other multi-table launch of this library, and one grid copies them all.
 #include "common.h"
+#include "replay.h"
 
 namespace {
 
@@ -85,23 +86,5 @@ extern "C" int dlrm_stage_inputs(int n_seg, void* const* dst_host, const void* c
 
 extern "C" int dlrm_forward_replay(int n_seg, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host,
                                    int memcpy_max_segs, void* graph_exec, int sync_first, void* stream) {
-    if (n_seg < 0 || !graph_exec || (n_seg > 0 && (!dst_host || !src_host || !bytes_host))) return DLRM_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (sync_first) {
-        const hipError_t e = dlrm_stream_wait_polling(st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (n_seg <= memcpy_max_segs) {
-        for (int i = 0; i < n_seg; ++i) {
-            if (!dst_host[i] || !src_host[i] || bytes_host[i] < 0) return DLRM_E_ARG;
-            if (dst_host[i] == src_host[i] || bytes_host[i] == 0) continue;
-            const hipError_t e = hipMemcpyAsync(dst_host[i], src_host[i], (size_t)bytes_host[i], hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return (int)e;
-        }
-    } else {
-        const int rc = dlrm_stage_inputs(n_seg, dst_host, src_host, bytes_host, stream);
-        if (rc) return rc;
-    }
-    const hipError_t e = hipGraphLaunch((hipGraphExec_t)graph_exec, st);
-    return e == hipSuccess ? 0 : (int)e;
+    return dlrm_replay(n_seg, dst_host, src_host, bytes_host, memcpy_max_segs, 0, nullptr, nullptr, graph_exec, sync_first, stream);
 }

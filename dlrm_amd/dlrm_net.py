@@ -1172,6 +1172,22 @@ class DLRM_Net(nn.Module):
                 kind = "qr"
         return kind
 
+    def fused_route_now(self, tables: Optional[str] = None, T: Optional[int] = None, D: Optional[int] = None,
+                        grad_wanted: bool = False) -> Optional[FusedRoute]:
+        """fused_route for this model as it is now, on a GPU batch: THE place that reads the model's attributes for it (_fused_forward at
+        every step, which passes the table kind and sizes it already has; GraphedForward and GraphedTrainStep to learn whether an offsets
+        proof is worth its host wait).  None: the two-kernel form."""
+        tables = self._table_kind() if tables is None else tables
+        packed = tables == "quant"
+        if T is None:
+            T, D = (len(self.emb_l_q), self.emb_q_dim) if packed else (len(self.emb_l), self._emb_dim(self.emb_l))
+        return fused_route(
+            tables, 1 + T, D, self.quantize_bits if packed else 0, fuse_emb_interact=self.fuse_emb_interact,
+            fuse_quant_interact=self.fuse_quant_interact, fuse_qr_interact=self.fuse_qr_interact, fuse_bf16_interact=self.fuse_bf16_interact,
+            fuse_narrow_interact=self.fuse_narrow_interact, update_in_backward=self.update_in_backward,
+            interaction_op=self.arch_interaction_op, pooling_weights=any(w is not None for w in (self.v_W_l or [])),
+            grad_wanted=grad_wanted, bf16_rows=self.emb_bf16 is not None)
+
     def _fused_forward(self, dense_x, lS_o, lS_i, B, T, D, rx):
         """The interaction output through the fused lookup + interaction kernels of the route fused_route picks, or None: the two-kernel form.
         What the route cannot know is asked here: B lookups per table, every table's base address a multiple of route.align bytes (one lane's
@@ -1183,13 +1199,8 @@ class DLRM_Net(nn.Module):
             return None                     # (fused_route's first three conditions, asked before anything is looked at)
         tables = self._table_kind()
         packed = tables == "quant"
-        route = fused_route(
-            tables, 1 + T, D, self.quantize_bits if packed else 0, fuse_emb_interact=True, fuse_quant_interact=self.fuse_quant_interact,
-            fuse_qr_interact=self.fuse_qr_interact, fuse_bf16_interact=self.fuse_bf16_interact, fuse_narrow_interact=self.fuse_narrow_interact,
-            update_in_backward=self.update_in_backward, pooling_weights=any(w is not None for w in (self.v_W_l or [])),
-            grad_wanted=packed and torch.is_grad_enabled() and (dense_x.requires_grad or (
-                getattr(self.bot_l, "quant_bits", 32) == 32 and any(p_.requires_grad for p_ in self.bot_l.parameters()))),
-            bf16_rows=self.emb_bf16 is not None)
+        route = self.fused_route_now(tables, T, D, grad_wanted=packed and torch.is_grad_enabled() and (dense_x.requires_grad or (
+            getattr(self.bot_l, "quant_bits", 32) == 32 and any(p_.requires_grad for p_ in self.bot_l.parameters()))))
         if route is None:
             return None
         bags = self._bags(lS_o, lS_i, None)

@@ -11,6 +11,9 @@ Everything the C ABI enqueues is capture-safe by construction: kernels take tabl
 the kernarg segment, nothing allocates or synchronises, scratch buffers come from torch's caching allocator (graph
 private pool during capture) and the segmented sort of the embedding updates is made of plain kernels on the capture stream.
 
+The mechanics (static inputs, capture stream, the one-replay-in-flight rule, the replay call) are graph_core.py's, shared with
+graph_forward.py; here: what is refused, the sort mode, the offsets proof, and the owners DeviceLearningRates and StepStateMirrors.
+
 Constraints (checked, never silently worked around):
   * single process (ext_dist.my_size == 1): RCCL collectives and DDP hooks are not captured;
   * fixed shapes: every call must pass tensors of the shapes/dtypes of the first call (multi-hot batches whose number
@@ -45,63 +48,171 @@ Constraints (checked, never silently worked around):
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Union
-
+import contextlib
+import ctypes as C
 import os as _os
 import sys
 import weakref
+from typing import List, Optional
 
 import torch
 
 from . import ext_dist, ops
+from .graph_core import (Capture, InFlight, StagePlan, TensorOrList, _check_struct, _clone_struct, _copy_struct,  # noqa: F401  (the input
+                         replay)                                                   # helpers stay importable from here)
+from .graph_forward import GraphedForward  # noqa: F401  (the forward pass on the same core: dlrm_amd/graph_forward.py)
 
-TensorOrList = Union[torch.Tensor, Sequence[torch.Tensor]]
 _TRACE = _os.environ.get("DLRM_GTS_TRACE", "0") == "1"
 
 
-def _clone_struct(x: TensorOrList):
-    """Static copies; tensors that appear several times in a list (e.g. one shared offsets tensor for all tables) are
-    cloned once and aliased the same way."""
-    if isinstance(x, torch.Tensor):
-        return x.clone()
-    seen = {}
-    out = []
-    for t in x:
-        if id(t) not in seen:
-            seen[id(t)] = t.clone()
-        out.append(seen[id(t)])
-    return out
+class DeviceLearningRates:
+    """Step sizes on the device: one fp32 scalar per param group, read by the captured update kernels (module docstring, "learning
+    rates"); for any other optimizer only the values the capture baked in."""
+
+    def __init__(self, optimizer):
+        self.optimizer = optimizer
+        # (FusedAdagrad gets here only with device_step_state)
+        self.on_device = type(optimizer).__name__ in ("FusedSGD", "FusedRWSAdagrad", "FusedAdagrad") and _os.environ.get("DLRM_GTS_DEVICE_LR", "1") == "1"
+        self.dev: Optional[torch.Tensor] = None     # [number of param groups at capture time]
+        self.values: List[float] = []               # the captured graph runs with these
+        self.writes = 0                             # replays that carried new step sizes (observability: tests, bench)
+
+    def current(self) -> List[float]:
+        return [float(g["lr"]) for g in self.optimizer.param_groups]
+
+    def valid(self) -> bool:
+        """False: re-capture (another number of param groups than the scalars were made for; a host step size baked into the capture)"""
+        return len(self.optimizer.param_groups) == len(self.values) and (self.on_device or self.current() == self.values)
+
+    @contextlib.contextmanager
+    def capturing(self, dev):
+        """Around a capture: the scalars, holding the CURRENT lr, handed to the update kernels (ops._graph_lr) for the duration of the
+        capture only, so that an eager step of the same optimizer outside the graph keeps passing its host value"""
+        groups = list(self.optimizer.param_groups)
+        self.dev = torch.tensor(self.current(), dtype=torch.float32, device=dev) if self.on_device else None
+        for i, g in enumerate(groups if self.on_device else ()):
+            ops._graph_lr[id(g)] = self.dev[i:i + 1]
+        try:
+            yield
+        finally:
+            for g in groups:
+                ops._graph_lr.pop(id(g), None)
+        self.values = self.current()
+
+    def changed(self):
+        """(count, device pointers, values) of the step sizes this replay must write first, or None: every group's value whenever any
+        changed (at most 16 go with the replay call, more are written right here); never for another group count than the captured one"""
+        if self.dev is None:
+            return None
+        lrs = self.current()
+        n = len(lrs)
+        if lrs == self.values or n != self.dev.numel():
+            return None
+        self.values = lrs
+        self.writes += 1
+        if n > 16:
+            ops.set_f32([self.dev[i:i + 1] for i in range(n)], lrs)
+            return None
+        base = self.dev.data_ptr()
+        return n, (C.c_void_p * n)(*[base + 4 * i for i in range(n)]), (C.c_float * n)(*lrs)
 
 
-def _copy_now(d: torch.Tensor, s_: torch.Tensor) -> None:
-    d.copy_(s_, non_blocking=True)
+class StepStateMirrors:
+    """Step state (device_step_state; module docstring): what ONE replay advances — bf16 key draws and (parameter, state["step"]
+    increment) pairs, found at capture time — the replays the host mirrors have not taken in yet, and the device counter of update calls."""
+
+    def __init__(self, model, optimizer, enabled: bool, bf16: bool):
+        self.model, self.optimizer, self.enabled, self.bf16 = model, optimizer, enabled, bf16
+        self.step_dev = None       # ops.DeviceStepState
+        self.draws, self.deltas, self.unsettled = 0, [], 0
+        self.calls_seen = 0        # model._bf16_update_calls when the device counter last agreed with it (resync)
+        self._hooks = []
+        if enabled:
+            settle = weakref.WeakMethod(self.settle)        # (the optimizer and the model must not keep this object alive)
+
+            def _observed(*_args, _m=settle):
+                f = _m()
+                if f is not None:
+                    f()
+            # the observation points of the host mirrors: state_dict(), load_state_dict(), an eager optimizer step; the model calls the
+            # same function in front of an eager bf16 key draw, which comes before the optimizer's own pre-hooks (a global hook)
+            self._hooks = [optimizer.register_state_dict_pre_hook(_observed), optimizer.register_load_state_dict_pre_hook(_observed),
+                           optimizer.register_step_pre_hook(_observed)]
+            model._step_state_settle = _observed
+
+    def __del__(self):
+        try:
+            self.settle()
+            for h in self._hooks:
+                h.remove()
+        except Exception:                                   # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def settle(self) -> None:
+        """Host mirrors <- the replays since the last call: model._bf16_update_calls and every optimizer.state[p]["step"] the captured step
+        advances read as if those replays had been eager steps.  Pure host arithmetic (a replay advances them by known amounts): no wait,
+        no per-replay work — called where someone can observe the counters (the hooks of __init__, _drop_graph, a re-capture)."""
+        n, self.unsettled = self.unsettled, 0
+        if not n:
+            return
+        if self.draws:
+            self.model._bf16_update_calls += self.draws * n
+            self.calls_seen = self.model._bf16_update_calls
+        state = self.optimizer.state
+        for p, d in self.deltas:
+            st = state.get(p)
+            if st is not None and "step" in st:
+                st["step"] = st["step"] + d * n
+
+    def resync(self) -> None:
+        """In front of a replay: EAGER bf16 update calls since the device counter was last written (a step taken outside this object) moved
+        the host counter on; the device counter follows, written in stream order.  One comparison per replay otherwise."""
+        sd = self.step_dev
+        if sd is not None and self.model._bf16_update_calls != self.calls_seen:
+            self.settle()           # (the eager draw settled already: nothing is pending; kept for a counter someone set by hand)
+            self.calls_seen = self.model._bf16_update_calls
+            sd.calls.fill_(self.calls_seen)
+
+    @contextlib.contextmanager
+    def capturing(self, dev, cap: Capture):
+        """Around a capture, which starts from settled host counters: (calls, key) on the device, registered for its duration only.
+        Afterwards: what one replay advances.  The capture RECORDED a step and ran none, yet its Python side advanced the optimizer's
+        step counts: they are put back, so that every replay — the one that executes this step included — counts the same way."""
+        self.settle()
+        self.step_dev, self.draws, self.deltas = None, 0, []
+        if not self.enabled:
+            yield
+            return
+        state = self.optimizer.state
+        before = {id(p): (st["step"].clone() if isinstance(st["step"], torch.Tensor) else st["step"]) for p, st in state.items() if "step" in st}
+        if self.bf16:
+            sd = self.step_dev = ops.DeviceStepState(self.model._bf16_update_calls, dev)
+            self.calls_seen = self.model._bf16_update_calls
+            ops._graph_step_state[id(self.model)] = sd
+        try:
+            yield
+        finally:
+            ops._graph_step_state.pop(id(self.model), None)
+        for p, st in state.items():
+            if "step" not in st:
+                continue
+            was = before.get(id(p), 0)
+            d = st["step"] - was
+            if float(d) != 0.0:
+                st["step"] = was
+                self.deltas.append((p, d))
+        if self.bf16:
+            if sd.draws < 1 or sd.draws != sd.passes:
+                cap.reset()
+                self.step_dev, self.deltas = None, []
+                raise RuntimeError("dlrm_amd.graph: the captured step drew %d bf16 rounding keys for %d parked backward passes (one per pass "
+                                   "is what a replay can follow); use the eager step" % (sd.draws, sd.passes))
+            self.draws = sd.draws
 
 
-def _copy_struct(dst: TensorOrList, src: TensorOrList, put=_copy_now) -> None:
-    """static buffers <- the caller's tensors: `put(dst_tensor, src_tensor)` for every distinct tensor whose storage differs, after the
-    shape / dtype checks (default: an ATen copy_ each; the raw replay path collects the pairs for dlrm_graph_replay instead).  (All copies
-    in ONE launch of the library's block copy was measured too: building its views costs the host more than the four copy_ calls it
-    replaces, and the host is what the GPU waits for between replays — Criteo-Kaggle graph 0.378 -> 0.406 ms, profiles/round5/kaggle_towers.md.)"""
-    if isinstance(dst, torch.Tensor):
-        if not isinstance(src, torch.Tensor) or src.shape != dst.shape or src.dtype != dst.dtype:
-            raise RuntimeError("dlrm_amd.graph: input shape/dtype differs from the captured step")
-        if src.data_ptr() != dst.data_ptr():
-            put(dst, src)
-        return
-    if isinstance(src, torch.Tensor) or len(src) != len(dst):
-        raise RuntimeError("dlrm_amd.graph: input structure differs from the captured step")
-    done = set()
-    for d, s_ in zip(dst, src):
-        if s_.shape != d.shape or s_.dtype != d.dtype:
-            raise RuntimeError("dlrm_amd.graph: input shape/dtype differs from the captured step "
-                               "(variable-length multi-hot batches cannot be replayed)")
-        if id(d) in done or s_.data_ptr() == d.data_ptr():
-            continue
-        done.add(id(d))
-        # one copy per distinct tensor.  (torch._foreach_copy_ on int64 lists raised GPU memory faults on
-        # torch 2.10 + ROCm 7 at B = 65536 — profiles/r02/graph_probe.md; pass stacked [T, B] index / offset tensors to
-        # make this a single copy.)
-        put(d, s_)
+def _held_by(owner: str, name: str):
+    """an attribute of the step object that lives in one of its owners (the tests and tools read and set these names on the step)"""
+    return property(lambda self: getattr(getattr(self, owner), name), lambda self, v: setattr(getattr(self, owner), name, v))
 
 
 class GraphedTrainStep:
@@ -154,84 +265,26 @@ class GraphedTrainStep:
         # workspace per backward pass and binds to the optimizer's first EAGER step: not part of a captured step)
         model.update_in_backward = False
         self.warmup = max(int(warmup), 1)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.stream: Optional[torch.cuda.Stream] = None
+        self.cap = Capture()        # stream, graph, raw handle, pinned scratch, out (the predictions of the last step)
+        self.flight = InFlight()
         self.static = None
+        self.plan: Optional[StagePlan] = None
         self.loss: Optional[torch.Tensor] = None
-        self.out: Optional[torch.Tensor] = None
-        self._lrs: List[float] = []
-        # step sizes on the device: one fp32 scalar per param group, read by the captured update kernels (module docstring)
-        # (FusedAdagrad gets here only with device_step_state)
-        self._lr_on_device = (type(optimizer).__name__ in ("FusedSGD", "FusedRWSAdagrad", "FusedAdagrad")
-                              and _os.environ.get("DLRM_GTS_DEVICE_LR", "1") == "1")
-        self._lr_dev: Optional[torch.Tensor] = None
-        self.lr_writes = 0          # replays that carried new step sizes (observability: tests, bench)
+        self.lrs = DeviceLearningRates(optimizer)
+        self.state = StepStateMirrors(model, optimizer, self.device_step_state, self._bf16)
         self.captures = 0
         self._eager_calls = 0
-        self._replayed = False
-        self.serialize = _os.environ.get("DLRM_GTS_SERIALIZE", "1") == "1"
+        self._keep = None
         # raw replay: wait + input copies + hipGraphLaunch in ONE C call (dlrm_graph_replay) instead of stream.synchronize(), a copy_ per
         # input and CUDAGraph.replay() from Python — the host path is what a launch-bound step waits for.  DLRM_GTS_RAW=0: the torch calls.
         self.raw = _os.environ.get("DLRM_GTS_RAW", "1") == "1"
-        self._exec = None          # hipGraphExec_t of the captured step (None: not available -> torch's replay)
-        self._raw_arrays = None    # cached ctypes arrays of the raw call
-        # step state (device_step_state): what ONE replay advances — bf16 key draws and (parameter, state["step"] increment) pairs, found at
-        # capture time — and the replays the host mirrors have not taken in yet (_settle)
-        self._step_dev = None      # ops.DeviceStepState the captured kernels read and advance
-        self._draws = 0
-        self._step_deltas = []
-        self._unsettled = 0
-        self._calls_seen = 0       # model._bf16_update_calls when the device counter last agreed with it (_resync_step_state)
-        if self.device_step_state:
-            settle = weakref.WeakMethod(self._settle)       # (the optimizer and the model must not keep this object alive)
 
-            def _observed(*_args, _m=settle):
-                f = _m()
-                if f is not None:
-                    f()
-            # the observation points of the host mirrors: state_dict(), load_state_dict(), an eager optimizer step; the model calls the
-            # same function in front of an eager bf16 key draw, which comes before the optimizer's own pre-hooks (a global hook)
-            self._hooks = [optimizer.register_state_dict_pre_hook(_observed), optimizer.register_load_state_dict_pre_hook(_observed),
-                           optimizer.register_step_pre_hook(_observed)]
-            model._step_state_settle = _observed
-
-    def __del__(self):
-        try:
-            self._settle()
-            for h in getattr(self, "_hooks", ()):
-                h.remove()
-        except Exception:                                   # noqa: BLE001 - interpreter shutdown
-            pass
+    graph, stream, out, _exec = (_held_by("cap", n) for n in ("graph", "stream", "out", "exec"))
+    _lr_on_device, lr_writes = _held_by("lrs", "on_device"), _held_by("lrs", "writes")
+    _draws, _step_deltas, _unsettled = (_held_by("state", n) for n in ("draws", "deltas", "unsettled"))
 
     def _settle(self) -> None:
-        """Host mirrors <- the replays since the last call: model._bf16_update_calls and every optimizer.state[p]["step"] the captured step
-        advances read as if those replays had been eager steps.  Pure host arithmetic (a replay advances them by known amounts): no wait,
-        no per-replay work — called where someone can observe the counters (the hooks of __init__, _drop_graph, a re-capture)."""
-        n, self._unsettled = self._unsettled, 0
-        if not n:
-            return
-        if self._draws:
-            self.model._bf16_update_calls += self._draws * n
-            self._calls_seen = self.model._bf16_update_calls
-        state = self.optimizer.state
-        for p, d in self._step_deltas:
-            st = state.get(p)
-            if st is not None and "step" in st:
-                st["step"] = st["step"] + d * n
-
-    def _resync_step_state(self) -> None:
-        """In front of a replay: EAGER bf16 update calls since the device counter was last written (a step taken outside this object) moved
-        the host counter on; the device counter follows, written in stream order.  One comparison per replay otherwise."""
-        sd = self._step_dev
-        if sd is not None and self.model._bf16_update_calls != self._calls_seen:
-            self._settle()          # (the eager draw settled already: nothing is pending; kept for a counter someone set by hand)
-            self._calls_seen = self.model._bf16_update_calls
-            sd.calls.fill_(self._calls_seen)
-
-    def _step_counts(self):
-        """id(parameter) -> its state["step"] now (python numbers, or a copy of a tensor)"""
-        return {id(p): (st["step"].clone() if isinstance(st["step"], torch.Tensor) else st["step"])
-                for p, st in self.optimizer.state.items() if "step" in st}
+        self.state.settle()
 
     def _settle_sort_mode(self, lS_o, lS_i) -> None:
         """First batch: keep the sort-based embedding update only if every table segment goes through the library's own segmented
@@ -280,13 +333,11 @@ class GraphedTrainStep:
             return
         # (a model that cannot take the fused path anyway — Criteo-Kaggle's D = 16, a cat interaction, pooling weights — needs no proof: a
         # per-replay host wait doubled that launch-bound step when every replay brought a new offsets tensor)
-        try:
-            D = model.emb_l[0].weight.size(1)
-            if (getattr(model, "arch_interaction_op", "dot") != "dot" or not ops.gather_ok(1 + len(model.emb_l), D)
-                    or any(w is not None for w in (getattr(model, "v_W_l", None) or []))):
+        ask = getattr(model, "fused_route_now", None)
+        if ask is not None:
+            route = ask()
+            if route is None or not route.none_fused:       # (undecided offsets inside the capture take the two-kernel form anyway)
                 return
-        except (AttributeError, IndexError, TypeError):
-            pass
         n_i = lS_i.size(-1) if isinstance(lS_i, torch.Tensor) else None
         n_o = lS_o.size(-1) if isinstance(lS_o, torch.Tensor) else None
         if isinstance(lS_i, torch.Tensor) != isinstance(lS_o, torch.Tensor) or (n_i is not None and n_i != n_o):
@@ -298,16 +349,15 @@ class GraphedTrainStep:
             self._drop_graph(lS_o)
 
     def _drop_graph(self, like) -> None:
-        """forget the captured step (the next call re-captures): the replay in flight is waited for first, and the raw handle and its
-        cached argument arrays go with the graph — a dangling hipGraphExec_t must never reach dlrm_graph_replay"""
-        if self.graph is None:
+        """forget the captured step (the next call re-captures): the replay in flight is waited for first, and the raw handle goes with
+        the graph (Capture.reset)"""
+        if self.cap.graph is None:
             return
-        self._settle()
+        self.state.settle()
         dev = like.device if isinstance(like, torch.Tensor) else like[0].device
         torch.cuda.current_stream(dev).synchronize()
-        self._replayed = False
-        self.graph.reset()
-        self.graph, self._exec, self._raw_arrays = None, None, None
+        self.flight.pending = False
+        self.cap.reset()
 
     # one eager training step on the static buffers (the reference loop body)
     def _eager(self):
@@ -328,185 +378,49 @@ class GraphedTrainStep:
         self.optimizer.step()
         return Z, E
 
-    def _current_lrs(self) -> List[float]:
-        return [float(g["lr"]) for g in self.optimizer.param_groups]
-
-    def _capture(self) -> None:
-        if ops.timers is not None:
-            raise RuntimeError("dlrm_amd.graph: per-kernel event timers cannot be recorded inside a graph capture")
-        dev = self.static[0].device
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=dev)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        if self.graph is not None:
-            self.graph.reset()
-        self.graph = torch.cuda.CUDAGraph()
-        groups = self.optimizer.param_groups
-        model = self.model
-        self._settle()              # a re-capture starts from settled host counters
-        self._step_dev, self._draws, self._step_deltas, before = None, 0, [], None
-        if self.device_step_state:
-            before = self._step_counts()
-            if self._bf16:
-                # (calls, key) on the device, calls = the host counter; registered, like the step sizes below, for the duration of the capture only
-                self._step_dev = ops.DeviceStepState(model._bf16_update_calls, dev)
-                self._calls_seen = model._bf16_update_calls
-                self.stream.wait_stream(torch.cuda.current_stream(dev))
-                ops._graph_step_state[id(model)] = self._step_dev
-        if self._lr_on_device:
-            # one device scalar per param group, holding the CURRENT lr; registered for the duration of the capture only, so that an eager
-            # step of the same optimizer outside the graph keeps passing its host value
-            self._lr_dev = torch.tensor(self._current_lrs(), dtype=torch.float32, device=dev)
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-            for i, g in enumerate(groups):
-                ops._graph_lr[id(g)] = self._lr_dev[i:i + 1]
-        try:
-            # backward runs on the autograd engine's thread: "relaxed" lets that thread enqueue into the capturing stream
-            with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="relaxed"):
-                Z, E = self._eager()
-        finally:
-            for g in groups:
-                ops._graph_lr.pop(id(g), None)
-            ops._graph_step_state.pop(id(model), None)
-        if before is not None:
-            self._adopt_step_state(before)
-        self.out, self.loss = Z.detach(), E.detach()
-        self._lrs = self._current_lrs()
-        # the graph holds raw pointers into the cached scratch workspaces: pin those tensors so that a later, larger
-        # request elsewhere (which replaces the cache entry) cannot free memory the replays still use
-        self._pinned_ws = [w for (_, d_, _), w in ops._scratch_ws.items() if d_ == dev]
+    def _capture(self, dev) -> None:
+        self.cap.reset()             # (before the owners replace device state the previous graph reads)
+        with self.lrs.capturing(dev), self.state.capturing(dev, self.cap):
+            Z, E = self.cap.record(dev, self._eager, raw=self.raw)
+        self.cap.out, self.loss = Z.detach(), E.detach()
         self.captures += 1
-        self._exec, self._raw_arrays = None, None
-        if self.raw:
-            try:
-                self._exec = int(self.graph.raw_cuda_graph_exec())
-            except Exception:                               # noqa: BLE001 - a torch without the raw handle: keep its own replay
-                self._exec = None
-        torch.cuda.current_stream(dev).wait_stream(self.stream)
-
-    def _adopt_step_state(self, before) -> None:
-        """After a capture: what one replay advances.  The capture RECORDED a step and ran none, yet its Python side advanced the optimizer's
-        step counts: they are put back, so that every replay — the one that executes this step included — counts the same way (_settle)."""
-        for p, st in self.optimizer.state.items():
-            if "step" not in st:
-                continue
-            was = before.get(id(p), 0)
-            d = st["step"] - was
-            if float(d) != 0.0:
-                st["step"] = was
-                self._step_deltas.append((p, d))
-        sd = self._step_dev
-        if sd is not None:
-            if sd.draws < 1 or sd.draws != sd.passes:
-                self.graph.reset()
-                self.graph, self._exec, self._raw_arrays, self._step_dev, self._step_deltas = None, None, None, None, []
-                raise RuntimeError("dlrm_amd.graph: the captured step drew %d bf16 rounding keys for %d parked backward passes (one per pass "
-                                   "is what a replay can follow); use the eager step" % (sd.draws, sd.passes))
-            self._draws = sd.draws
-
-    def _changed_lrs(self):
-        """(count, device pointers, values) of the step sizes this replay must write first: every group's value whenever any changed (a
-        schedule moves all groups together; at most 16 go with dlrm_graph_replay, more are written by dlrm_set_f32 right here)"""
-        import ctypes as C
-        if not self._lr_on_device or self._lr_dev is None:
-            return 0, None, None
-        lrs = self._current_lrs()
-        if lrs == self._lrs:
-            return 0, None, None
-        self._lrs = lrs
-        self.lr_writes += 1
-        n = len(lrs)
-        if n > 16:
-            ops.set_f32([self._lr_dev[i:i + 1] for i in range(n)], lrs)
-            return 0, None, None
-        base = self._lr_dev.data_ptr()
-        return n, (C.c_void_p * n)(*[base + 4 * i for i in range(n)]), (C.c_float * n)(*lrs)
-
-    def _lr_current_or_on_device(self) -> bool:
-        """True when the captured graph is valid for the optimizer's present learning rates"""
-        return self._lr_on_device or self._lrs == self._current_lrs()
-
-    def _raw_replay(self, X, lS_o, lS_i, T) -> bool:
-        """the steady state: inputs checked and collected, then ONE call that waits for the previous replay, copies and launches"""
-        import ctypes as C
-        from . import _lib
-        pairs = []
-        xs, os_, is_, ts = self.static
-        put = lambda d, s_: pairs.append((d, s_))           # noqa: E731
-        _copy_struct(xs, X, put); _copy_struct(os_, lS_o, put); _copy_struct(is_, lS_i, put); _copy_struct(ts, T, put)
-        n = len(pairs)
-        for d, s_ in pairs:
-            if not (d.is_cuda and s_.is_cuda and s_.device == d.device and d.is_contiguous() and s_.is_contiguous()):
-                return False                                # (host tensors, strided views: torch's copy_ handles them)
-        arr = self._raw_arrays
-        if arr is None or arr[0] != n:
-            arr = self._raw_arrays = (n, (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))(), (C.c_int64 * max(n, 1))())
-        _, dst, src, nbytes = arr
-        for i, (d, s_) in enumerate(pairs):
-            dst[i], src[i], nbytes[i] = d.data_ptr(), s_.data_ptr(), d.numel() * d.element_size()
-        ns, sdst, sval = self._changed_lrs()
-        self._resync_step_state()
-        rc = _lib.load().dlrm_graph_replay(n, dst, src, nbytes, ns, sdst, sval, C.c_void_p(self._exec), int(self._replayed),
-                                           C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream))
-        _lib.check(rc, "dlrm_graph_replay")
-        self._unsettled += 1                                # (host mirrors of the step state: taken in lazily, _settle)
-        self._keep = pairs                                  # the sources stay alive until the next call (their copies are asynchronous)
-        self._replayed = self.serialize
-        return True
 
     def __call__(self, X, lS_o, lS_i, T):
-        if (self._exec is not None and self.static is not None and self.graph is not None and self._eager_calls >= self.warmup
-                and self._lr_current_or_on_device() and not _TRACE):
+        cap, flight = self.cap, self.flight
+        request = (X, lS_o, lS_i, T)
+        dev = X.device if self.static is None else self.static[0].device
+        # the steady state: the request checked, then ONE call that waits for the previous replay, copies and launches (graph_core.replay)
+        raw = False
+        if cap.exec is not None and self.lrs.valid() and not _TRACE:    # (a raw handle: captured, after the warm-up calls)
             self._prove_one_lookup_per_bag(lS_o, lS_i)
-            if self.graph is not None and self._raw_replay(X, lS_o, lS_i, T):
+            if cap.exec is not None:                        # (the proof may have dropped the graph)
+                for s_, r in zip(self.static, request):
+                    _check_struct(s_, r)
+                raw = self.plan.takes(request)              # (host tensors, strided views: torch's copy_ handles them)
+        if not raw:
+            if _TRACE:
+                print("[gts] call eager=%d captures=%d replay_in_flight=%s" % (self._eager_calls, self.captures, flight.pending),
+                      flush=True)
+            flight.wait(torch.cuda.current_stream(dev))     # before the static inputs are touched again (graph_core.InFlight)
+            self._prove_one_lookup_per_bag(lS_o, lS_i)
+            if self.static is None:
+                self._settle_sort_mode(lS_o, lS_i)
+                self.static = (X.clone(), _clone_struct(lS_o), _clone_struct(lS_i), T.clone())
+                self.plan = StagePlan(self.static, request)
+            else:
+                for s_, r in zip(self.static, request):
+                    _copy_struct(s_, r)
+            if self._eager_calls < self.warmup:
+                # the first calls are ordinary eager steps, issued on the stream the capture will use
+                Z, E = cap.run(dev, self._eager)
+                self._eager_calls += 1
+                cap.out, self.loss = Z.detach(), E.detach()
                 return self.loss
-        if _TRACE:
-            print("[gts] call eager=%d captures=%d replay_in_flight=%s" % (self._eager_calls, self.captures, self._replayed),
-                  flush=True)
-        if self._replayed:
-            # at most ONE replay in flight, and a full stream synchronisation between replays.  Two launches of the same
-            # executable graph queued behind each other overlapped on ROCm 7.2 (they share every intermediate buffer), and
-            # event waits alone were not enough once the application synchronised the stream somewhere in between
-            # (profiles/r02/graph_probe.md, b and d): the pattern that was clean in every probe is "synchronise the stream
-            # after every replay", so that is what happens here before the static inputs are touched again.  At
-            # Criteo-Terabyte sizes the GPU is the bottleneck (the wait costs one launch latency per step); at launch-bound
-            # sizes the replay has finished long before the host gets here.
-            ops.wait_spinning(torch.cuda.current_stream(X.device))      # (polled, not slept on: see ops.wait_spinning)
-            self._replayed = False
-        self._prove_one_lookup_per_bag(lS_o, lS_i)
-        if self.static is None:
-            self._settle_sort_mode(lS_o, lS_i)
-            self.static = (X.clone(), _clone_struct(lS_o), _clone_struct(lS_i), T.clone())
-        else:
-            xs, os_, is_, ts = self.static
-            _copy_struct(xs, X)
-            _copy_struct(os_, lS_o)
-            _copy_struct(is_, lS_i)
-            _copy_struct(ts, T)
-        dev = X.device
-        if self._eager_calls < self.warmup:
-            # the first calls are ordinary eager steps, issued on the stream the capture will use so that kernel
-            # attributes, scratch workspaces and allocator pools are those the graph will see
-            if self.stream is None:
-                self.stream = torch.cuda.Stream(device=dev)
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(self.stream):
-                Z, E = self._eager()
-            torch.cuda.current_stream(dev).wait_stream(self.stream)
-            self._eager_calls += 1
-            self.out, self.loss = Z.detach(), E.detach()
-            return self.loss
-        if self.graph is None or not self._lr_current_or_on_device():
-            self._capture()          # capture only records; the replay below executes this step
-        ns, sdst, sval = self._changed_lrs()
-        if ns:                       # torch's replay path: the new step sizes go in front of the launch on the same stream
-            from . import _lib
-            _lib.check(_lib.load().dlrm_set_f32(ns, sdst, sval, torch.cuda.current_stream(dev).cuda_stream), "dlrm_set_f32")
-        self._resync_step_state()
-        self.graph.replay()
-        self._unsettled += 1
-        self._replayed = self.serialize
+            if cap.graph is None or not self.lrs.valid():
+                self._capture(dev)       # capture only records; the replay below executes this step
+        scalars = self.lrs.changed()
+        self.state.resync()
+        replay(cap, flight, torch.cuda.current_stream(dev), self.plan, request, scalars=scalars, staged=not raw)
+        self.state.unsettled += 1                           # (host mirrors of the step state: taken in lazily, settle)
+        self._keep = request                                # the sources stay alive until the next call (their copies are asynchronous)
         return self.loss
-
-
-from .graph_forward import GraphedForward  # noqa: E402,F401  (the forward pass's twin of GraphedTrainStep: dlrm_amd/graph_forward.py)

@@ -1,13 +1,13 @@
 """Whole-forward HIP graph for small-batch serving: `model(X, lS_o, lS_i)` under no_grad captured once per shape and replayed with one
 host call per request (dlrm_forward_replay: wait for the previous replay, stage the request into the static buffers, hipGraphLaunch).
-The twin of graph.GraphedTrainStep, which captures a training step and therefore refuses the inference models (packed tables, int8 /
-fp16 towers); re-exported as dlrm_amd.graph.GraphedForward.
+The counterpart of graph.GraphedTrainStep, which captures a training step and therefore refuses the inference models (packed tables, int8 /
+fp16 towers); both stand on graph_core.py (Capture, InFlight, StagePlan, replay); re-exported as dlrm_amd.graph.GraphedForward.
 
     fwd = GraphedForward(model, batch_sizes=(64, 256, 2048))
     Z = fwd(X, lS_o, lS_i)          # [n, 1] view of a static buffer, valid until the next call
 
 What is captured is the model's own forward, unchanged: every table kind and tower kind whose forward is built.  The rules of
-GraphedTrainStep._capture hold (own stream, no event timers, the scratch workspaces of the capture pinned, single stream, single process).
+graph_core.Capture hold (own stream, no event timers, the scratch workspaces of the capture pinned, single stream, single process).
 
 Shapes.  Without `batch_sizes` every distinct request shape gets its own graph (at most `max_exact_shapes`, least recently used dropped).
 With `batch_sizes` a request of n rows whose lookup structure is FIXED — table k has exactly P_k lookups in every bag, offsets ==
@@ -35,8 +35,6 @@ from __future__ import annotations
 
 import collections
 import contextlib
-import ctypes as C
-import os as _os
 import sys
 import weakref
 from typing import Optional, Sequence, Tuple
@@ -44,10 +42,8 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import ext_dist, ops
-
-STAGE_MEMCPY_MAX = 4        # requests of at most this many segments are staged with one hipMemcpyAsync each (stacked inputs), more with one
-                            # dlrm_stage_inputs launch (profiles/graph_forward/rates.md)
-STAGE_SEGS_PER_LAUNCH = 64  # DLRM_MAX_STAGE_SEGS of csrc/stage.hip
+from .graph_core import (STAGE_MEMCPY_MAX, STAGE_SEGS_PER_LAUNCH, Capture, InFlight, StagePlan, _clone_struct,  # noqa: F401  (the constants
+                         replay, stage)                                                  # and StagePlan stay importable from here)
 
 
 # ------------------------------------------------------------------------------------------------ host logic (no device needed)
@@ -161,74 +157,6 @@ class LRU:
         return len(self._d)
 
 
-class StagePlan:
-    """The segment list of one graph: static buffers <- a request of the same input structure, as the ctypes arrays of
-    dlrm_forward_replay.  Built ONCE per graph (destinations never change); patch() writes the source pointers and lengths of a request.
-      X          one segment: the request's n rows are the head of the static [B, m] buffer;
-      a list     one segment per DISTINCT static tensor (alias_pattern), the request's tensor at the first position that maps to it;
-      stacked    one segment, the whole [T, n'] tensor — unless its group is named in `by_rows`: then the T rows, each into the head of
-                 its row of the static buffer.  A BUCKET names its stacked indices there whatever the width of the request the plan is
-                 built from: a later request of the same key may be narrower, and T rows laid end to end are not the heads of T rows.
-    A group whose static is None is not staged (a bucket's offsets never change).  patch() refuses a segment longer than its destination."""
-
-    def __init__(self, statics: Sequence, like: Sequence, by_rows: Sequence[int] = ()):
-        self.entries = []       # (group, position in the list or None, row or None)
-        dst, cap = [], []
-        for g, (s, r) in enumerate(zip(statics, like)):
-            if s is None:
-                continue
-            if isinstance(s, torch.Tensor):
-                if not isinstance(r, torch.Tensor) or r.dtype != s.dtype or r.dim() != s.dim():
-                    raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
-                if g in by_rows:
-                    if s.dim() != 2 or r.size(0) != s.size(0) or r.size(1) > s.size(1) or (s.size(1) > 1 and s.stride(1) != 1):
-                        raise RuntimeError("dlrm_amd.graph: a stacked input does not fit its static buffer")
-                    for k in range(s.size(0)):
-                        self.entries.append((g, None, k))
-                        dst.append(s.data_ptr() + k * s.stride(0) * s.element_size())
-                        cap.append(s.size(1) * s.element_size())
-                else:
-                    if s.dim() == 2 and r.size(1) != s.size(1):
-                        raise RuntimeError("dlrm_amd.graph: a stacked input narrower than its static buffer is staged by rows (by_rows)")
-                    self.entries.append((g, None, None))
-                    dst.append(s.data_ptr())
-                    cap.append(s.numel() * s.element_size())
-                continue
-            if isinstance(r, torch.Tensor) or len(r) != len(s):
-                raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
-            seen = set()
-            for k, t in enumerate(s):
-                if id(t) in seen:
-                    continue
-                seen.add(id(t))
-                self.entries.append((g, k, None))
-                dst.append(t.data_ptr())
-                cap.append(t.numel() * t.element_size())
-        self.n = len(dst)
-        m = max(self.n, 1)
-        self.cap = cap
-        self.dst = (C.c_void_p * m)(*dst)
-        self.src = (C.c_void_p * m)()
-        self.nbytes = (C.c_int64 * m)()
-
-    def patch(self, request: Sequence) -> None:
-        src, nbytes, cap = self.src, self.nbytes, self.cap
-        for j, (g, k, row) in enumerate(self.entries):
-            t = request[g] if k is None else request[g][k]
-            if row is None:
-                p, nb = t.data_ptr(), t.numel() * t.element_size()
-            else:
-                nb = t.size(1) * t.element_size()
-                p = t.data_ptr() + row * nb
-            if nb > cap[j]:
-                raise RuntimeError("dlrm_amd.graph: an input is larger than the static buffer it is staged into")
-            src[j], nbytes[j] = p, nb
-
-    def launches(self, memcpy_max: int) -> int:
-        """kernel launches of one staging (0: the memcpy path)"""
-        return 0 if self.n <= memcpy_max else (self.n + STAGE_SEGS_PER_LAUNCH - 1) // STAGE_SEGS_PER_LAUNCH
-
-
 def model_tensors(model) -> list:
     """the tensors a forward reads through raw pointers: the tables (packed ones first), then every parameter, then the towers' packed
     int8 weights"""
@@ -256,14 +184,15 @@ def fingerprint(model, tensors: Sequence) -> tuple:
     return model_scalars(model) + (tensors[0].data_ptr(), tensors[-1].data_ptr())
 
 
-class _Graph:
-    __slots__ = ("key", "bucket", "n", "static", "plan", "graph", "exec", "out", "eager_calls", "pinned_ws", "views", "iota")
+class _Graph(Capture):
+    """one captured forward: the capture plus its key, static inputs and plan"""
+    __slots__ = ("key", "bucket", "n", "static", "plan", "eager_calls", "views", "iota")
 
-    def __init__(self, key, bucket, n):
+    def __init__(self, key, bucket, n, stream):
+        super().__init__(stream)
         self.key, self.bucket, self.n = key, bucket, n
-        self.static = self.plan = self.graph = self.exec = self.out = None
+        self.static = self.plan = None
         self.eager_calls = 0
-        self.pinned_ws = None
         self.views = {}
         self.iota = None          # the offsets verdict the forward on the static buffers runs with (None: no fused route asks)
 
@@ -289,10 +218,9 @@ class GraphedForward:
         self.warmup = max(int(warmup), 1)
         self.stream: Optional[torch.cuda.Stream] = None
         self.stage_memcpy_max = STAGE_MEMCPY_MAX
-        self.serialize = _os.environ.get("DLRM_GTS_SERIALIZE", "1") == "1"      # one replay in flight (graph.py: the ROCm 7.2 rule)
+        self.flight = InFlight()    # one replay in flight
         self._exact = LRU(max_exact_shapes)
         self._buckets: dict = {}
-        self._in_flight = False
         self._keep = None
         self._tensors: list = []
         self._fp = None
@@ -319,8 +247,7 @@ class GraphedForward:
         """forget every captured graph (the next calls capture again) — after anything that moved a tensor the forward reads"""
         self._wait()
         for g in self._exact.values() + list(self._buckets.values()):
-            if g.graph is not None:
-                g.graph.reset()
+            g.reset()
         self._exact.clear()
         self._buckets.clear()
         self._keep = None
@@ -338,29 +265,16 @@ class GraphedForward:
         """does this model have fused lookup + interaction kernels at all (dlrm_net.fused_route, asked as DLRM_Net._fused_forward asks under
         no_grad)?  Only then is a request's offsets proof worth its host wait."""
         m = self.model
-        if not (getattr(m, "fuse_emb_interact", False) and hasattr(m, "_table_kind")):
+        if not (getattr(m, "fuse_emb_interact", False) and hasattr(m, "fused_route_now")):
             return False
-        from .dlrm_net import DLRM_Net, fused_route
+        from .dlrm_net import DLRM_Net
         if type(m).sequential_forward is not DLRM_Net.sequential_forward:
             return False                      # (the cat-interaction variants bring their own forward: no route)
-        tables = m._table_kind()
-        packed = tables == "quant"
-        try:
-            T, D = (len(m.emb_l_q), m.emb_q_dim) if packed else (len(m.emb_l), m._emb_dim(m.emb_l))
-        except (AttributeError, IndexError, TypeError):
-            return False
-        return fused_route(tables, 1 + T, D, m.quantize_bits if packed else 0, fuse_emb_interact=True,
-                           fuse_quant_interact=m.fuse_quant_interact, fuse_qr_interact=m.fuse_qr_interact,
-                           fuse_bf16_interact=m.fuse_bf16_interact, fuse_narrow_interact=m.fuse_narrow_interact,
-                           update_in_backward=m.update_in_backward, interaction_op=m.arch_interaction_op,
-                           pooling_weights=any(w is not None for w in (m.v_W_l or [])), grad_wanted=False,
-                           bf16_rows=m.emb_bf16 is not None) is not None
+        return m.fused_route_now() is not None
 
     # ---- helpers -------------------------------------------------------------------------------------------------------------------
     def _wait(self) -> None:
-        if self._in_flight:
-            ops.wait_spinning(torch.cuda.current_stream())
-            self._in_flight = False
+        self.flight.wait(torch.cuda.current_stream())
 
     def _check_errors(self) -> None:
         """ops.check_index_errors() as the eager forward calls it.  A reported id may still sit in a bucket's rows, and a request replayed
@@ -370,8 +284,7 @@ class GraphedForward:
         try:
             ops.check_index_errors()
         except IndexError as first:
-            ops.wait_spinning(torch.cuda.current_stream())
-            self._in_flight = False
+            self.flight.wait(torch.cuda.current_stream(), always=True)
             second = None
             try:
                 ops.check_index_errors()
@@ -424,8 +337,8 @@ class GraphedForward:
             key = ("bucket", bucket, stacked, X.size(1), X.dtype, idt, Ps, None if stacked else alias_pattern(lS_i))
             g = self._buckets.get(key)
             if g is None:
-                g = self._buckets[key] = _Graph(key, bucket, bucket)
                 dev = X.device
+                g = self._buckets[key] = _Graph(key, bucket, bucket, self.stream)
                 Xs = torch.zeros((bucket, X.size(1)), dtype=X.dtype, device=dev)
                 step = torch.arange(bucket, dtype=idt, device=dev)
                 if stacked:
@@ -452,8 +365,7 @@ class GraphedForward:
         key = ("exact", stacked, tuple(X.shape), X.dtype, idt, shape, iota)
         g = self._exact.get(key)
         if g is None:
-            g = _Graph(key, None, n)
-            from .graph import _clone_struct
+            g = _Graph(key, None, n, self.stream)
             g.static = (X.clone(), _clone_struct(lS_o), _clone_struct(lS_i))
             g.plan = StagePlan(g.static, (X, lS_o, lS_i))
             g.iota = iota
@@ -461,8 +373,7 @@ class GraphedForward:
             if dropped:
                 self._wait()
                 for d in dropped:
-                    if d.graph is not None:
-                        d.graph.reset()
+                    d.reset()
         return g
 
     @staticmethod
@@ -477,52 +388,19 @@ class GraphedForward:
         for t in ([static_o] if isinstance(static_o, torch.Tensor) else static_o):
             _iota.vouch_offsets(t, g.iota)
 
-    def _stage_now(self, g: _Graph, request) -> None:
-        """request -> static buffers on the current stream, outside a replay (the eager calls in front of the capture)"""
-        from . import _lib
-        g.plan.patch(request)
-        if g.plan.n:
-            rc = _lib.load().dlrm_stage_inputs(g.plan.n, g.plan.dst, g.plan.src, g.plan.nbytes,
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "dlrm_stage_inputs")
-
-    def _eager(self, g: _Graph, dev):
-        """the model's forward on the static buffers, on the stream the capture uses (its scratch workspaces are per stream)"""
-        cur = torch.cuda.current_stream(dev)
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=dev)
-        self.stream.wait_stream(cur)
+    def _forward(self, g: _Graph, dev, how):
+        """the model's forward on the static buffers through g.run (warm-up) or g.record (capture)"""
         self._vouch(g)
-        with self._single_stream(), torch.no_grad(), torch.cuda.stream(self.stream):
-            Z = self.model(*g.static)
-        cur.wait_stream(self.stream)
-        Z.record_stream(cur)
-        return Z
+        with self._single_stream(), torch.no_grad():
+            return how(dev, lambda: self.model(*g.static))
 
     def _capture(self, g: _Graph, dev) -> None:
-        if ops.timers is not None:
-            raise RuntimeError("dlrm_amd.graph: per-kernel event timers cannot be recorded inside a graph capture")
-        cur = torch.cuda.current_stream(dev)
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=dev)
-        self.stream.wait_stream(cur)
-        graph = torch.cuda.CUDAGraph()
-        self._vouch(g)
-        # ("relaxed": the forward polls events of finished offsets proofs and reads the pinned error block while the stream captures)
-        with self._single_stream(), torch.no_grad(), torch.cuda.graph(graph, stream=self.stream, capture_error_mode="relaxed"):
-            Z = self.model(*g.static)
+        Z = self._forward(g, dev, g.record)
         if Z.dim() != 2 or Z.size(0) != g.n or not Z.is_contiguous():
-            graph.reset()
+            g.reset()
             raise RuntimeError("dlrm_amd.graph: the captured forward returned %s, expected a contiguous [%d, k] tensor" % (tuple(Z.shape), g.n))
-        g.graph, g.out, g.views = graph, Z.detach(), {}
-        # the graph holds raw pointers into the cached scratch workspaces: pinned, as GraphedTrainStep pins them
-        g.pinned_ws = [w for (_, d_, _), w in ops._scratch_ws.items() if d_ == dev]
-        try:
-            g.exec = int(graph.raw_cuda_graph_exec())
-        except Exception:                                   # noqa: BLE001 - a torch without the raw handle: its own replay
-            g.exec = None
+        g.out, g.views = Z.detach(), {}
         self.captures += 1
-        cur.wait_stream(self.stream)
 
     # ---- the call ------------------------------------------------------------------------------------------------------------------
     def __call__(self, X, lS_o, lS_i):
@@ -535,6 +413,8 @@ class GraphedForward:
         dev = self._tensors[0].device if self._tensors else X.device
         if dev.type != "cuda":
             raise RuntimeError("dlrm_amd.graph: GraphedForward captures a HIP graph; move the model to the GPU first (model.to('cuda'))")
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=dev)     # ONE capture stream for every graph: the scratch workspaces are per stream
         X, lS_o, lS_i = self._normalise(X, lS_o, lS_i, dev)
         n = X.size(0)
         g = self._lookup(X, lS_o, lS_i)
@@ -543,28 +423,18 @@ class GraphedForward:
             self._wait()
             self._check_errors()            # (exact for everything this object enqueued: nothing of it is in flight any more)
             if g.eager_calls < self.warmup:
-                self._stage_now(g, request)
-                g.out = self._eager(g, dev)
+                stage(g.plan, request, torch.cuda.current_stream())
+                g.out = self._forward(g, dev, g.run)
+                g.out.record_stream(torch.cuda.current_stream(dev))
                 g.eager_calls += 1
                 self._keep = request
                 return g.out if g.bucket is None else g.out[:n]
             self._capture(g, dev)           # capture only records; the replay below executes this request
-        plan = g.plan
-        from . import _lib
-        if g.exec is not None:
-            plan.patch(request)
-            rc = _lib.load().dlrm_forward_replay(plan.n, plan.dst, plan.src, plan.nbytes, self.stage_memcpy_max, C.c_void_p(g.exec),
-                                                 int(self._in_flight), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "dlrm_forward_replay")
-            self.staged_launches += plan.launches(self.stage_memcpy_max)
-        else:
-            self._wait()
-            self._stage_now(g, request)
-            g.graph.replay()
-            self.staged_launches += plan.launches(0)
+        raw = g.exec is not None
+        replay(g, self.flight, torch.cuda.current_stream(), g.plan, request, memcpy_max=self.stage_memcpy_max)
+        self.staged_launches += g.plan.launches(self.stage_memcpy_max if raw else 0)
         self.replays += 1
         self._keep = request                # the sources stay alive until the next call (their copies are asynchronous)
-        self._in_flight = self.serialize
         if g.bucket is None:
             return g.out
         z = g.views.get(n)

@@ -1050,7 +1050,9 @@ int dlrm_graph_replay(int n, void* const* dst_host, const void* const* src_host,
  *   source is its destination, copies nothing; segments must not overlap otherwise.
  * dlrm_forward_replay: optionally wait for the stream (the previous replay; the polling wait of dlrm_graph_replay), stage the n_seg
  *   segments — one hipMemcpyAsync each when n_seg <= memcpy_max_segs (a stacked [T, B] request is three tensors), one
- *   dlrm_stage_inputs otherwise — then hipGraphLaunch(graph_exec). */
+ *   dlrm_stage_inputs otherwise — then hipGraphLaunch(graph_exec).
+ * Both replay calls are one implementation (csrc/replay.h): every segment is checked (DLRM_E_ARG for a null pointer or a negative length)
+ *   before the wait and before anything is enqueued; dlrm_graph_replay is the form with scalars that always copies per segment. */
 int dlrm_stage_inputs(int n_seg, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host, void* stream);
 int dlrm_forward_replay(int n_seg, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host,
                         int memcpy_max_segs, void* graph_exec, int sync_first, void* stream);

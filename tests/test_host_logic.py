@@ -259,27 +259,88 @@ def test_graph_input_helpers():
 
 
 def test_graph_input_pairs_for_the_raw_replay():
-    """The raw replay path (dlrm_graph_replay: wait + input copies + hipGraphLaunch in one C call) collects (static, caller) tensor pairs
-    through the same checks as the copy_ path: one pair per DISTINCT static tensor, none where the caller already passed the static
-    buffer, the shape / structure errors unchanged."""
-    from dlrm_amd.graph import _clone_struct, _copy_struct
+    """The raw replay path (dlrm_graph_replay: wait + input copies + hipGraphLaunch in one C call) takes its (static, caller) segments from
+    a StagePlan, behind the same checks as the copy_ path: one segment per DISTINCT static tensor, source == destination (which the C side
+    skips) where the caller already passed the static buffer, the shape / structure errors unchanged."""
+    from dlrm_amd.graph import StagePlan, _check_struct, _clone_struct
     off = torch.arange(5)
     st = _clone_struct([off, off, torch.arange(5) * 2])
-    pairs = []
-    put = lambda d, s_: pairs.append((d, s_))           # noqa: E731
     a, b = off + 1, off * 3
-    _copy_struct(st, [a, a, b], put)
-    assert len(pairs) == 2 and pairs[0][0] is st[0] and pairs[0][1] is a and pairs[1][0] is st[2] and pairs[1][1] is b
-    assert torch.equal(st[0], off)                      # nothing was copied: the pairs are for the C call
-    pairs.clear()
-    _copy_struct(st, [st[0], st[1], b], put)            # the caller handed the static buffers back: only the third tensor moves
-    assert len(pairs) == 1 and pairs[0][1] is b
+    plan = StagePlan((st,), ([a, a, b],))
+    plan.patch(([a, a, b],))
+    assert plan.n == 2 and [plan.dst[j] for j in range(2)] == [st[0].data_ptr(), st[2].data_ptr()]
+    assert [plan.src[j] for j in range(2)] == [a.data_ptr(), b.data_ptr()] and [plan.nbytes[j] for j in range(2)] == [40, 40]
+    assert torch.equal(st[0], off)                      # nothing was copied: the segments are for the C call
+    plan.patch(([st[0], st[1], b],))                    # the caller handed the static buffers back: only the third tensor moves
+    assert plan.src[0] == plan.dst[0] and plan.src[1] == b.data_ptr() != plan.dst[1]
     with pytest.raises(RuntimeError, match="shape"):
-        _copy_struct(st, [a, a, torch.arange(6)], put)
+        _check_struct(st, [a, a, torch.arange(6)])
+    with pytest.raises(RuntimeError, match="structure"):
+        _check_struct(st, [a, a])
     t = _clone_struct(torch.ones(2, 3))
-    pairs.clear()
-    _copy_struct(t, t, put)
-    assert pairs == []
+    plan = StagePlan((t,), (t,))
+    plan.patch((t,))
+    assert plan.n == 1 and plan.src[0] == plan.dst[0] and plan.nbytes[0] == 24
+
+
+def test_step_shaped_stage_plan_and_its_device_predicate():
+    """The plan GraphedTrainStep builds over (X, offsets, indices, T): one segment for each tensor, one for an offsets tensor the tables
+    share; takes() — the raw path's condition — is false for a tensor on another device and for a strided view.  (Once with
+    the static buffers on the meta device: a device that a host tensor is foreign to, without a GPU.)"""
+    from dlrm_amd.graph import StagePlan, _clone_struct
+    B, T = 6, 3
+
+    def request(dev):
+        off = torch.arange(B, device=dev)
+        return (torch.zeros(B, 13, device=dev), [off] * T, [torch.zeros(B, dtype=torch.int64, device=dev) for _ in range(T)],
+                torch.zeros(B, 1, device=dev))
+    for here, elsewhere in (("cpu", "meta"), ("meta", "cpu")):     # (real pointers; then static buffers a host tensor is foreign to)
+        X, lS_o, lS_i, Y = like = request(here)
+        static = (X.clone(), _clone_struct(lS_o), _clone_struct(lS_i), Y.clone())
+        plan = StagePlan(static, like)
+        assert plan.n == 1 + 1 + T + 1 and plan.flat
+        assert plan.entries == [(0, None, None), (1, 0, None)] + [(2, k, None) for k in range(T)] + [(3, None, None)]
+        assert plan.cap == [B * 13 * 4, B * 8] + [B * 8] * T + [B * 4]
+        want = [static[0], static[1][0]] + static[2] + [static[3]]
+        assert [plan.dst[j] or 0 for j in range(plan.n)] == [t.data_ptr() for t in want]
+        assert here == "meta" or len(set(plan.dst[j] for j in range(plan.n))) == plan.n
+        assert plan.takes(like) and plan.takes(request(here))
+        far = request(elsewhere)
+        assert not plan.takes(far) and not plan.takes((X, lS_o, lS_i, far[3])) and not plan.takes((X, lS_o, lS_i[:2] + far[2][2:], Y))
+        wide = torch.zeros(B, 26, device=here)
+        assert not plan.takes((wide[:, ::2], lS_o, lS_i, Y)) and not plan.takes((wide[:, :13], lS_o, lS_i, Y))
+    # on the host's own device, with real pointers: a static tensor that kept the strides of a permuted first input is no run of bytes
+    Xt = torch.zeros(13, B).t()
+    Y = torch.zeros(B, 1)
+    permuted = StagePlan((Xt.clone(), Y.clone()), (Xt, Y))
+    assert not permuted.flat and not permuted.takes((torch.zeros(B, 13), Y))
+
+
+@pytest.mark.parametrize("export", ["dlrm_graph_replay", "dlrm_forward_replay@0", "dlrm_forward_replay@1000000"])
+def test_replay_exports_refuse_bad_arguments_before_any_device_call(export):
+    """Both replay calls are one implementation (csrc/replay.h): DLRM_E_ARG for n < 0, a null graph handle, null arrays with n > 0, and —
+    with sync_first = 0 — for a segment without a destination, all before the first HIP call (this test has no GPU to call).  The
+    forward's call on both sides of its memcpy threshold."""
+    import ctypes as C
+    from dlrm_amd import _lib
+    lib, E_ARG = _lib.load(), -1
+    name, _, threshold = export.partition("@")
+    keep = torch.zeros(4)
+    fake_exec, stream = C.c_void_p(keep.data_ptr()), C.c_void_p(0)       # (never dereferenced: every call returns before using it)
+
+    def call(n, dst, src, nb, graph_exec):
+        if name == "dlrm_graph_replay":
+            return lib.dlrm_graph_replay(n, dst, src, nb, 0, None, None, graph_exec, 0, stream)
+        return lib.dlrm_forward_replay(n, dst, src, nb, int(threshold), graph_exec, 0, stream)
+    one = lambda v: (C.c_void_p * 1)(v)                 # noqa: E731
+    dst, src, nb = one(keep.data_ptr()), one(keep.data_ptr()), (C.c_int64 * 1)(16)
+    assert call(-1, dst, src, nb, fake_exec) == E_ARG
+    assert call(1, dst, src, nb, None) == E_ARG and call(0, None, None, None, None) == E_ARG
+    for arrays in ((None, src, nb), (dst, None, nb), (dst, src, None)):
+        assert call(1, *arrays, fake_exec) == E_ARG
+    assert call(1, one(None), src, nb, fake_exec) == E_ARG
+    assert call(1, dst, one(None), nb, fake_exec) == E_ARG
+    assert call(1, dst, src, (C.c_int64 * 1)(-4), fake_exec) == E_ARG
 
 
 def test_small_batch_tower_path_is_chosen_by_rows_widths_and_weight_traffic(monkeypatch):

@@ -182,6 +182,28 @@ def test_a_discarded_step_object_leaves_no_hook_behind_that_keeps_it_alive():
     opt.state_dict()                             # its hooks left with it
 
 
+def test_a_param_group_added_after_the_capture_means_recapture_and_no_pointer_array():
+    """The device learning rates are one scalar per param group OF THE CAPTURE.  The state a capture leaves behind, set by hand: a changed
+    lr hands out the pointers and values of the replay's write; once a group is appended, the owner reports "re-capture" and hands out
+    nothing — a write of len(param_groups) scalars would run past the captured buffer."""
+    from dlrm_amd.graph import GraphedTrainStep
+    from dlrm_amd.optim import FusedSGD
+    model = tiny_model()
+    opt = FusedSGD(model.parameters(), lr=0.1)
+    step = GraphedTrainStep(model, opt)
+    lrs = step.lrs
+    assert step._lr_on_device is True and not lrs.valid()                # nothing captured yet
+    lrs.dev, lrs.values = torch.zeros(len(opt.param_groups)), lrs.current()
+    assert lrs.valid() and lrs.changed() is None and step.lr_writes == 0
+    opt.param_groups[0]["lr"] = 0.25
+    n, dst, values = lrs.changed()
+    assert (n, dst[0], values[0]) == (1, lrs.dev.data_ptr(), 0.25) and step.lr_writes == 1 and lrs.valid()
+    opt.add_param_group({"params": [torch.nn.Parameter(torch.zeros(3))]})
+    assert not lrs.valid() and lrs.changed() is None
+    opt.param_groups[0]["lr"] = 0.5                                      # ... whatever else changed meanwhile
+    assert not lrs.valid() and lrs.changed() is None and step.lr_writes == 1 and lrs.values == [0.25]
+
+
 def test_seed_argument_of_the_bf16_updates_is_an_int_or_a_one_element_int64_gpu_tensor():
     from dlrm_amd import ops
     assert ops._seed_args(2 ** 64 + 5) == (False, 5) and ops._seed_args(-1) == (False, 2 ** 64 - 1)
