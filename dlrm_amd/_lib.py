@@ -173,6 +173,9 @@ SIGNATURES = {
     "dlrm_graph_replay": (_i32, [_i32, _pp, _pp, _pi64, _i32, _pp, C.POINTER(_f32), _vp, _i32, _vp]),
     "dlrm_stage_inputs": (_i32, [_i32, _pp, _pp, _pi64, _vp]),
     "dlrm_forward_replay": (_i32, [_i32, _pp, _pp, _pi64, _i32, _vp, _i32, _vp]),
+    "dlrm_stage_ragged": (_i32, [_vp, _vp, _i64, _i32, _pp, _pp, _pi64, _pi64, _i32, _pp, _pp, _pi64, _pi64, _i64, _i64, _i32, _vp]),
+    "dlrm_forward_replay_ragged": (_i32, [_vp, _vp, _i64, _i32, _pp, _pp, _pi64, _pi64, _i32, _pp, _pp, _pi64, _pi64, _i64, _i64, _i32,
+                                          _vp, _i32, _vp]),
     "dlrm_tower_fwd": (_i32, [_i64, _i32, C.POINTER(_i32), C.POINTER(_i32), _vp, _i64, _pp, _pi64, _pp, _pp, _pi64, _vp]),
     "dlrm_tower_bwd": (_i32, [_i64, _i32, C.POINTER(_i32), C.POINTER(_i32), _vp, _i64, _i32, _pp, _pi64, _pp, _pi64, _pp, _pi64, _vp, _i64, _vp]),
     "dlrm_tower_wgrad_workspace_bytes": (_i64, [_i64, _i32, C.POINTER(_i32)]),

@@ -19,16 +19,18 @@ from . import ext_dist, ops
 
 @torch.no_grad()
 def inference(model, test_batches: Iterable, device: Optional[torch.device] = None, nbatches: int = -1,
-              graphed: bool = False) -> Dict[str, float]:
+              graphed: bool = False, batch_sizes=None, lookup_capacity=None) -> Dict[str, float]:
     """`test_batches` yields (X, lS_o, lS_i, T) like the reference's unpack_batch (:733-757).  Returns the
     validation_results dictionary of the reference plus `round_accuracy` (its non-mlperf accuracy) and raw counts.
     graphed=True: the batches run through one dlrm_amd.graph.GraphedForward (an exact-shape graph per batch shape: the short last batch
-    captures a second one; single process only) — its predictions are a static buffer, so each batch's are cloned before the next call."""
+    captures a second one; single process only) — its predictions are a static buffer, so each batch's are cloned before the next call.
+    batch_sizes / lookup_capacity go to GraphedForward as they are: buckets over rows, and ragged buckets for multi-hot batches whose bags
+    have their own lengths (otherwise every such batch is a shape of its own and captures its own graph)."""
     scores, targets = [], []
     forward = model
     if graphed:
         from .graph import GraphedForward
-        fwd = GraphedForward(model)
+        fwd = GraphedForward(model, batch_sizes=batch_sizes, lookup_capacity=lookup_capacity)
 
         def forward(X_, lS_o_, lS_i_):
             return fwd(X_, lS_o_, lS_i_).clone()

@@ -1,6 +1,7 @@
 """Capture and replay of a HIP graph, the one protocol of graph.GraphedTrainStep and graph_forward.GraphedForward: static inputs
-(_clone_struct, _check_struct, the torch copies of _copy_struct, the C arrays of StagePlan), Capture (warm up on a private stream, capture
-relaxed, pin the scratch workspaces, take the raw hipGraphExec_t), InFlight (one replay in flight) and replay (one C call: csrc/replay.h)."""
+(_clone_struct, _check_struct, the torch copies of _copy_struct, the C arrays of StagePlan and of RaggedPlan), Capture (warm up on a
+private stream, capture relaxed, pin the scratch workspaces, take the raw hipGraphExec_t), InFlight (one replay in flight) and replay (one
+C call: csrc/replay.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -143,10 +144,135 @@ class StagePlan:
         return 0 if self.n <= memcpy_max else (self.n + STAGE_SEGS_PER_LAUNCH - 1) // STAGE_SEGS_PER_LAUNCH
 
 
-def stage(plan: StagePlan, request: Sequence, stream) -> None:
-    """request -> static buffers on `stream`, outside a replay call: dlrm_stage_inputs, one launch per 64 copying segments"""
+class RaggedPlan:
+    """The staging of one RAGGED bucket (graph_forward.py), as the ctypes arguments of dlrm_stage_ragged / dlrm_forward_replay_ragged.
+    statics = (X [bucket, m], offsets, ids): lists of 1-D tensors (ids k of `caps[k]` elements, offsets of `bucket`; one tensor object
+    at several positions is ONE buffer) or stacked [T, Lcap] / [T, bucket] tensors, staged by rows.  Destinations and capacities are
+    fixed here; patch() writes the sources, n and nnz_k of a request and keeps shift_k = cap_k - nnz_k (the C side derives the same from
+    nnz and cap: ids go to ids_static[shift_k:], offsets become shift_k + clamp(off, 0, nnz_k), tail bags start at cap_k).  An offsets
+    buffer shared by several tables needs one capacity (refused here otherwise) and one nnz (refused by patch)."""
+
+    def __init__(self, statics: Sequence, caps: Sequence[int], bucket: int):
+        Xs, Os, Is = statics
+        self.bucket, self.caps = int(bucket), tuple(int(c) for c in caps)
+        self.stacked = isinstance(Is, torch.Tensor)
+        T = Is.size(0) if self.stacked else len(Is)
+        if isinstance(Os, torch.Tensor) != self.stacked or (Os.size(0) if self.stacked else len(Os)) != T or len(self.caps) != T:
+            raise RuntimeError("dlrm_amd.graph: a ragged bucket needs offsets and indices of one structure and one capacity per table")
+        if Xs.dim() != 2 or Xs.size(0) != self.bucket or not Xs.is_contiguous() or min(self.caps, default=1) < 1:
+            raise RuntimeError("dlrm_amd.graph: a ragged bucket needs a contiguous [bucket, m] dense buffer and capacities >= 1")
+        self.T, self.idt = T, Is.dtype if self.stacked else Is[0].dtype
+        self.elem = 8 if self.idt == torch.int64 else 4
+        self.x_dst, self.x_row = Xs.data_ptr(), Xs.size(1) * Xs.element_size()
+        self.x_shape, self.x_dtype = Xs.size(1), Xs.dtype
+        # (table whose nnz the segment takes, destination, capacity); off_tabs: every table that shares the offsets buffer
+        self.ids_tab, self.off_tab, self.off_tabs = [], [], []
+        ids_dst, ids_cap, off_dst, off_cap = [], [], [], []
+        if self.stacked:
+            if tuple(Is.shape) != (T, self.caps[0]) or tuple(Os.shape) != (T, self.bucket) or len(set(self.caps)) != 1 or Os.dtype != self.idt \
+                    or not (Is.is_contiguous() and Os.is_contiguous()):
+                raise RuntimeError("dlrm_amd.graph: stacked ragged buffers are [T, Lcap] and [T, bucket] with one capacity for all tables")
+            for k in range(T):
+                self.ids_tab.append(k)
+                ids_dst.append(Is.data_ptr() + k * self.caps[0] * self.elem)
+                ids_cap.append(self.caps[0])
+                self.off_tab.append(k)
+                self.off_tabs.append((k,))
+                off_dst.append(Os.data_ptr() + k * self.bucket * self.elem)
+                off_cap.append(self.caps[0])
+        else:
+            seen: dict = {}
+            for k, t in enumerate(Is):
+                if t.dtype != self.idt or t.numel() != self.caps[k] or not t.is_contiguous():
+                    raise RuntimeError("dlrm_amd.graph: the static ids of table %d are not %d contiguous elements of one dtype" % (k, self.caps[k]))
+                if id(t) not in seen:
+                    seen[id(t)] = k
+                    self.ids_tab.append(k)
+                    ids_dst.append(t.data_ptr())
+                    ids_cap.append(self.caps[k])
+            seen = {}
+            for k, t in enumerate(Os):
+                if t.dtype != self.idt or t.numel() != self.bucket or not t.is_contiguous():
+                    raise RuntimeError("dlrm_amd.graph: the static offsets of table %d are not %d contiguous elements of the ids' dtype" % (k, self.bucket))
+                j = seen.setdefault(id(t), len(self.off_tab))
+                if j == len(self.off_tab):
+                    self.off_tab.append(k)
+                    self.off_tabs.append(())
+                    off_dst.append(t.data_ptr())
+                    off_cap.append(self.caps[k])
+                elif self.caps[k] != off_cap[j]:
+                    raise RuntimeError("dlrm_amd.graph: tables that share one offsets tensor need one lookup capacity")
+                self.off_tabs[j] += (k,)
+        self.n_ids, self.n_off = len(ids_dst), len(off_dst)
+        self.ids_dst = (C.c_void_p * self.n_ids)(*ids_dst)
+        self.ids_src = (C.c_void_p * self.n_ids)()
+        self.ids_nnz = (C.c_int64 * self.n_ids)()
+        self.ids_cap = (C.c_int64 * self.n_ids)(*ids_cap)
+        self.off_dst = (C.c_void_p * self.n_off)(*off_dst)
+        self.off_src = (C.c_void_p * self.n_off)()
+        self.off_nnz = (C.c_int64 * self.n_off)()
+        self.off_cap = (C.c_int64 * self.n_off)(*off_cap)
+        self.x_src, self.x_bytes, self.rows = 0, 0, 0
+        self.nnz = [0] * T              # of the request patched last, per table
+        self.shift = list(self.caps)
+        self._segs = self.n_off
+
+    def patch(self, request: Sequence) -> None:
+        X, lS_o, lS_i = request
+        n = X.size(0)
+        if X.dim() != 2 or X.size(1) != self.x_shape or X.dtype != self.x_dtype or n > self.bucket or not X.is_contiguous():
+            raise RuntimeError("dlrm_amd.graph: the dense input does not fit the ragged bucket (rows, width, dtype, or not contiguous)")
+        if isinstance(lS_i, torch.Tensor) != self.stacked or isinstance(lS_o, torch.Tensor) != self.stacked:
+            raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
+        T, caps, elem = self.T, self.caps, self.elem
+        if self.stacked:
+            if lS_i.dim() != 2 or lS_o.dim() != 2 or lS_i.size(0) != T or lS_o.size(0) != T or lS_i.dtype != self.idt or lS_o.dtype != self.idt:
+                raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
+            w = lS_i.size(1)
+            if w > caps[0] or lS_o.size(1) != n or not (lS_i.is_contiguous() and lS_o.is_contiguous()):
+                raise RuntimeError("dlrm_amd.graph: a ragged request does not fit its bucket (lookups above the capacity, not n offsets, "
+                                   "or not contiguous)")
+            nnz = [w] * T
+            ip, op = lS_i.data_ptr(), lS_o.data_ptr()
+            for k in range(T):
+                self.ids_src[k], self.ids_nnz[k] = (ip + k * w * elem) if w else None, w
+                self.off_src[k], self.off_nnz[k] = (op + k * n * elem) if n else None, w
+        else:
+            if len(lS_i) != T or len(lS_o) != T:
+                raise RuntimeError("dlrm_amd.graph: input structure differs from the captured forward")
+            nnz = [t.numel() for t in lS_i]
+            for k in range(T):
+                if nnz[k] > caps[k] or lS_o[k].numel() != n or lS_i[k].dtype != self.idt or lS_o[k].dtype != self.idt \
+                        or not (lS_i[k].is_contiguous() and lS_o[k].is_contiguous()):
+                    raise RuntimeError("dlrm_amd.graph: a ragged request does not fit its bucket (lookups above the capacity, not n offsets, "
+                                       "another index dtype, or not contiguous)")
+            for j, k in enumerate(self.ids_tab):
+                self.ids_src[j], self.ids_nnz[j] = (lS_i[k].data_ptr() if nnz[k] else None), nnz[k]
+            for j, k in enumerate(self.off_tab):
+                if any(nnz[q] != nnz[k] for q in self.off_tabs[j]):
+                    raise RuntimeError("dlrm_amd.graph: tables that share one offsets tensor need the same number of lookups")
+                self.off_src[j], self.off_nnz[j] = (lS_o[k].data_ptr() if n else None), nnz[k]
+        self.x_src, self.x_bytes, self.rows = (X.data_ptr() if n else 0), n * self.x_row, n
+        self.nnz = nnz
+        self.shift = [c - z for c, z in zip(caps, nnz)]
+        self._segs = (1 if n else 0) + sum(1 for j in range(self.n_ids) if self.ids_nnz[j]) + self.n_off
+
+    def launches(self, memcpy_max: int = 0) -> int:
+        """stage_ragged_kernel launches of the request patched last (there is no memcpy path: the offsets are computed)"""
+        return (self._segs + STAGE_SEGS_PER_LAUNCH - 1) // STAGE_SEGS_PER_LAUNCH
+
+    def args(self) -> tuple:
+        return (C.c_void_p(self.x_dst), C.c_void_p(self.x_src), self.x_bytes, self.n_ids, self.ids_dst, self.ids_src, self.ids_nnz,
+                self.ids_cap, self.n_off, self.off_dst, self.off_src, self.off_nnz, self.off_cap, self.rows, self.bucket, self.elem)
+
+
+def stage(plan, request: Sequence, stream) -> None:
+    """request -> static buffers on `stream`, outside a replay call: dlrm_stage_inputs, one launch per 64 copying segments
+    (a RaggedPlan: dlrm_stage_ragged)"""
     plan.patch(request)
-    if plan.n:
+    if isinstance(plan, RaggedPlan):
+        _lib.check(_lib.load().dlrm_stage_ragged(*plan.args(), C.c_void_p(stream.cuda_stream)), "dlrm_stage_ragged")
+    elif plan.n:
         _lib.check(_lib.load().dlrm_stage_inputs(plan.n, plan.dst, plan.src, plan.nbytes, C.c_void_p(stream.cuda_stream)), "dlrm_stage_inputs")
 
 
@@ -227,14 +353,17 @@ def replay(cap: Capture, flight: InFlight, stream, plan: StagePlan, request: Seq
            scalars=None, staged: bool = False) -> None:
     """One replay of `cap` on `stream`.  With the raw handle: the plan patched and ONE C call — wait for the replay in flight, stage, write
     `scalars` ((count <= 16, device pointers, values) or None), hipGraphLaunch: dlrm_graph_replay for memcpy_max == MEMCPY_ALWAYS (a
-    step), else dlrm_forward_replay (no scalars).  Without it the torch calls: wait, dlrm_stage_inputs, dlrm_set_f32, CUDAGraph.replay().
+    step), else dlrm_forward_replay (no scalars), dlrm_forward_replay_ragged for a RaggedPlan.  Without it the torch calls: wait, dlrm_stage_inputs, dlrm_set_f32, CUDAGraph.replay().
     staged: the caller has waited and staged already, with torch copies (_copy_struct) — the torch calls without the first two."""
     n, sdst, sval = scalars or (0, None, None)
     lib = _lib.load()
     where = C.c_void_p(stream.cuda_stream)
     if cap.exec is not None and not staged:
         plan.patch(request)
-        if memcpy_max >= MEMCPY_ALWAYS:
+        if isinstance(plan, RaggedPlan):        # (a ragged bucket of GraphedForward: the same protocol, its own staging)
+            rc = lib.dlrm_forward_replay_ragged(*plan.args(), C.c_void_p(cap.exec), int(flight.pending), where)
+            _lib.check(rc, "dlrm_forward_replay_ragged")
+        elif memcpy_max >= MEMCPY_ALWAYS:
             rc = lib.dlrm_graph_replay(plan.n, plan.dst, plan.src, plan.nbytes, n, sdst, sval, C.c_void_p(cap.exec), int(flight.pending), where)
             _lib.check(rc, "dlrm_graph_replay")
         else:

@@ -16,7 +16,25 @@ buffers (the static offsets are P_k * arange(bucket) and never change), Z[:n] co
 the zeros of the capture: every sample's forward is independent, so rows < n do not depend on them — with one exception, the int8 towers,
 whose activation range is taken over the whole batch tensor; such a model is refused with buckets.  The answer of a bucket is the eager
 forward on the padded batch, bit for bit (the library picks GEMM variants by M: the eager forward at n may sum in another order).  A ragged
-request, or n above the largest bucket, takes an exact-shape graph.
+request, or n above the largest bucket, takes an exact-shape graph — unless ragged buckets are asked for:
+
+Ragged buckets (`lookup_capacity=c`, an int or one per table; opt-in, needs `batch_sizes`).  A multi-hot request whose bags have their own
+lengths — the reference's default data — is a new shape tuple almost every time, and exact-shape graphs then capture per request.  A ragged
+bucket holds, per table, static ids of Lcap_k = bucket * c_k lookups and `bucket` static offsets, and is captured ONCE with nnz = Lcap_k.
+Every lookup kernel takes nnz by value (bag b is [off[b], off[b+1]), the last one ends at nnz), so padding the ids on the right would hand
+the padding to the last bag; a request of nnz_k <= Lcap_k ids is RIGHT-ALIGNED instead, shift_k = Lcap_k - nnz_k:
+    ids_static[shift_k:] = ids_req;   off_static[b] = shift_k + clamp(off_req[b], 0, nnz_k) for b < n,   Lcap_k for n <= b < bucket
+(one dlrm_stage_ragged launch inside the replay call: csrc/stage.hip, graph_core.RaggedPlan).  Real bags keep their ids in order, the last
+real bag ends at off_static[n] = Lcap_k (or at the baked nnz when n == bucket), tail bags are empty and pool to zero, and what lies in front
+of off_static[0] — zeros, or an earlier request's valid ids — is never pooled: every forward lookup (dlrm_emb_fwd, _bf16, _quant, _qr, _md)
+reads ids one element at a time inside [off[b], off[b+1]) only, so any 4-byte alignment of the shifted ids is fine.  dlrm_pool_weights_gather
+(weighted pooling) does walk all Lcap_k ids: harmless, stale ids are valid ids and their weights are read by no bag.  A lane sums a bag's
+rows in index order wherever the bag sits, so rows < n are the bits of the eager forward on the padded batch (X padded with zero rows,
+offsets cat(off_req, full(bucket - n, nnz_k)), the request's ids).  The clamp changes nothing for well-formed offsets; for any others it keeps
+the captured kernels inside the static ids.  Routing: a fixed-length bucket where fixed_bag_lengths succeeds, else a ragged bucket when every
+table has n offsets and nnz_k <= Lcap_k (tables that share a tensor object: one nnz, one capacity; stacked inputs: one capacity), else an
+exact-shape graph.  The key holds no nnz.  The train step (graph.GraphedTrainStep) has no such form: its backward and sorted updates walk
+all nnz lookups and would see the stale head.  Rates: profiles/graph_forward/ragged_rates.md.
 
 Fused lookup + interaction.  Inside a capture nothing can ask the device whether offsets == arange(B); the proof is made per request on
 the caller's tensors (ops.offsets_are_iota: cached per tensor object, free for producer-tagged tensors), only for models that have a fused
@@ -42,8 +60,8 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import ext_dist, ops
-from .graph_core import (STAGE_MEMCPY_MAX, STAGE_SEGS_PER_LAUNCH, Capture, InFlight, StagePlan, _clone_struct,  # noqa: F401  (the constants
-                         replay, stage)                                                  # and StagePlan stay importable from here)
+from .graph_core import (STAGE_MEMCPY_MAX, STAGE_SEGS_PER_LAUNCH, Capture, InFlight, RaggedPlan, StagePlan,  # noqa: F401  (the constants
+                         _clone_struct, replay, stage)                                   # and the plans stay importable from here)
 
 
 # ------------------------------------------------------------------------------------------------ host logic (no device needed)
@@ -123,6 +141,51 @@ def alias_pattern(ts) -> Optional[tuple]:
     return tuple(out) if shared else None
 
 
+def lookup_capacities(lookup_capacity, T: Optional[int] = None) -> Optional[Tuple[int, ...]]:
+    """the constructor's `lookup_capacity` as (c_0, ..., c_{T-1}): an int holds for every table (a 1-tuple until T is known), a sequence
+    names each table's; ValueError for anything that is not an int >= 1, or a sequence of another length than T"""
+    if lookup_capacity is None:
+        return None
+    seq = isinstance(lookup_capacity, (list, tuple))
+    cs = tuple(lookup_capacity) if seq else (lookup_capacity,)
+    if not cs or any(isinstance(c, bool) or not isinstance(c, int) or c < 1 for c in cs):
+        raise ValueError("dlrm_amd.graph: lookup_capacity is an int >= 1 or a sequence of one int >= 1 per table")
+    if T is None:
+        return cs
+    if not seq:
+        return cs * T
+    if len(cs) != T:
+        raise ValueError("dlrm_amd.graph: lookup_capacity names %d tables, the request has %d" % (len(cs), T))
+    return cs
+
+
+def ragged_fits(lS_o, lS_i, n: int, lcaps: Sequence[int]) -> bool:
+    """does a request of n rows go into a ragged bucket whose table k holds lcaps[k] lookups?  Every table has n offsets and at most
+    lcaps[k] ids, offsets and ids share one int32 / int64 dtype; stacked inputs need ONE capacity; tables that share a tensor object
+    (one offsets tensor for all tables) need the same nnz and the same capacity — the shared static buffer has one shift."""
+    stacked = _is_stacked(lS_o, lS_i)
+    if n < 1:
+        return False
+    if stacked:
+        return (lS_o.size(0) == len(lcaps) and len(set(lcaps)) == 1 and lS_o.size(1) == n and lS_i.size(1) <= lcaps[0]
+                and lS_i.dtype == lS_o.dtype and lS_i.dtype in (torch.int32, torch.int64))
+    T = len(lS_i)
+    if T != len(lcaps) or T == 0:
+        return False
+    idt = lS_i[0].dtype
+    if idt not in (torch.int32, torch.int64):
+        return False
+    for k in range(T):
+        o, i = lS_o[k], lS_i[k]
+        if o.dim() != 1 or i.dim() != 1 or o.numel() != n or i.numel() > lcaps[k] or o.dtype != idt or i.dtype != idt:
+            return False
+    for pattern in (alias_pattern(lS_o), alias_pattern(lS_i)):
+        for k, j in enumerate(pattern or ()):
+            if j != k and (lS_i[j].numel() != lS_i[k].numel() or lcaps[j] != lcaps[k]):
+                return False
+    return True
+
+
 class LRU:
     """key -> value, at most `cap` entries; put() returns the values that fell out (least recently used first)"""
 
@@ -199,20 +262,27 @@ class _Graph(Capture):
 
 # ------------------------------------------------------------------------------------------------ the class
 class GraphedForward:
-    """fwd = GraphedForward(model, batch_sizes=None, warmup=2);  Z = fwd(X, lS_o, lS_i)   ([n, 1] view of a static buffer)
+    """fwd = GraphedForward(model, batch_sizes=None, warmup=2, lookup_capacity=None);  Z = fwd(X, lS_o, lS_i)   ([n, 1] view of a static
+    buffer).  lookup_capacity (an int, or one int per table; needs batch_sizes): ragged multi-hot requests run in ragged buckets of
+    bucket * c_k lookups for table k (module docstring); None: they take exact-shape graphs.
 
     The first `warmup` calls of a graph are eager forwards on its static buffers (kernel attributes, workspaces and allocator pools
     settle; a bucket answers with the padded batch's bits from its first call on); the next call captures, every later one stages and
-    replays.  Counters: captures, replays, staged_launches (dlrm_stage_inputs kernel launches of the replays; the memcpy path adds
-    none), buckets_in_use."""
+    replays.  Counters: captures, replays, staged_launches (dlrm_stage_inputs / dlrm_stage_ragged kernel launches of the replays; the
+    memcpy path adds none), buckets_in_use (bucket sizes with a captured graph, of either kind), ragged_buckets_in_use."""
 
-    def __init__(self, model, batch_sizes: Optional[Sequence[int]] = None, warmup: int = 2, max_exact_shapes: int = 8):
+    def __init__(self, model, batch_sizes: Optional[Sequence[int]] = None, warmup: int = 2, max_exact_shapes: int = 8,
+                 lookup_capacity=None):
         if ext_dist.is_distributed():
             raise RuntimeError("dlrm_amd.graph: the whole-forward HIP graph is single-process only "
                                "(the RCCL all-to-all of the distributed forward is not captured)")
         self.batch_sizes = tuple(sorted({int(b) for b in batch_sizes})) if batch_sizes else None
         if self.batch_sizes and self.batch_sizes[0] < 1:
             raise ValueError("dlrm_amd.graph: batch_sizes must be positive")
+        self.lookup_capacity = lookup_capacities(lookup_capacity)
+        if self.lookup_capacity is not None and not self.batch_sizes:
+            raise ValueError("dlrm_amd.graph: lookup_capacity sizes the ragged buckets; it needs batch_sizes")
+        self._lookup_capacity_arg = lookup_capacity
         self.model = model
         self._refuse_int8_buckets()
         self.warmup = max(int(warmup), 1)
@@ -238,6 +308,10 @@ class GraphedForward:
     @property
     def buckets_in_use(self) -> int:
         return len({g.bucket for g in self._buckets.values() if g.graph is not None})
+
+    @property
+    def ragged_buckets_in_use(self) -> int:
+        return len({g.bucket for g in self._buckets.values() if g.graph is not None and g.key[0] == "ragged"})
 
     @property
     def exact_shapes(self) -> int:
@@ -353,6 +427,10 @@ class GraphedForward:
                 g.plan = StagePlan((Xs, None, Is), (X, lS_o, lS_i), by_rows=(2,) if stacked else ())
                 g.iota = all(p == 1 for p in Ps)
             return g
+        if bucket is not None and self.lookup_capacity is not None:
+            g = self._ragged(X, lS_o, lS_i, stacked, n, bucket, idt)
+            if g is not None:
+                return g
         # exact shape.  The offsets' verdict is part of the key where the model could take a fused route with these shapes
         if stacked:
             shape = (tuple(lS_o.shape), tuple(lS_i.shape))
@@ -374,6 +452,36 @@ class GraphedForward:
                 self._wait()
                 for d in dropped:
                     d.reset()
+        return g
+
+    def _ragged(self, X, lS_o, lS_i, stacked, n, bucket, idt):
+        """-> the ragged bucket of this request, or None: it does not fit one (an exact-shape graph).  The static ids of table k hold
+        Lcap_k = bucket * c_k lookups, the request's at their END; the static offsets are rewritten by every request (RaggedPlan)."""
+        T = lS_o.size(0) if stacked else len(lS_o)
+        caps = lookup_capacities(self._lookup_capacity_arg, T)
+        lcaps = tuple(bucket * c for c in caps)
+        if X.dim() != 2 or not ragged_fits(lS_o, lS_i, n, lcaps):
+            return None
+        key = ("ragged", bucket, stacked, X.size(1), X.dtype, idt, caps, None if stacked else (alias_pattern(lS_o), alias_pattern(lS_i)))
+        g = self._buckets.get(key)
+        if g is None:
+            dev = X.device
+            g = self._buckets[key] = _Graph(key, bucket, bucket, self.stream)
+            Xs = torch.zeros((bucket, X.size(1)), dtype=X.dtype, device=dev)
+            if stacked:
+                Os = torch.full((T, bucket), lcaps[0], dtype=idt, device=dev)
+                Is = torch.zeros((T, lcaps[0]), dtype=idt, device=dev)
+            else:
+                mo, mi = {}, {}         # (one tensor object at several positions: one static buffer)
+                Os = [mo[id(t)] if id(t) in mo else mo.setdefault(id(t), torch.full((bucket,), L, dtype=idt, device=dev))
+                      for t, L in zip(lS_o, lcaps)]
+                Is = [mi[id(t)] if id(t) in mi else mi.setdefault(id(t), torch.zeros(L, dtype=idt, device=dev)) for t, L in zip(lS_i, lcaps)]
+            g.static = (Xs, Os, Is)
+            g.plan = RaggedPlan(g.static, lcaps, bucket)
+            # Lcap_k == bucket for every table is the shape the fused lookup + interaction kernels take, and a captured forward must not
+            # ask the device about offsets: stated "not arange" (a request that IS arange went to its fixed-length bucket above), so the
+            # capture holds the two-kernel form.  Any other capacity never reaches that question (nnz != B).
+            g.iota = False if (self._route and all(L == bucket for L in lcaps)) else None
         return g
 
     @staticmethod

@@ -1058,6 +1058,30 @@ int dlrm_forward_replay(int n_seg, void* const* dst_host, const void* const* src
                         int memcpy_max_segs, void* graph_exec, int sync_first, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A RAGGED multi-hot request into a ragged bucket of GraphedForward (csrc/stage.hip: stage_ragged_kernel; symbols added, the ABI version
+ * stays 17).  The bucket's lookups were captured with nnz = cap, so a request's ids go to the END of their static buffer:
+ *   X        x_dst[0 .. x_bytes) = x_src[...]                                          (x_bytes == 0: nothing)
+ *   ids i    shift = ids_cap[i] - ids_nnz[i];  (ids_dst[i] + shift * idx_bytes)[0 .. ids_nnz[i] * idx_bytes) = ids_src[i][...]
+ *            (ids_dst[i] is the START of the static buffer of ids_cap[i] elements; ids_nnz[i] == 0 copies nothing, its source may be null)
+ *   offsets j  shift = off_cap[j] - off_nnz[j];  for b < bucket:
+ *            off_dst[j][b] = b < n ? shift + min(max(off_src[j][b], 0), off_nnz[j]) : off_cap[j]
+ *            (all `bucket` elements, on every call; off_src[j] has n elements and may be null only when n == 0)
+ * idx_bytes is 4 (int32) or 8 (int64) for ids and offsets alike.  One launch per 64 segments (1 + n_ids + n_off of them, fewer where
+ * nothing is copied), descriptors by value in the kernarg, nothing read from host memory after the call returns.  Checked before anything
+ * is enqueued: DLRM_E_ARG for idx_bytes, n < 0, n > bucket, bucket < 1, a negative count, nnz < 0, nnz > cap, a cap that an offset of
+ * idx_bytes cannot hold, a null pointer where something is read or written; DLRM_E_ALIGN for a pointer or x_bytes that is no multiple of 4.
+ * dlrm_forward_replay_ragged: the protocol of dlrm_forward_replay (check, optional polling wait, stage, hipGraphLaunch) with this staging. */
+int dlrm_stage_ragged(void* x_dst, const void* x_src, int64_t x_bytes, int n_ids, void* const* ids_dst_host,
+                      const void* const* ids_src_host, const int64_t* ids_nnz_host, const int64_t* ids_cap_host, int n_off,
+                      void* const* off_dst_host, const void* const* off_src_host, const int64_t* off_nnz_host,
+                      const int64_t* off_cap_host, int64_t n, int64_t bucket, int idx_bytes, void* stream);
+int dlrm_forward_replay_ragged(void* x_dst, const void* x_src, int64_t x_bytes, int n_ids, void* const* ids_dst_host,
+                               const void* const* ids_src_host, const int64_t* ids_nnz_host, const int64_t* ids_cap_host, int n_off,
+                               void* const* off_dst_host, const void* const* off_src_host, const int64_t* off_nnz_host,
+                               const int64_t* off_cap_host, int64_t n, int64_t bucket, int idx_bytes, void* graph_exec,
+                               int sync_first, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Strided block copy = torch.cat / torch.split along dim 1 without ATen:
  *   for k < nblk:  dst_host[k][m*dst_ld_host[k] + c] = src_host[k][m*src_ld_host[k] + c],  m < M, c < width_host[k]
  * Uses: the "cat" interaction R = cat([x] + ly, 1) (dlrm_s_pytorch.py:505-507) when the features do not already sit
