@@ -2,23 +2,13 @@
 // the interact_narrow*.hip files share: the selector hand-off, the kernarg tables' way into LDS, the dR row staging, the grid rule and the host-side
 // argument checks.  The D = 128 pipeline built on these is gather_pipeline.h; the narrow kernels use this header alone.
 #pragma once
-#include "common.h"
+#include "interact_tiles.h"      // the typedefs, pair_pos and the forward MFMA section
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) char gchar;          // pointers rebuilt from integers: tag them global (global_*, not flat_* accesses)
-typedef __attribute__((address_space(1))) floatx4 gfloatx4;
 
 constexpr int GC_MAXF = 32;                 // feature slots of an argument block
 constexpr int GC_WAVES = 4;                 // waves of a workgroup: one per SIMD
 constexpr unsigned GC_BAD = 0xFFFFFFFFu;    // row selector of an out-of-range id (tables have at most 0xFFFFFFFF rows: never a valid row)
-
-// position of the pair (i, j), j <= i, in the flattened interaction output — as interact.hip: bit 0 = with the diagonal, bit 1 = torchrec order
-__device__ __forceinline__ int pair_pos(int i, int j, int F, int mode) {
-    if (mode & 2) return j * F - j * (j + 1) / 2 + (i - j - 1);
-    return ((mode & 1) ? i * (i + 1) / 2 : i * (i - 1) / 2) + j;
-}
 
 // fma(1, v, +0): the lookup kernels' sum of a bag of one row without per-sample weights (-0.0 becomes +0.0)
 __device__ __forceinline__ float bag1(float v) { return __builtin_fmaf(1.0f, v, 0.f); }

@@ -2,9 +2,10 @@
 //
 // The kernels widen / dequantise / compose the table rows of a sample into the wave-private swizzled fp32 LDS image of
 //   interact_{fwd,bwd}_dma_kernel (interact.hip: 16-byte slot q of row r holds quad q ^ (r & 15); row 0 is x, rows F.. are zero) and run
-//   those kernels' fragment-read / MFMA / store sections on it unchanged, so the products have the summation order of every D = 128
-//   interaction kernel.  What a table kind is — bf16 (interact_bf16.hip), row-wise quantised (interact_quant.hip), quotient-remainder
-//   (interact_qr.hip) — is the source type S; everything here is the same for all of them.
+//   those kernels' fragment-read / MFMA / store sections on it unchanged (the forward's MFMA section IS theirs: tile_fwd_mfma of
+//   interact_tiles.h), so the products have the summation order of every D = 128 interaction kernel.  What a table kind is — bf16
+//   (interact_bf16.hip), row-wise quantised (interact_quant.hip), quotient-remainder (interact_qr.hip) — is the source type S; everything
+//   here is the same for all of them.
 //
 // Pipeline (per wave, four waves per workgroup = one per SIMD, no barrier in the sample loop, two images per wave): at the top of sample
 //   n the rows (and x, and the dR row) of sample n + 1 are issued into registers from selectors that were loaded during sample n - 1, then
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256) void gather_fwd_kernel(typename S::Args ba, co
         const Sel<IT> seln = sel_load<IT>(bl, s2 < B ? s2 : last);
 
         const char* my = img0 + cur * IMGB;
-        // ---- the fragment-read / MFMA section of interact_fwd_dma_kernel (interact.hip) ----
+        // ---- the fragment reads of interact_fwd_dma_kernel (interact.hip), then the MFMA section both share ----
         float4 fr[NB][BI_D / 16];
 #pragma unroll
         for (int r = 0; r < NB; ++r)
@@ -125,22 +126,7 @@ __global__ __launch_bounds__(256) void gather_fwd_kernel(typename S::Args ba, co
         const float4 xrow = *(const float4*)(my + (lane & 31) * 16);
         __builtin_amdgcn_sched_barrier(0);      // all fragment reads (and the next sample's loads) in front of the first MFMA
         floatx4 acc[NPAIR][2];
-#pragma unroll
-        for (int p = 0; p < NPAIR; ++p) { acc[p][0] = (floatx4){0.f, 0.f, 0.f, 0.f}; acc[p][1] = (floatx4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int s = 0; s < BI_D / 16; ++s) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int r = 0; r < NB; ++r)
-#pragma unroll
-                    for (int c = 0; c <= r; ++c) {
-                        const float av = e == 0 ? fr[r][s].x : e == 1 ? fr[r][s].y : e == 2 ? fr[r][s].z : fr[r][s].w;
-                        const float bv = e == 0 ? fr[c][s].x : e == 1 ? fr[c][s].y : e == 2 ? fr[c][s].z : fr[c][s].w;
-                        acc[r * (r + 1) / 2 + c][e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[r * (r + 1) / 2 + c][e & 1], 0, 0, 0);
-                    }
-            }
-        }
+        tile_fwd_mfma<NB, BI_D / 16>(acc, fr);      // interact_tiles.h: the summation order of every one of these kernels
 
         // only now are the next sample's registers touched (the first rule of the header)
         S::template image_write<NP>(img0 + (cur ^ 1) * IMGB, vn, bl, xn, lane, ba);

@@ -19,25 +19,9 @@
 #include <string.h>
 #include <algorithm>
 #include <type_traits>
-#include "common.h"
+#include "interact_tiles.h"      // the typedefs, pair_pos and the forward MFMA section, shared with the fused lookup + interaction kernels
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-// pointers that round-trip through LDS as integers lose their address space; tag them global so
-// the loads/stores are global_* (not flat_*) instructions
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) floatx4 gfloatx4;
-typedef __attribute__((address_space(1))) char gchar;          // a pointer rebuilt from an integer table is GENERIC unless told otherwise: its stores
-                                                               // would be FLAT instructions, which also count on lgkmcnt — every LDS wait then waits for them
-
-// position of the pair (i, j), j <= i, in the flattened interaction output.  `self` is a mode word: bit 0 = pairs include the
-// diagonal (--arch-interaction-itself), bit 1 = torchrec order — torch.triu_indices(F, F, offset=1), i.e. pair (j, i) of the
-// upper triangle enumerated row by row (torchrec InteractionArch) — instead of the reference's tril order (dlrm_s_pytorch.py:499-501).
-__device__ __forceinline__ int pair_pos(int i, int j, int F, int mode) {
-    if (mode & 2) return j * F - j * (j + 1) / 2 + (i - j - 1);
-    return ((mode & 1) ? i * (i + 1) / 2 : i * (i - 1) / 2) + j;
-}
 
 #define DLRM_MAX_FEATURES 64
 struct FeatArgs {
@@ -550,8 +534,6 @@ __global__ __launch_bounds__(320) void interact_fwd_dma_kernel(FeatArgs fa, Gath
         // (the scheduler sinks each k-step's two reads to just before its 12 MFMAs — one wave per SIMD, so those LDS round trips are exposed.
         // Pinning all reads in front of the first MFMA with a scheduling fence: round 5 measured the kernel 195 -> 188 us and the step no
         // faster (profiles/round5/interact_frags_first_ab.txt) and left it out; end of round 6: 0.196-0.198 -> 0.194 ms again, adopted below)
-        // the tile pairs advance together, one k-substep at a time: consecutive MFMAs are independent, the two accumulators of a
-        // pair (even / odd substeps, summed at the end — the summation order of every version of this kernel) are three issues apart
         // (x = image row 0, for R[:, 0:D]: read with the fragments, not as an exposed LDS round trip behind the MFMAs)
         const float4 xrow = *(const float4*)(my + (lane & 31) * 16);
 #ifndef DLRM_FWD_PIN
@@ -559,22 +541,7 @@ __global__ __launch_bounds__(320) void interact_fwd_dma_kernel(FeatArgs fa, Gath
 #endif
         if (DLRM_FWD_PIN) __builtin_amdgcn_sched_barrier(0);      // all fragment reads in front of the first MFMA (end of round 6: adopted)
         floatx4 acc[NPAIR][2];
-#pragma unroll
-        for (int p = 0; p < NPAIR; ++p) { acc[p][0] = (floatx4){0.f, 0.f, 0.f, 0.f}; acc[p][1] = (floatx4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int s = 0; s < IDMA_D / 16; ++s) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int r = 0; r < NB; ++r)
-#pragma unroll
-                    for (int c = 0; c <= r; ++c) {
-                        const float av = e == 0 ? fr[r][s].x : e == 1 ? fr[r][s].y : e == 2 ? fr[r][s].z : fr[r][s].w;
-                        const float bv = e == 0 ? fr[c][s].x : e == 1 ? fr[c][s].y : e == 2 ? fr[c][s].z : fr[c][s].w;
-                        acc[r * (r + 1) / 2 + c][e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[r * (r + 1) / 2 + c][e & 1], 0, 0, 0);
-                    }
-            }
-        }
+        tile_fwd_mfma<NB, IDMA_D / 16>(acc, fr);      // interact_tiles.h: the summation order of every one of these kernels
         float* Rb = R + b * ldr;
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) {

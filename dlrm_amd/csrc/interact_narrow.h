@@ -24,10 +24,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(1))) float gfloat;
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) floatx2 gfloatx2;
-
 template <int D, int NB> struct NGeom {
     static constexpr int LPR = D / 4;                           // lanes per row
     static constexpr int RPP = 64 / LPR;                        // rows per pass

@@ -40,7 +40,6 @@
 
 namespace {
 
-typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float f16_bits_to_f32(unsigned h) {
